@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the RAW image chain on MI355X, with the roofline of its dominant kernel
-and the CPU baseline beside it.
+(and, with --full, the CPU baseline beside it).
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched by
 torch.distributed.run with one rank per GPU -- or called plainly, in which case it launches its N ranks itself
@@ -17,6 +17,12 @@ every rank runs its own batch); RCCL is used only for the barrier and the max-ov
 Other workloads (for development, not the driver's line): --workload chain (configs 2a: the fused
 per-pixel kernel alone), config3 (1920x1200 gbrg8, ccc + enhancer), config5 (3840x2160 debayer +
 remap).
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, ms_per_step, and the roofline
+of the dominant kernel from the HIP events recorded around the timed launches).  Everything that takes runs of its
+own comes with --full only: the live PMC passes (roofline.traffic / valu / per_kernel), the memory-rate variant,
+the remap components, the streaming probes (roofline.empirical), the CPU baseline, and for N > 1 the scatter and
+end-to-end leg.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 """
 import argparse
 import json
@@ -72,6 +78,10 @@ def parse_args():
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
     ap.add_argument("--batch-total", type=int, default=0, help="N > 1: frames of the ONE batch rank 0 owns in the end-to-end leg "
                     "(scatter -> every rank processes the shard it received -> checksums compared); 0 = --batch.  BASELINE config 5: 512")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement (live PMC passes, memory-rate variant, remap "
+                    "components, streaming probes, CPU baseline; N > 1: scatter + end-to-end leg); --no-* switch single ones off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the output of the last timed step (rank 0) as .npy "
+                    "files under DIR: a seeded sample of its values and per-frame checksums")
     return ap.parse_args()
 
 
@@ -305,6 +315,33 @@ def frame_checksums(images):
     return out
 
 
+DUMP_SAMPLE = 1 << 22  # values in output_sample.npy: 16 MiB of float32
+DUMP_SEED = 0
+
+
+def dump_outputs(path, images):
+    """--dump-outputs: what the timed path computed in its last step -- the [frames, rows, cols, channels] uint8 images a caller
+    of apply_device receives -- as .npy files under `path`, about 16 MiB in all:
+      output_sample.npy           float32, DUMP_SAMPLE values of the whole batch at flat indices drawn with a fixed seed (sorted),
+                                  or every value in flat order when the batch holds fewer;
+      output_frame_checksums.npy  float64 [frames, 2], per frame the sum of its values and a position-weighted sum (frame_checksums:
+                                  both exact in float64), so that every pixel of every frame is covered;
+      output_shape.npy            float64, the shape of the batch.
+    The inputs are synthetic and seeded: two runs with the same arguments see the same frames."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = images.numel()
+    flat = images.reshape(-1)
+    if n <= DUMP_SAMPLE:
+        sample = flat
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE))
+        sample = flat[torch.from_numpy(idx).to(images.device)]
+    np.save(os.path.join(path, "output_sample.npy"), sample.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "output_frame_checksums.npy"), np.asarray(frame_checksums(images), np.float64).reshape(-1, 2))
+    np.save(os.path.join(path, "output_shape.npy"), np.asarray(images.shape, np.float64))
+
+
 def end_to_end_leg(args, pipe, frames, pattern, frame_shape, rank, world, backend, barrier):
     """N > 1: ONE batch that originates on rank 0 goes through the whole multi-GPU path (VERDICT round 4 missing-3; BASELINE
     configs 4 / 5): scatter_frames -> every rank processes THE SHARD IT RECEIVED -> per-frame checksums are gathered and
@@ -386,7 +423,7 @@ def memory_rate_variant(args):
     dominant kernel.  Never part of the timed region of the headline."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "default_chain", "--steps", "10", "--warmup", "2", "--batch", str(args.batch),
-           "--no-cpu-baseline", "--no-hbm-probe"]
+           "--full", "--no-cpu-baseline", "--no-hbm-probe"]
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=600, check=False)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -596,6 +633,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     prof = pipe.profile_end()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     from raw_image_pipeline_amd import sharding
     own_elapsed = elapsed
     elapsed = sharding.max_over_ranks(elapsed)  # the job is as slow as its slowest rank
@@ -681,7 +720,7 @@ def main():
             pass
 
     scatter = None
-    if dist_on:
+    if dist_on and args.full:
         # The only data movement between ranks on this path: the frame scatter when a batch originates on one rank.
         # Timed outside the steady state (it is bounded by the source GPU's xGMI egress) and reported apart.
         # It runs LAST and under a watchdog: the steady-state numbers above are complete at this point, so a point-to-point
@@ -732,7 +771,7 @@ def main():
         if dist_on:
             dist.destroy_process_group()
         return
-    if world == 1 and not args.no_pmc:
+    if world == 1 and args.full and not args.no_pmc:
         live, valu_live, why = live_pmc_traffic(args, dom)
         if valu_live is not None:
             allk = valu_live.pop("all_classes", {})
@@ -767,12 +806,12 @@ def main():
                                           "(separate passes, KiB, x2 on FETCH_SIZE for gfx950), median launch of the %s kernels" % dom)
         elif roofline.get("traffic_source"):
             roofline["traffic_source"] += "; live PMC pass unavailable (%s)" % why
-    if world == 1 and not args.no_pmc and args.workload == "config2":
+    if world == 1 and args.full and not args.no_pmc and args.workload == "config2":
         roofline["memory_rate_variant"] = memory_rate_variant(args)
         comp = remap_components(args)
         if comp is not None:
             roofline.setdefault("per_kernel", {}).setdefault("remap", {})["components"] = comp
-    if world == 1 and not args.no_hbm_probe:
+    if world == 1 and args.full and not args.no_hbm_probe:
         # what this box's HBM actually delivers to a plain streaming kernel, beside the 8 TB/s spec
         del out
         probe = hbm_probe(pipe, torch)
@@ -809,7 +848,7 @@ def main():
         multi["single_gpu_reference"] = n1
         multi["retained_vs_n1"] = round(fps / world / n1["value"], 4) if n1 else None
         result.update(multi)
-    if not args.no_cpu_baseline and world == 1 and args.workload == "config2":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "config2":
         result["cpu_baseline"] = cpu_baseline(width, height, pattern, args.cpu_seconds)
     elif world == 1:
         result["cpu_baseline"] = None

@@ -118,7 +118,7 @@ def test_bench_two_rank_rehearsal_prints_one_json_line():
     env = dict(os.environ, RIP_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29611", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", "--no-hbm-probe", "--no-pmc"]
+           "--full", "--no-cpu-baseline", "--no-hbm-probe", "--no-pmc"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -142,7 +142,7 @@ def test_bench_config5_end_to_end_leg_with_a_batch_total(rip_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(RIP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "config5", "--steps", "1", "--warmup", "1", "--batch", "4",
-           "--batch-total", "12", "--no-cpu-baseline", "--no-hbm-probe", "--no-pmc"]
+           "--batch-total", "12", "--full", "--no-cpu-baseline", "--no-hbm-probe", "--no-pmc"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -179,7 +179,7 @@ def test_bench_single_rank_rccl_communicator_runs_every_multi_rank_code_path():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "RIP_BENCH_BACKEND")}
     env.update(RIP_DIST_FORCE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29633", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", "--no-hbm-probe", "--no-pmc"]
+           "--full", "--no-cpu-baseline", "--no-hbm-probe", "--no-pmc"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -213,6 +213,44 @@ def test_bench_refuses_more_gpus_than_the_node_has():
     env2 = dict(env, RIP_BENCH_BACKEND="gloo", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     r = subprocess.run(cmd[:3] + ["2"] + cmd[4:], env=env2, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_last_step(rip_lib, tmp_path):
+    """A plain `bench.py --gpus 1` (no --full) prints the headline line without the side measurements, and --dump-outputs
+    writes what its last timed step computed: shape, per-frame checksums and the seeded sample all equal the same frames
+    run through a handle of this process configured as bench.py configures it."""
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    batch = 4
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "RIP_BENCH_BACKEND", "RIP_DIST_FORCE")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(batch),
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j["n_gpus"] == 1 and j["steps"] == 3 and j["ms_per_step"] > 0
+    assert abs(j["value"] - batch / (j["ms_per_step"] * 1e-3)) / j["value"] < 1e-3
+    assert j["cpu_baseline"] is None and "empirical" not in j["roofline"] and "memory_rate_variant" not in j["roofline"]
+
+    from raw_image_pipeline_amd import RawImagePipeline
+    w, h = 2448, 2048
+    pipe = RawImagePipeline(False, "", "", "", device=0)
+    pattern, _ = bench.configure(pipe, "config2", w, h)
+    want = pipe.apply_device(torch.from_numpy(bench.make_frames(w, h, pattern, batch, 0)).cuda(), pattern)
+    torch.cuda.synchronize()
+    shape = np.load(str(tmp_path / "output_shape.npy"))
+    assert shape.dtype == np.float64 and tuple(int(v) for v in shape) == tuple(want.shape)
+    sums = np.load(str(tmp_path / "output_frame_checksums.npy"))
+    assert sums.dtype == np.float64 and np.array_equal(sums, np.asarray(bench.frame_checksums(want), np.float64))
+    sample = np.load(str(tmp_path / "output_sample.npy"))
+    flat = want.reshape(-1)
+    assert flat.numel() > bench.DUMP_SAMPLE and sample.dtype == np.float32 and sample.shape == (bench.DUMP_SAMPLE,)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, flat.numel(), size=bench.DUMP_SAMPLE))
+    assert np.array_equal(sample, flat[torch.from_numpy(idx).cuda()].float().cpu().numpy())
 
 
 def test_config3_sequence_of_64_frames_1920x1200_tracks_the_drifting_tint(gpu_pipe, oracle):

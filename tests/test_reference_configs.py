@@ -1,5 +1,5 @@
-"""The reference's OWN configuration files through this repository's loaders (CPU; skipped where the reference tree is not
-mounted, i.e. on the GPU box; the files are read in place, nothing is copied).
+"""The reference's OWN configuration files through this repository's loaders (CPU).  The four YAML files of the reference's
+raw_image_pipeline/config/ are stored unchanged as fixtures under tests/golden/reference/config (MIT licence beside them).
 
 A user of the reference starts it as `RawImagePipeline(use_gpu, params_path, calibration_path, color_calibration_path)`
 (raw_image_pipeline.hpp:40-41, .cpp:27-40) with the YAML files of raw_image_pipeline/config/.  A drop-in has to accept
@@ -14,12 +14,10 @@ import yaml
 
 from raw_image_pipeline_amd import RawImagePipeline
 
-CFG = "/root/reference/raw_image_pipeline/config"
-PARAMS = CFG + "/pipeline_params_example.yaml"
-COLOR = CFG + "/alphasense_color_calib_example.yaml"
-CALIBS = [CFG + "/alphasense_calib_1.6mp_example.yaml", CFG + "/alphasense_calib_example.yaml"]
-
-pytestmark = pytest.mark.skipif(not os.path.exists(PARAMS), reason="reference tree not mounted (GPU box)")
+CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "config")
+PARAMS = os.path.join(CFG, "pipeline_params_example.yaml")
+COLOR = os.path.join(CFG, "alphasense_color_calib_example.yaml")
+CALIBS = ["alphasense_calib_1.6mp_example.yaml", "alphasense_calib_example.yaml"]
 
 
 def _yaml(path):
@@ -27,8 +25,9 @@ def _yaml(path):
         return yaml.safe_load(f)
 
 
-@pytest.mark.parametrize("calib_path", CALIBS)
-def test_four_argument_constructor_with_the_reference_config_files(oracle, calib_path):
+@pytest.mark.parametrize("calib_name", CALIBS)
+def test_four_argument_constructor_with_the_reference_config_files(oracle, calib_name):
+    calib_path = os.path.join(CFG, calib_name)
     prm, cal, col = _yaml(PARAMS), _yaml(calib_path), _yaml(COLOR)
     p = RawImagePipeline(False, PARAMS, calib_path, COLOR, device=-1)  # parameter handling needs no GPU
     # enable flags (loadParams, .cpp:56-160)

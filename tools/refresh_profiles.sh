@@ -14,7 +14,7 @@ python "$ROOT/tools/collect_pmc.py" "$OUT/pmc" config2 chain default_chain confi
 for wl in config2 chain default_chain config3 config5; do
   python "$ROOT/bench.py" --workload $wl --steps 20 --no-cpu-baseline --no-hbm-probe --no-pmc 2>/dev/null | tail -1 > "$OUT/bench_$wl.json"
 done
-python "$ROOT/bench.py" 2>/dev/null | tail -1 > "$OUT/bench_default.json"
+python "$ROOT/bench.py" --full 2>/dev/null | tail -1 > "$OUT/bench_default.json"
 python "$ROOT/tools/collect_pmc_sq.py" "$OUT/sq" config2 chain default_chain config3 config5 > "$OUT/sq.log" 2>&1
 "$ROOT/tools/probes/bin/valu_probe2" > "$OUT/valu_probe2.txt" 2>&1
 "$ROOT/tools/probes/bin/valu_probe3" > "$OUT/valu_probe3.txt" 2>&1

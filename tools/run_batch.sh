@@ -83,7 +83,7 @@ case $exp in
     python tools/probes/remap_exp_probe.py --workload chain --rounds 3 --tunable chain_frames=12,16,24,32,64 2>&1 | grep "^mask" | sed "s/^/chain /" | tee $out/frames.log
     python tools/probes/remap_exp_probe.py --workload config3 --size 1920x1200 --rounds 3 --tunable chain_frames=8,16,24,32,64 2>&1 | grep "^mask" | sed "s/^/config3 /" | tee -a $out/frames.log
     python tools/probes/remap_exp_probe.py --workload config2 --rounds 3 --tunable chain_frames=16,32 2>&1 | grep "^mask" | sed "s/^/config2 /" | tee -a $out/frames.log
-    python bench.py --no-cpu-baseline 2>&1 | tail -1 | tee $out/bench.log ;;
+    python bench.py --full --no-cpu-baseline 2>&1 | tail -1 | tee $out/bench.log ;;
   step_ab)       # the whole config 2 step, round 5's library (variants/r5.so) beside the tree's, one process
     python tools/probes/remap_exp_probe.py --workload config2 --libs r5=$V/r5.so,new= --rounds 4 2>&1 | grep "^mask" | tee $out/ab.log ;;
   step_sweep)    # tunables inside the whole config 2 step (the chain behaves differently in front of the remap)
@@ -153,8 +153,8 @@ case $exp in
   suite)         # whole GPU suite + smoke
     python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $out/pytest.log
     python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 | tee $out/smoke.log ;;
-  bench)         # default line (+ any extra bench.py arguments)
-    python bench.py "$@" 2>&1 | tee $out/bench.log ;;
+  bench)         # the --full line (+ any extra bench.py arguments)
+    python bench.py --full "$@" 2>&1 | tee $out/bench.log ;;
   ab)            # tools/ab_chain.py run <args>: library variants in separate processes
     python tools/ab_chain.py run "$@" 2>&1 | tee $out/ab.log ;;
   sh)            # free-form: the rest of the line is the command
