@@ -314,6 +314,14 @@ rip_status rip_debug_atan(rip_pipeline* p, const double* in, double* out, int n)
  * border pixels, largest LDS footprint of a tile's source rectangle in bytes, largest rectangle width, height, 1 if the
  * plan was compiled on the device, tile width, tile height}.  Needs a loaded calibration and a device. */
 rip_status rip_debug_plan_info(rip_pipeline* p, int src_rows, int src_cols, int info[9]);
+/* Test hook: the part of a src_rows x src_cols intermediate image the undistortion reads, as the fused Bayer chain kernel
+ * walks it in front of the remap (items of 4 x 2 pixels in its input's coordinates, flipped by flip_angle, 0 or 180):
+ * info = {items of the whole frame, items in the footprint, row pairs with a footprint, items per frame the last chain
+ * launch of this handle walked (0 before the first)}.  intervals (optional, capacity_pairs >= src_rows / 2): per row pair of
+ * the chain's input the items [lo, hi) it walks, (0, 0) for none.  Works on RIP_DEVICE_NONE handles (footprint of the
+ * host-built maps); on device handles it compiles the plan as a frame would. */
+rip_status rip_debug_chain_footprint(rip_pipeline* p, int src_rows, int src_cols, int flip_angle, int info[4], int* intervals,
+                                     int capacity_pairs);
 /* Test hook for the debug dumps: writes image (rows x cols x channels bytes, channels 1 or 3 = BGR) to path as the PNG
  * writer of rip_set_debug does, after the reference's min-max normalisation when normalize != 0.  No device needed;
  * p may be NULL. */

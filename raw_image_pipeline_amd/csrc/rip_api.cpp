@@ -358,6 +358,12 @@ struct rip_pipeline {
   bool plan_uploaded = false;
   bool plan_on_device = false;  // compiled by remap_plan_kernel: plan.words / tiles / border stay empty on the host
   int plan_n_border = 0;
+  DevBuf d_plan_fp;  // the device compiler's footprint (lo, hi per source row pair), read back into plan.fp_lo / fp_hi
+  // the fast chain kernel's items inside the plan's footprint (rip::chain_footprint_items), uploaded once per (plan, flip)
+  DevBuf d_chain_items;
+  int chain_items_flip = -1;  // -1: not built for the current plan
+  int chain_items_n = 0;
+  int last_chain_walked = 0;  // items per frame the last chain launch of run_batch walked (rip_debug_chain_footprint)
   bool use_tiled_remap = true;
   int last_batch_frames = 0;
   bool work_enqueued = false;  // some frame call has put work on `stream` (rip_set_stream orders a new stream behind it)
@@ -404,7 +410,7 @@ struct rip_pipeline {
     if (dl_stream) (void)hipStreamDestroy(dl_stream);
     for (DevBuf* b : {&d_tabs, &d_vig_image, &d_map, &d_map_ckpt, &d_filter_fft, &d_bias_fft, &d_accum, &d_ccc_state, &d_geom, &d_stats, &d_wb,
                       &d_hist, &d_work, &d_rowbest, &d_argmax, &d_mid, &d_in, &d_out, &d_tap_deb, &d_tap_col, &d_vig, &d_plan_words,
-                      &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_dbg})
+                      &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg})
       b->release();
   }
 };
@@ -507,6 +513,7 @@ void ensure_plan(rip_pipeline* p, int src_rows, int src_cols) {
   if (!p->plan.valid || p->plan.src_rows != src_rows || p->plan.src_cols != src_cols || p->plan.drows != m.dist_h ||
       p->plan.dcols != m.dist_w) {
     p->plan_on_device = false;
+    p->chain_items_flip = -1;
     if (maps_on_device(p) && !p->plan_on_host) {
       // Compile the plan where the maps are (rip_maps.hip remap_plan_kernel: one workgroup per tile; the same words, tile
       // rectangles and border pixels as rip::compile_remap_plan, the border list in another order): no 8 B/px map read-back,
@@ -540,9 +547,31 @@ void ensure_plan(rip_pipeline* p, int src_rows, int src_cols) {
       bp.border_cap = border_cap;
       bp.counters = p->d_plan_counters.as<unsigned>();
       rip::launch_remap_plan_build(bp, p->stream);
+      // the footprint of the same quantised taps (rip::compile_remap_footprint's hull): lo starts at 0x7F7F7F7F, hi at 0
+      const int pairs = (src_rows + 1) / 2;
+      p->d_plan_fp.reserve(2 * (size_t)pairs * sizeof(int));
+      HIP_CHECK(hipMemsetAsync(p->d_plan_fp.ptr, 0x7F, (size_t)pairs * sizeof(int), p->stream));
+      HIP_CHECK(hipMemsetAsync(p->d_plan_fp.as<int>() + pairs, 0, (size_t)pairs * sizeof(int), p->stream));
+      rip::RemapFootprintParams fq = {};
+      fq.map_xy = bp.map_xy;
+      fq.drows = pl.drows;
+      fq.dcols = pl.dcols;
+      fq.src_rows = src_rows;
+      fq.src_cols = src_cols;
+      fq.tiles_x = pl.tiles_x;
+      fq.tiles_y = pl.tiles_y;
+      fq.lo = p->d_plan_fp.as<int>();
+      fq.hi = p->d_plan_fp.as<int>() + pairs;
+      rip::launch_remap_footprint(fq, p->stream);
+      pl.fp_lo.resize(pairs);
+      pl.fp_hi.resize(pairs);
       unsigned counters[4] = {0, 0, 0, 0};
       HIP_CHECK(hipMemcpyAsync(counters, p->d_plan_counters.ptr, sizeof(counters), hipMemcpyDeviceToHost, p->stream));
+      HIP_CHECK(hipMemcpyAsync(pl.fp_lo.data(), fq.lo, (size_t)pairs * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+      HIP_CHECK(hipMemcpyAsync(pl.fp_hi.data(), fq.hi, (size_t)pairs * sizeof(int), hipMemcpyDeviceToHost, p->stream));
       HIP_CHECK(hipStreamSynchronize(p->stream));
+      for (int i = 0; i < pairs; i++)
+        if (pl.fp_lo[i] >= pl.fp_hi[i]) pl.fp_lo[i] = INT32_MAX, pl.fp_hi[i] = 0;  // the host compiler's "no tap" form
       if (counters[0] <= border_cap) {
         p->plan_n_border = (int)counters[0];
         pl.max_lds_bytes = counters[1];
@@ -574,6 +603,26 @@ void ensure_plan(rip_pipeline* p, int src_rows, int src_cols) {
     HIP_CHECK(hipStreamSynchronize(p->stream));
     p->plan_uploaded = true;
   }
+}
+
+// The fast chain kernel's items whose output the remap reads (rip::chain_footprint_items on the current plan's footprint), on
+// the device; uploaded once per (plan, flip).  Returns how many there are, or -1 when the footprint covers more than 95 % of
+// the frame (balance 1, wide fields of view): the dense walk is as good there and needs no table.
+int ensure_chain_items(rip_pipeline* p, int rows, int cols, int flip_angle) {
+  if (p->chain_items_flip != flip_angle) {
+    std::vector<uint32_t> items;
+    rip::chain_footprint_items(p->plan.fp_lo, p->plan.fp_hi, rows, cols, flip_angle, items);
+    const long long dense = (long long)(rows / 2) * (cols / 4);
+    p->chain_items_n = (long long)items.size() * 20 > dense * 19 ? -1 : (int)items.size();
+    if (p->chain_items_n >= 0) {
+      p->d_chain_items.reserve(std::max<size_t>(4, items.size() * sizeof(uint32_t)));
+      if (!items.empty())
+        HIP_CHECK(hipMemcpyAsync(p->d_chain_items.ptr, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+      HIP_CHECK(hipStreamSynchronize(p->stream));
+    }
+    p->chain_items_flip = flip_angle;
+  }
+  return p->chain_items_n;
 }
 
 void ensure_maps(rip_pipeline* p) {
@@ -955,6 +1004,15 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
     chain_step = mid_pitch;
     chain_stride = mid_frame;
   }
+  // In front of the remap, with no tap asking for the whole intermediate image, the fast Bayer kernel computes only the items
+  // whose pixels the remap reads (its plan's footprint: the corners a fisheye map never samples are ~21 % of config 2's frame).
+  // The statistics pass above it still reads every pixel: the white-balance estimates are defined over the whole frame.
+  int chain_items = -1;
+  if (tiled && !fused && !direct && chain_dst == p->d_mid.as<uint8_t>() && !d_tap_deb && !d_tap_col && p->tn.chain_footprint &&
+      pl.src_kind == rip::SRC_BAYER && pl.channels == 3 && (pl.flip_angle == 0 || pl.flip_angle == 180) && rows % 2 == 0 &&
+      cols % 4 == 0 && rows / 2 <= 65535 && cols / 4 <= 65535 && rows == pl.mid_rows && cols == pl.mid_cols &&
+      p->plan.fp_lo.size() == (size_t)(rows + 1) / 2)
+    chain_items = ensure_chain_items(p, rows, cols, pl.flip_angle);
   if (pl.stage_bits & rip::ST_VIG) ensure_vignette(p, pl.mid_rows, pl.mid_cols);
 
   // ---- frame groups -------------------------------------------------------------------------------------
@@ -1127,6 +1185,11 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
     c.tap = d_tap_deb ? d_tap_deb + (size_t)f0 * tap_frame : nullptr;
     c.tap_frame_stride = tap_frame;
     c.deal = pl.remap ? -1 : 0;  // hint for launch_chain: the remap gathers from this image next (Tunables::chain_deal)
+    if (chain_items >= 0 && rip::chain_uses_fast_path(c)) {
+      c.item_list = p->d_chain_items.as<uint32_t>();
+      c.n_list_items = chain_items;
+    }
+    p->last_chain_walked = c.item_list ? chain_items : (rows / 2) * (cols / 4);
     // overlap_mode 2: only the statistics of this group share the chip with the remap of the previous one; the chain waits
     if (back != front && p->tn.overlap_mode == 2 && g > 0) HIP_CHECK(hipStreamWaitEvent(front, p->ovl_events[groups + g - 1], 0));
     {
@@ -1294,6 +1357,7 @@ Tunables tunables_from_env() {
   if (const char* e = std::getenv("RIP_REMAP_DEAL")) t.remap_deal = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("RIP_CHAIN_DEAL")) t.chain_deal = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("RIP_REMAP_FUSED")) t.remap_fused = std::atoi(e) != 0;
+  if (const char* e = std::getenv("RIP_CHAIN_FOOTPRINT")) t.chain_footprint = std::atoi(e) != 0;
   if (const char* e = std::getenv("RIP_CHAIN_NT")) t.chain_nt = std::atoi(e);
   t.ccc_lds_hist_min = positive("RIP_CCC_LDS_HIST_MIN", t.ccc_lds_hist_min);
   t.overlap_groups = positive("RIP_OVERLAP_GROUPS", t.overlap_groups);
@@ -2130,6 +2194,45 @@ rip_status rip_debug_plan_info(rip_pipeline* p, int src_rows, int src_cols, int 
   });
 }
 
+rip_status rip_debug_chain_footprint(rip_pipeline* p, int src_rows, int src_cols, int flip_angle, int info[4], int* intervals,
+                                     int capacity_pairs) {
+  return guarded(p, [&] {
+    need(p);
+    if (!info) throw InvalidArgument("null info");
+    if (flip_angle != 0 && flip_angle != 180) throw InvalidArgument("the footprint walk serves flips of 0 and 180 degrees");
+    if (src_rows < 2 || src_cols < 4 || src_rows % 2 || src_cols % 4 || src_rows / 2 > 65535 || src_cols / 4 > 65535)
+      throw InvalidArgument("the footprint walk needs an even number of rows and a multiple of 4 columns");
+    const int pairs = src_rows / 2, groups = src_cols / 4;
+    if (intervals && capacity_pairs < pairs) throw InvalidArgument("intervals: one (lo, hi) per row pair");
+    std::vector<int> lo, hi;
+    if (p->device == RIP_DEVICE_NONE) {  // no plan on such a handle: the host compiler's footprint of the host-built maps
+      ensure_host_maps(p);
+      rip::compile_remap_footprint(p->h_map.data(), p->m.dist_h, p->m.dist_w, src_rows, src_cols, lo, hi);
+    } else {
+      DeviceGuard device_guard(p->device);
+      ensure_plan(p, src_rows, src_cols);
+      lo = p->plan.fp_lo;
+      hi = p->plan.fp_hi;
+    }
+    std::vector<uint32_t> items;
+    rip::chain_footprint_items(lo, hi, src_rows, src_cols, flip_angle, items);
+    int touched = 0;
+    for (size_t i = 0; i < lo.size(); i++) touched += lo[i] < hi[i] ? 1 : 0;
+    info[0] = pairs * groups;
+    info[1] = (int)items.size();
+    info[2] = touched;
+    info[3] = p->last_chain_walked;
+    if (intervals) {
+      for (int i = 0; i < pairs; i++) intervals[2 * i] = intervals[2 * i + 1] = 0;
+      for (size_t k = 0; k < items.size(); k++) {  // each pair's items are one run [lo, hi) in ascending order
+        const int pr = (int)(items[k] >> 16), g = (int)(items[k] & 0xFFFFu);
+        if (k == 0 || (int)(items[k - 1] >> 16) != pr) intervals[2 * pr] = g;
+        intervals[2 * pr + 1] = g + 1;
+      }
+    }
+  });
+}
+
 rip_status rip_debug_atan(rip_pipeline* p, const double* in, double* out, int n) {
   if (!p) return RIP_ERR_INVALID_ARGUMENT;
   return guarded(p, [&] {
@@ -2172,6 +2275,7 @@ rip_status rip_set_tunable(rip_pipeline* p, const char* name, int value) {
     else if (n == "remap_per_cu") t.remap_per_cu = value;
     else if (n == "remap_frames") t.remap_frames = value;
     else if (n == "remap_fused") t.remap_fused = value;
+    else if (n == "chain_footprint") t.chain_footprint = value != 0;
     else if (n == "remap_exp") t.remap_exp = value;
     else if (n == "remap_deal") t.remap_deal = value;
     else if (n == "chain_deal") t.chain_deal = value;

@@ -97,7 +97,10 @@ __global__ __launch_bounds__(kBlock) void debayer16_kernel(Debayer16Params p) {
 // reverse the six planar dwords for the 180-degree flip -- 96 issue cycles per item that are gone: the pattern's column
 // parity and the flip are selectors of the demosaic's own v_perm_b32 (debayer_tile_sel), the row parity is one scalar
 // branch around four v_swap_b32.
-template <int BITS, int WB, int NT, bool PLAIN>
+// LIST: the items come from p.item_list (pair << 16 | grp; items_per_frame of them) instead of the dense split of the item number --
+// in front of the remap only the pixels it reads are computed (rip_host.hpp chain_footprint_items).  A compile-time variant, so
+// the dense kernel is the same code as without it.
+template <int BITS, int WB, int NT, bool PLAIN, bool LIST>
 __device__ __forceinline__ void fast_chunks(const ChainParams& p, const ItemMap& im, const int items_per_frame, const FastTabs<BITS>& tb,
                                             const CcRegs& cc, const HsvRegs& hr) {
   // Persistent workgroups: the LDS tables are loaded once and amortised over many chunks of
@@ -136,7 +139,13 @@ __device__ __forceinline__ void fast_chunks(const ChainParams& p, const ItemMap&
     const int item = chunk * NT + threadIdx.x;
     if (item >= items_per_frame) continue;
     int pair, grp;
-    im.split(item, pair, grp);
+    if constexpr (LIST) {
+      const uint32_t packed = p.item_list[item];
+      pair = (int)(packed >> 16);
+      grp = (int)(packed & 0xFFFFu);
+    } else {
+      im.split(item, pair, grp);
+    }
     const int y0 = pair * 2, x0 = grp * 4;
     const int xbase = flip180 ? p.cols - 4 - x0 : x0;
     float mask[2][4];
@@ -213,7 +222,7 @@ __device__ __forceinline__ void fast_chunks(const ChainParams& p, const ItemMap&
   }
 }
 
-template <int BITS, int WB, int NT>
+template <int BITS, int WB, int NT, bool LIST>
 __global__ __launch_bounds__(NT, fast_waves_per_simd<BITS>()) void chain_fast_kernel(ChainParams p, ItemMap im, int items_per_frame) {
   __shared__ FastTabs<BITS> tb;
   tb.template load<NT>(p.tabs, p.vig_image, p.hsv_gain);
@@ -224,9 +233,9 @@ __global__ __launch_bounds__(NT, fast_waves_per_simd<BITS>()) void chain_fast_ke
   __syncthreads();
   const bool bias = (BITS & ST_CC) != 0 && (p.cc_bias[0] != 0.f || p.cc_bias[1] != 0.f || p.cc_bias[2] != 0.f);
   if (p.tap == nullptr && !bias)
-    fast_chunks<BITS, WB, NT, true>(p, im, items_per_frame, tb, cc, hr);
+    fast_chunks<BITS, WB, NT, true, LIST>(p, im, items_per_frame, tb, cc, hr);
   else
-    fast_chunks<BITS, WB, NT, false>(p, im, items_per_frame, tb, cc, hr);
+    fast_chunks<BITS, WB, NT, false, LIST>(p, im, items_per_frame, tb, cc, hr);
 }
 
 
@@ -473,18 +482,25 @@ __global__ __launch_bounds__(512) void vig_image_kernel(const DevTables* tabs, u
   for (int i = threadIdx.x; i < (int)(sizeof(VigTabs) / 4); i += 512) image[i] = src[i];
 }
 
-template <int BITS, int WB>
-void launch_fast(const ChainParams& p, const ItemMap& im, int items, dim3 grid, hipStream_t stream, bool debug_occupancy) {
+template <int BITS, int WB, bool LIST>
+void launch_fast_as(const ChainParams& p, const ItemMap& im, int items, dim3 grid, hipStream_t stream, bool debug_occupancy) {
   constexpr int NT = fast_threads<BITS>();
   if (debug_occupancy) {  // development aid: resident workgroups per CU the runtime computes for this variant
     int nb = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, chain_fast_kernel<BITS, WB, NT>, NT, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, chain_fast_kernel<BITS, WB, NT, LIST>, NT, 0);
     hipFuncAttributes fa;
-    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(chain_fast_kernel<BITS, WB, NT>));
-    std::fprintf(stderr, "[rip] chain_fast_kernel<%d,%d,%d>: %d workgroups/CU, %d VGPR, %zu B LDS, grid %u x %u\n", BITS, WB, NT, nb,
-                 fa.numRegs, fa.sharedSizeBytes, grid.x, grid.y);
+    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(chain_fast_kernel<BITS, WB, NT, LIST>));
+    std::fprintf(stderr, "[rip] chain_fast_kernel<%d,%d,%d,%d>: %d workgroups/CU, %d VGPR, %zu B LDS, grid %u x %u\n", BITS, WB, NT, (int)LIST,
+                 nb, fa.numRegs, fa.sharedSizeBytes, grid.x, grid.y);
   }
-  hipLaunchKernelGGL((chain_fast_kernel<BITS, WB, NT>), grid, dim3(NT), 0, stream, p, im, items);
+  hipLaunchKernelGGL((chain_fast_kernel<BITS, WB, NT, LIST>), grid, dim3(NT), 0, stream, p, im, items);
+}
+template <int BITS, int WB>
+void launch_fast(const ChainParams& p, const ItemMap& im, int items, dim3 grid, hipStream_t stream, bool debug_occupancy) {
+  if (p.item_list != nullptr)
+    launch_fast_as<BITS, WB, true>(p, im, items, grid, stream, debug_occupancy);
+  else
+    launch_fast_as<BITS, WB, false>(p, im, items, grid, stream, debug_occupancy);
 }
 
 template <int BITS, int WB>
@@ -641,7 +657,9 @@ void launch_chain(const ChainParams& p_in, const Tunables& tn, hipStream_t strea
   }
   if (chain_uses_fast_path(p)) {
     ItemMap im{p.cols / 4, 1.0f / (float)(p.cols / 4)};
-    const int items = (p.rows / 2) * (p.cols / 4);
+    // with an item list (run_batch: in front of the remap) the launch walks only the listed items, in the same per-XCD ranges
+    const int items = p.item_list != nullptr ? p.n_list_items : (p.rows / 2) * (p.cols / 4);
+    if (items <= 0) return;
     const int nt = (p.stage_bits & ST_VIG) ? fast_threads<ST_VIG>() : fast_threads<0>();
     const long long chunks = (long long)((items + nt - 1) / nt);
     // persistent grid: at most 256 CUs x 8 x 256 threads, a multiple of 8 workgroups (one share per XCD; the kernel

@@ -743,6 +743,41 @@ size_t remap_tile_lds_bytes(int x0, int w, int h) {
   return pitch * (size_t)h;
 }
 
+void compile_remap_footprint(const float* map_xy, int drows, int dcols, int src_rows, int src_cols, std::vector<int>& lo,
+                             std::vector<int>& hi) {
+  const int pairs = (src_rows + 1) / 2;
+  lo.assign(pairs, INT32_MAX);
+  hi.assign(pairs, 0);
+  for (int y = 0; y < drows; y++)
+    for (int x = 0; x < dcols; x++) {
+      const float* m = map_xy + ((size_t)y * dcols + x) * 2;
+      const int sx = sat_s16(quantise_map(m[0]) >> 5), sy = sat_s16(quantise_map(m[1]) >> 5);
+      // the in-bounds taps of {sx, sx + 1} x {sy, sy + 1}: what the interior word or the per-tap border path reads
+      const int x0 = std::max(sx, 0), x1 = std::min(sx + 1, src_cols - 1);
+      const int y0 = std::max(sy, 0), y1 = std::min(sy + 1, src_rows - 1);
+      if (x0 > x1 || y0 > y1) continue;  // outside: no tap
+      for (int r = y0; r <= y1; r++) {
+        const int i = r >> 1;
+        lo[i] = std::min(lo[i], x0 >> 2);
+        hi[i] = std::max(hi[i], (x1 >> 2) + 1);
+      }
+    }
+}
+
+void chain_footprint_items(const std::vector<int>& lo, const std::vector<int>& hi, int rows, int cols, int flip_angle,
+                           std::vector<uint32_t>& items) {
+  items.clear();
+  const int pairs = rows / 2, groups = cols / 4;
+  const bool flip180 = flip_angle == 180;
+  for (int pair = 0; pair < pairs; pair++) {
+    const int fp = flip180 ? pairs - 1 - pair : pair;  // the row pair of the remap's source image this item writes
+    if (fp >= (int)lo.size() || lo[fp] >= hi[fp]) continue;
+    const int g_lo = std::max(0, flip180 ? groups - hi[fp] : lo[fp]);
+    const int g_hi = std::min(groups, flip180 ? groups - lo[fp] : hi[fp]);
+    for (int g = g_lo; g < g_hi; g++) items.push_back(((uint32_t)pair << 16) | (uint32_t)g);
+  }
+}
+
 void compile_remap_plan(RemapPlan& plan, const float* map_xy, int drows, int dcols, int src_rows, int src_cols) {
   plan = RemapPlan();
   plan.drows = drows;
@@ -828,6 +863,7 @@ void compile_remap_plan(RemapPlan& plan, const float* map_xy, int drows, int dco
         }
     }
   }
+  compile_remap_footprint(map_xy, drows, dcols, src_rows, src_cols, plan.fp_lo, plan.fp_hi);
   for (const RemapTile& tile : plan.tiles) {
     plan.max_rect_w = std::max(plan.max_rect_w, tile.w);
     plan.max_rect_h = std::max(plan.max_rect_h, tile.h);

@@ -160,11 +160,25 @@ struct RemapPlan {
   std::vector<uint32_t> border;  // (y << 16 | x) of every destination pixel marked kRemapBorder
   int max_rect_w = 0, max_rect_h = 0;
   size_t max_lds_bytes = 0;      // over tiles, for a source pixel size of 3 bytes
+  // Footprint in the source image: per source row pair (rows 2i, 2i + 1) the hull [fp_lo[i], fp_hi[i]) of the 4-pixel groups
+  // that hold a bilinear tap of some destination pixel -- interior and border pixels alike, from the same quantised
+  // coordinates as the words; fp_lo[i] >= fp_hi[i]: no tap in that pair.  Filled by compile_remap_plan, or read back from
+  // the device compiler (rip_maps.hip remap_footprint_kernel).
+  std::vector<int> fp_lo, fp_hi;
   bool valid = false;
 };
 // LDS bytes the kernel needs for a source rectangle w x h of 3-byte pixels
 size_t remap_tile_lds_bytes(int x0, int w, int h);
 void compile_remap_plan(RemapPlan& plan, const float* map_xy, int drows, int dcols, int src_rows, int src_cols);
+// The footprint part of compile_remap_plan on its own (lo / hi get (src_rows + 1) / 2 entries).
+void compile_remap_footprint(const float* map_xy, int drows, int dcols, int src_rows, int src_cols, std::vector<int>& lo,
+                             std::vector<int>& hi);
+// The items of the fused Bayer chain kernel (pair << 16 | grp: the 4 x 2 pixels at source rows 2 pair, 2 pair + 1 and columns
+// 4 grp .. 4 grp + 3 of its input, row-major) whose output lies in the footprint, for a chain of rows x cols pixels that
+// writes the remap's source image flipped by flip_angle (0 or 180): item (pair, grp) writes row pair rows / 2 - 1 - pair and
+// group cols / 4 - 1 - grp under the 180-degree flip.  rows even, cols a multiple of 4, both below 2^17.
+void chain_footprint_items(const std::vector<int>& lo, const std::vector<int>& hi, int rows, int cols, int flip_angle,
+                           std::vector<uint32_t>& items);
 
 // ---------------------------------------------------------------------------------------------
 // CCC model (convolutional_color_constancy.cpp:116-207)

@@ -106,6 +106,11 @@ struct ChainParams {
   int fp_contract;
   // in: -1 = the remap gathers from dst next (run_batch's hint); set by launch_chain (Tunables::chain_deal): 1 = the fast kernel deals its chunks round-robin to the XCDs (fast_chunks kDeal), 0 = one contiguous range per XCD
   int deal;
+  // optional: the items (pair << 16 | grp, in the fast kernel's source coordinates, row-major) the fast kernel walks instead of
+  // all (rows / 2) x (cols / 4) -- the part of the intermediate image the remap behind it reads (rip_host.hpp chain_footprint_items);
+  // null: dense.  Only the Bayer fast path honours it; run_batch sets it for nothing else.
+  const uint32_t* item_list;
+  int n_list_items;
 };
 
 // 16-bit Bayer extension (the reference lists bayer_*16 and rejects them, debayer.hpp:73-80 / debayer.cpp:76-78):
@@ -224,6 +229,16 @@ struct RemapPlanBuildParams {
   unsigned* counters;   // [4]
 };
 void launch_remap_plan_build(const RemapPlanBuildParams& p, hipStream_t stream);
+// Footprint of the remap in its source image (the device counterpart of the one rip_host.cpp compile_remap_plan builds): for
+// every source row pair the hull [lo[pair], hi[pair]) of the 4-pixel groups holding a bilinear tap of some destination pixel.
+// lo must be filled with 0x7F bytes and hi with zeros before the launch; a pair no tap reaches keeps lo >= hi.
+struct RemapFootprintParams {
+  const float* map_xy;  // [drows][dcols] interleaved (x, y)
+  int drows, dcols, src_rows, src_cols, tiles_x, tiles_y;
+  int* lo;              // [src_rows / 2] (rows rounded up)
+  int* hi;
+};
+void launch_remap_footprint(const RemapFootprintParams& p, hipStream_t stream);
 
 // Launch tunables.  The defaults are the measured optima (sweeps in EXPERIMENTS.md); the environment variables named beside them
 // override them for experiments, and are read ONCE, by tunables_from_env() when a handle is created -- never on a launch path.
@@ -239,6 +254,7 @@ struct Tunables {
   int remap_deal = 4;         // RIP_REMAP_DEAL: how the ring kernels deal the tiles to the eight XCDs -- k > 0: runs of about k tile rows round-robin (all XCDs work on one band of the image; round 6: -5 % at 4 frames per visit, -12 % with 6-8; 1, 2 and 4 tile rows run alike, 4 fetches least: 7.58 / 7.11 / 6.54 GB per 256 frames at the L2s), 0: one contiguous range of tiles per XCD (rounds 1-5)
   int remap_exp = 0;          // RIP_REMAP_EXP: bit mask of timing-only experiments (wrong pixels), honoured by -DRIP_EXPERIMENTS builds only (tools/probes/remap_exp_probe.py)
   int remap_fused = 1;        // RIP_REMAP_FUSED=0: never run the chain inside the remap's tiles (rip_fused.hip)
+  int chain_footprint = 1;    // RIP_CHAIN_FOOTPRINT=0: the fast chain kernel in front of the remap computes every pixel, not only the ones the remap reads (ChainParams::item_list)
   int chain_nt = -1;          // RIP_CHAIN_NT: non-temporal stores of the fused chain for batches of >= 8 frames; -1 = always (round 5: also when the remap reads the image back), 0 = never, 1 = only when no kernel of the batch reads the image again (rounds 3-4)
   int ccc_lds_hist_min = 12;  // RIP_CCC_LDS_HIST_MIN: smallest batch that takes the LDS histogram (round 4, with 4 workgroups per frame: ms per batch of 8 / 16 / 32 / 47 frames, atomic kernel vs LDS: 0.069 / 0.093 / 0.142 / 0.191 vs 0.077 / 0.081 / 0.093 / 0.108)
   int overlap_groups = 0;     // RIP_OVERLAP_GROUPS: frame groups a batch is split into on the handle's internal streams (rip_api.cpp run_batch); 0 / 1 = off (the measured optimum)

@@ -682,6 +682,16 @@ class RawImagePipeline:
         keys = ("tiles_x", "tiles_y", "border_pixels", "max_lds_bytes", "max_rect_w", "max_rect_h", "on_device", "tile_w", "tile_h")
         return dict(zip(keys, [int(v) for v in info]))
 
+    def debug_chain_footprint(self, src_rows, src_cols, flip_angle=0):
+        """Test hook (rip_debug_chain_footprint): (dict, intervals) -- the items the fused chain walks in front of the remap
+        and, per row pair of the chain's input, the walked groups [lo, hi) as an (src_rows // 2, 2) int32 array."""
+        info = (C.c_int * 4)()
+        iv = np.zeros((int(src_rows) // 2, 2), np.int32)
+        self._call("rip_debug_chain_footprint", int(src_rows), int(src_cols), int(flip_angle), info, iv.ctypes.data_as(C.c_void_p),
+                   int(iv.shape[0]))
+        keys = ("dense_items", "footprint_items", "row_pairs", "last_walked")
+        return dict(zip(keys, [int(v) for v in info])), iv
+
     def set_tunable(self, name, value):
         """Launch tunable of this handle (rip_set_tunable: development / test hook; the library reads its environment
         overrides once, when the handle is created)."""
