@@ -193,6 +193,10 @@ class RawImagePipeline {
   //-----------------------------------------------------------------------------
   void setDebayer(bool enabled) { check(rip_set_debayer(h_, enabled)); }
   void setDebayerEncoding(const std::string& encoding) { check(rip_set_debayer_encoding(h_, encoding.c_str())); }
+  // not in the reference: "bilinear" (default, the CPU path) or "mht" (Malvar-He-Cutler, the CUDA path's
+  // cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT), debayer.cpp:93-108), rip.h rip_set_debayer_method
+  void setDebayerMethod(const std::string& method) { check(rip_set_debayer_method(h_, method.c_str())); }
+  std::string getDebayerMethod() const { return str(&rip_get_debayer_method); }
 
   void setFlip(bool enabled) { check(rip_set_flip(h_, enabled)); }
   void setFlipAngle(int angle) { check(rip_set_flip_angle(h_, angle)); }

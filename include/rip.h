@@ -10,7 +10,8 @@
  *
  * Every per-frame stage runs as hand-written HIP kernels on gfx950; there is no CPU
  * fallback.  Results follow the reference's CPU/OpenCV path (the parity target named by
- * BASELINE.json), whatever `use_gpu` says.
+ * BASELINE.json), whatever `use_gpu` says; rip_set_debayer_method("mht") opts into the CUDA
+ * path's Malvar-He-Cutler demosaic.
  *
  * Errors: every function returns a rip_status; rip_last_error() gives the message.  The
  * C++ facade (include/raw_image_pipeline/raw_image_pipeline.hpp) maps
@@ -190,7 +191,8 @@ rip_status rip_set_ccc_kalman_model(rip_pipeline* p, double h, double r);
 
 /* ---- other interfaces (hpp:59-61) -------------------------------------------------------- */
 rip_status rip_reset_white_balance_temporal_consistency(rip_pipeline* p); /* cpp:218-220 */
-rip_status rip_set_gpu(rip_pipeline* p, int use_gpu);                     /* cpp:210-212; recorded only */
+rip_status rip_set_gpu(rip_pipeline* p, int use_gpu);                     /* cpp:210-212; recorded only (the CUDA path's
+                                                                           demosaic: rip_set_debayer_method "mht") */
 /* cpp:214-216.  While on, every rip_apply() of an 8-bit frame also writes the image after each of the eight modules --
  * enabled or not -- as the reference's pipeline() does (raw_image_pipeline.hpp:143-172 -> saveDebugImage :179-186: copy,
  * cv::normalize(0, 255, NORM_MINMAX), cv::imwrite): /tmp/00_debayer.png, 01_flip, 02_white_balancing, 03_color_calibration,
@@ -221,6 +223,20 @@ rip_status rip_set_debayer_encoding(rip_pipeline* p, const char* encoding);     
  * for CV_16UC1 -- and flipped; the result is 3 x uint16 per pixel, encoding "bgr16", rows * cols * 6 bytes.  Every other
  * stage is an 8-bit stage in the reference and must be disabled (RIP_ERR_ASSERT otherwise); no taps are kept. */
 rip_status rip_set_debayer_16bit(rip_pipeline* p, int enabled);
+/* Extension beyond the reference: the demosaic of bayer_{rggb,bggr,gbrg,grbg}8 frames (and of bayer_*16 frames under
+ * rip_set_debayer_16bit, clamped to [0, 65535]).  "bilinear" (default): the CPU path (debayer.cpp:49-70), what every other
+ * function here describes.  "mht": Malvar-He-Cutler, the 5 x 5 gradient-corrected filter the reference's CUDA path runs
+ * (cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT), debayer.cpp:93-108): integer weights over 16, rounded half to even,
+ * reflect-101 reads outside the frame (PARITY.md gives the contract; pixels within 2 px of an edge are defined by that rule,
+ * not checked against OpenCV's CUDA kernel).  Everything after the demosaic sees the MHT image exactly as it would see a bgr8
+ * frame holding it.  Like bilinear it runs whatever rip_set_debayer says (debayer.hpp:38-40); mono8 / bgr8 / rgb8 frames are
+ * not affected.  Cost: an MHT batch is demosaiced in a pass of its own, and without a DEBAYERED tap to hold its image it takes
+ * n_frames x rows x cols x 3 bytes of extra device memory (rows padded to 16 bytes), kept by the handle.  rip_set_gpu does not
+ * select it.  Unknown names: RIP_ERR_INVALID_ARGUMENT naming the two methods, nothing changed.  Works on RIP_DEVICE_NONE
+ * handles.  The params YAML key `debayer: method:` (default "bilinear") sets it too; rip_load_params fails with
+ * RIP_ERR_INVALID_ARGUMENT on an unknown value and leaves the parameters as they were. */
+rip_status rip_set_debayer_method(rip_pipeline* p, const char* method);
+rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
 rip_status rip_set_flip(rip_pipeline* p, int enabled);                            /* hpp:69 */
 rip_status rip_set_flip_angle(rip_pipeline* p, int angle);                        /* hpp:70 */
 rip_status rip_set_white_balance(rip_pipeline* p, int enabled);                   /* hpp:72 */

@@ -119,6 +119,7 @@ bool is_bayer16(const std::string& e) {
 struct Plan {
   int src_kind = rip::SRC_BGR, ry = 0, rx = 0;
   int elem_bytes = 1;     // 2: the 16-bit Bayer extension (debayer + flip only, bgr16 out)
+  bool mht = false;       // Bayer input demosaiced by Malvar-He-Cutler (rip_set_debayer_method "mht") instead of bilinear
   int channels = 3;       // channels after the debayer stage
   int flip_angle = 0;     // effective
   int mid_rows = 0, mid_cols = 0;  // post-flip geometry (pointwise chain output)
@@ -352,6 +353,7 @@ struct rip_pipeline {
   int geom_rows = -1, geom_cols = -1;
   // per-batch scratch
   DevBuf d_stats, d_wb, d_hist, d_work, d_rowbest, d_argmax, d_mid;
+  DevBuf d_mht;  // the Malvar-He-Cutler image of a batch when no DEBAYERED tap holds it (run_batch)
   // compiled remap plan (tiled LDS gather), rebuilt when the maps or the source geometry change
   rip::RemapPlan plan;
   DevBuf d_plan_words, d_plan_tiles, d_plan_border, d_plan_counters;
@@ -410,7 +412,7 @@ struct rip_pipeline {
     if (dl_stream) (void)hipStreamDestroy(dl_stream);
     for (DevBuf* b : {&d_tabs, &d_vig_image, &d_map, &d_map_ckpt, &d_filter_fft, &d_bias_fft, &d_accum, &d_ccc_state, &d_geom, &d_stats, &d_wb,
                       &d_hist, &d_work, &d_rowbest, &d_argmax, &d_mid, &d_in, &d_out, &d_tap_deb, &d_tap_col, &d_vig, &d_plan_words,
-                      &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg})
+                      &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg, &d_mht})
       b->release();
   }
 };
@@ -813,6 +815,7 @@ Plan make_plan(const rip_pipeline* p, int rows, int cols, int channels, const st
   } else {
     throw InvalidArgument("images with " + std::to_string(channels) + " channels are not supported");
   }
+  pl.mht = pl.src_kind == rip::SRC_BAYER && m.debayer_method == "mht";
   pl.flip_angle = (m.flip_enabled && (m.flip_angle == 90 || m.flip_angle == 180 || m.flip_angle == 270)) ? m.flip_angle : 0;
   const bool swap = pl.flip_angle == 90 || pl.flip_angle == 270;
   pl.mid_rows = swap ? cols : rows;
@@ -858,6 +861,58 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
                bool reuse_wb = false) {
   p->work_enqueued = true;  // from here on something may sit on p->stream
   DeviceGuard device_guard(p->device);
+  // Malvar-He-Cutler demosaic (rip_set_debayer_method "mht", rip_demosaic.hip): one pass of its own writes the post-flip BGR
+  // image -- the DEBAYERED tap (flip.cpp:60-62), into the caller's tap buffer when one was requested -- and the rest of the
+  // chain runs on that image exactly as on a bgr8 frame holding it, with no flip left to do.  16-bit frames: the kernel writes
+  // the bgr16 result and that is all.
+  if (pl.mht) {
+    rip::MhtParams d = {};
+    d.src = d_in;
+    d.src_step = in_step;
+    d.src_frame_stride = in_frame_stride;
+    d.rows = rows;
+    d.cols = cols;
+    d.bayer_ry = pl.ry;
+    d.bayer_rx = pl.rx;
+    d.elem_bytes = pl.elem_bytes;
+    d.drows = pl.mid_rows;
+    d.dcols = pl.mid_cols;
+    d.flip_angle = pl.flip_angle;
+    d.n_frames = n;
+    if (pl.elem_bytes == 2) {
+      d.dst = d_out;
+      d.dst_step = out_step ? out_step : (size_t)pl.out_cols * 6;
+      d.dst_frame_stride = out_frame_stride ? out_frame_stride : d.dst_step * pl.out_rows;
+    } else if (d_tap_deb) {
+      d.dst = d_tap_deb;
+      d.dst_step = (size_t)pl.mid_cols * 3;
+      d.dst_frame_stride = d.dst_step * pl.mid_rows;
+    } else {
+      // 16-byte aligned rows and frames: what launch_remap_tiled asks of the image it gathers from
+      d.dst_step = ((size_t)pl.mid_cols * 3 + 15) & ~(size_t)15;
+      d.dst_frame_stride = d.dst_step * pl.mid_rows;
+      p->d_mht.reserve(d.dst_frame_stride * (size_t)n);
+      d.dst = p->d_mht.as<uint8_t>();
+    }
+    {
+      ProfScope ps(p, RIP_KERNEL_CHAIN, p->stream);
+      rip::launch_demosaic_mht(d, p->stream);
+    }
+    hipError_t lem = hipGetLastError();
+    if (lem != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(lem));
+    if (pl.elem_bytes == 2) {
+      p->last_batch_frames = 0;  // no white balance ran (as on the bilinear 16-bit path)
+      return;
+    }
+    Plan s = pl;
+    s.mht = false;
+    s.src_kind = rip::SRC_BGR;
+    s.ry = s.rx = 0;
+    s.flip_angle = 0;
+    run_batch(p, s, d.dst, d.dst_step, d.dst_frame_stride, n, pl.mid_rows, pl.mid_cols, d_out, out_step, out_frame_stride, nullptr,
+              d_tap_col, reuse_wb);
+    return;
+  }
   if (pl.elem_bytes == 2) {  // 16-bit Bayer extension: one kernel, no taps
     rip::Debayer16Params d = {};
     d.src = d_in;
@@ -1976,6 +2031,8 @@ rip_status rip_set_debug(rip_pipeline* p, int v) {
 RIP_SETTER(rip_set_debayer, (rip_pipeline * p, int v), p->m.debayer_enabled = v != 0)
 RIP_SETTER(rip_set_debayer_16bit, (rip_pipeline * p, int v), p->m.debayer_16bit = v != 0)
 RIP_SETTER(rip_set_debayer_encoding, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.debayer_encoding = s)
+RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+           rip::check_debayer_method(s); p->m.debayer_method = s)
 RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
 RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)
 RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v != 0)
@@ -2038,6 +2095,13 @@ int rip_get_dist_image_height(const rip_pipeline* p) { return p ? p->m.dist_h : 
 int rip_get_dist_image_width(const rip_pipeline* p) { return p ? p->m.dist_w : 0; }
 int rip_get_rect_image_height(const rip_pipeline* p) { return p ? p->m.rect_h : 0; }
 int rip_get_rect_image_width(const rip_pipeline* p) { return p ? p->m.rect_w : 0; }
+
+rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t cap) {
+  return guarded(p, [&] {
+    need(p);
+    copy_string(p->m.debayer_method, out, cap);
+  });
+}
 
 rip_status rip_get_dist_distortion_model(const rip_pipeline* p, char* out, size_t cap) {
   return guarded(p, [&] {

@@ -288,6 +288,11 @@ void set_enhancer_gains_from_config(Modules& m, double hue, double sat, double v
 }
 
 void params_from_node(Modules& m, const YamlNode& node) {
+  // extension key debayer: method: (not in the reference's files).  Checked before anything is assigned: an unknown method
+  // fails the load and leaves every parameter as it was.
+  const std::string debayer_method = node["debayer"].get("method", std::string("bilinear"));
+  check_debayer_method(debayer_method);
+  m.debayer_method = debayer_method;
   // raw_image_pipeline.cpp:54-160, defaults as written there
   m.debayer_enabled = node["debayer"].get("enabled", true);
   m.debayer_encoding = node["debayer"].get("encoding", std::string("auto"));
@@ -338,6 +343,7 @@ void apply_example_params(Modules& m) {
   // values of the reference's config/pipeline_params_example.yaml (facts, not text)
   m.debayer_enabled = true;
   m.debayer_encoding = "auto";
+  m.debayer_method = "bilinear";
   m.flip_enabled = false;
   m.flip_angle = 0;
   m.wb_enabled = true;
@@ -359,6 +365,11 @@ void apply_example_params(Modules& m) {
   m.und_enabled = true;
   m.balance = 0.0;
   m.fov_scale = 0.8;
+}
+
+void check_debayer_method(const std::string& method) {
+  if (method != "bilinear" && method != "mht")
+    throw std::invalid_argument("Debayer method [" + method + "] not supported. Supported methods: 'bilinear', 'mht'");
 }
 
 bool load_params_file(Modules& m, const std::string& path) {

@@ -124,6 +124,19 @@ struct Debayer16Params {
   int drows, dcols, flip_angle, n_frames;
 };
 
+// rip_demosaic.hip: Malvar-He-Cutler demosaic + flip of Bayer frames (rip_set_debayer_method "mht"), interleaved BGR out of
+// the sample type: bayer_*8 -> 3 x uint8, bayer_*16 (the 16-bit extension) -> 3 x uint16 per pixel.
+struct MhtParams {
+  const uint8_t* src;
+  size_t src_step, src_frame_stride;
+  int rows, cols, bayer_ry, bayer_rx;
+  int elem_bytes;  // 1 or 2
+  uint8_t* dst;
+  size_t dst_step, dst_frame_stride;
+  int drows, dcols, flip_angle, n_frames;
+  int src_aligned4, dst_aligned4, frame_groups;  // set by the launcher
+};
+
 struct StatsParams {
   const uint8_t* src;
   size_t src_step, src_frame_stride;
@@ -280,6 +293,9 @@ void launch_chain_fc1(const ChainParams& p, const Tunables& tn, hipStream_t stre
 bool launch_remap_fused_fc1(const RemapTiledParams& p, const ChainParams& c, int max_rect_w, int max_rect_h, const Tunables& tn, hipStream_t stream,
                             bool dry_run);
 void launch_debayer16(const Debayer16Params& p, hipStream_t stream);
+void launch_demosaic_mht(const MhtParams& p, hipStream_t stream);
+// which kernel launch_demosaic_mht takes: 1 the LDS-tiled 8-bit kernel (every flip), 0 one thread per pixel (16-bit)
+int mht_uses_tile_path(const MhtParams& p);
 // builds the image ChainParams::vig_image points to (vig_image_bytes() bytes) from the handle's tables
 size_t vig_image_bytes();
 void launch_vig_image(const DevTables* tabs, uint32_t* image, hipStream_t stream);

@@ -18,6 +18,7 @@ NODE_DEFAULTS = OrderedDict([
     ("output_encoding", "BGR"), ("output_frame", "passthrough"), ("skip_number_of_images_for_slow_topic", -1),
     ("use_gpu", True), ("debug", False),
     ("debayer/enabled", True), ("debayer/encoding", "auto"),
+    ("debayer/method", "bilinear"),  # extension: "mht" selects the CUDA path's Malvar-He-Cutler demosaic (rip.h)
     ("flip/enabled", False), ("flip/angle", 0),
     ("white_balance/enabled", False), ("white_balance/method", "simple"), ("white_balance/clipping_percentile", 10.0),
     ("white_balance/saturation_bright_thr", 0.9), ("white_balance/saturation_dark_thr", 0.1),
@@ -83,6 +84,7 @@ class CameraStream:
         pipe.set_debug(p["debug"])
         pipe.set_debayer(p["debayer/enabled"])
         pipe.set_debayer_encoding(p["debayer/encoding"])
+        pipe.set_debayer_method(p["debayer/method"])
         pipe.set_flip(p["flip/enabled"])
         pipe.set_flip_angle(p["flip/angle"])
         pipe.set_white_balance(p["white_balance/enabled"])

@@ -474,6 +474,14 @@ class RawImagePipeline:
     def set_debayer_encoding(self, encoding):
         self._call("rip_set_debayer_encoding", encoding.encode())
 
+    def set_debayer_method(self, method):
+        """Extension: "bilinear" (default, the reference's CPU path) or "mht" (Malvar-He-Cutler, what its CUDA path's
+        cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT) computes).  include/rip.h rip_set_debayer_method."""
+        self._call("rip_set_debayer_method", method.encode())
+
+    def get_debayer_method(self):
+        return self._string("rip_get_debayer_method")
+
     def set_flip(self, enabled):
         self._call("rip_set_flip", int(bool(enabled)))
 
