@@ -93,6 +93,75 @@ def oracle_run(O, c, frame, encoding, ccc=None, taps=False):
     return O.pipeline(prm, frame, encoding, ccc=ccc, taps=taps)
 
 
+def expected_mht(O, c, frame, pattern, ccc=None, taps=False):
+    """The CPU expectation of a Bayer frame under configuration c with debayer method "mht": an MHT frame is processed exactly
+    like a bgr8 frame holding the MHT image (PARITY.md), so the oracle runs on the numpy restatement of the demosaic
+    (tests/mht_reference.py).  Returns what oracle_run returns: (out, encoding[, debayered tap, colour tap])."""
+    from mht_reference import mht_reference
+    return oracle_run(O, c, mht_reference(frame, pattern), "bgr8", ccc=ccc, taps=taps)
+
+
+# ---- device batches in other layouts than tightly packed ----------------------------------------------
+LAYOUTS = ("tight", "pitch16", "pitch_odd", "base_off", "frame_gap")
+SENTINEL = 0xA5
+
+
+class DeviceBatch:
+    """A stack of frames on the device as a strided view (``view``) of one flat byte buffer (``backing``) whose other bytes
+    hold SENTINEL.  ``check_padding`` asserts that they still do: the input is read-only for the library."""
+
+    def __init__(self, view, backing, expected, layout, pitch, frame_stride, offset):
+        self.view, self.backing, self.expected = view, backing, expected
+        self.layout, self.pitch, self.frame_stride, self.offset = layout, pitch, frame_stride, offset
+
+    def check_padding(self, what=""):
+        import torch
+        torch.cuda.synchronize()
+        bad = int((self.backing != self.expected).sum())
+        assert bad == 0, "%s: %d bytes of the %s input buffer (frames or padding) were written" % (what, bad, self.layout)
+
+
+def batch_geometry(layout, row_bytes, rows, rng):
+    """(offset of the first byte, row pitch, frame stride) in bytes of a layout; draws from rng for the layouts with a free amount."""
+    offset, pitch, gap_rows = 0, row_bytes, 0
+    if layout == "pitch16":
+        pitch = (row_bytes + 15) // 16 * 16 + 16
+    elif layout == "pitch_odd":
+        pitch = row_bytes + int(rng.integers(1, 4))
+    elif layout == "base_off":
+        offset = int(rng.integers(1, 4))
+        pitch = (row_bytes + 3) // 4 * 4 + 4 * int(rng.integers(0, 3))
+    elif layout == "frame_gap":
+        gap_rows = int(rng.integers(1, 4))
+    else:
+        assert layout == "tight", layout
+    return offset, pitch, pitch * (rows + gap_rows)
+
+
+def device_batch(frames, layout, rng):
+    """frames: [n, rows, cols] or [n, rows, cols, 3] uint8 on the host -> DeviceBatch.  The view is built with as_strided over
+    bytes, so three-channel frames take pitches that are no multiple of 3; apply_device only asks that pixels be contiguous.
+    The allocation itself is 4-aligned (torch's allocator hands out 512-byte blocks)."""
+    import torch
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n, rows, cols = frames.shape[:3]
+    cn = 1 if frames.ndim == 3 else frames.shape[3]
+    row_bytes = cols * cn
+    offset, pitch, frame_stride = batch_geometry(layout, row_bytes, rows, rng)
+    total = offset + frame_stride * n + 4
+    host = np.full(total, SENTINEL, np.uint8)
+    rows_view = np.lib.stride_tricks.as_strided(host[offset:], (n, rows, row_bytes), (frame_stride, pitch, 1))
+    rows_view[...] = frames.reshape(n, rows, row_bytes)
+    backing = torch.from_numpy(host).cuda()
+    assert backing.data_ptr() % 4 == 0
+    if cn == 1:
+        view = torch.as_strided(backing, (n, rows, cols), (frame_stride, pitch, 1), offset)
+    else:
+        view = torch.as_strided(backing, (n, rows, cols, cn), (frame_stride, pitch, cn, 1), offset)
+    assert torch.equal(view.cpu(), torch.from_numpy(frames)), "device_batch: the view does not hold the frames"
+    return DeviceBatch(view, backing, backing.clone(), layout, pitch, frame_stride, offset)
+
+
 def assert_images_equal(got, ref, what="", tol=0):
     assert got.shape == ref.shape, "%s: shape %s vs %s" % (what, got.shape, ref.shape)
     d = np.abs(got.astype(np.int16) - ref.astype(np.int16))

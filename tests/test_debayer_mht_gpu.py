@@ -88,6 +88,49 @@ def test_batch_with_padded_rows_on_the_device(gpu_pipe):
         assert_images_equal(out[i].cpu().numpy(), flip(mht_reference(frames[i], "bayer_gbrg8"), 180), "frame %d" % i)
 
 
+def batch_against_reference(gpu_pipe, w, h, n, pattern, angle, seed, what):
+    """n different frames as one resident batch, demosaic and flip only; every frame against the flipped numpy restatement."""
+    import torch
+    frames = np.stack([synth.gen_frame(w, h, pattern, seed=seed + i, kind="uniform" if i % 2 else "scene") for i in range(n)])
+    assert len({f.tobytes() for f in frames}) == n
+    configure(gpu_pipe, flip_cfg(angle))
+    gpu_pipe.set_debayer_method("mht")
+    ow, oh = (h, w) if angle in (90, 270) else (w, h)
+    out = torch.full((n, oh, ow, 3), 0x5A, dtype=torch.uint8, device="cuda")  # a pixel nobody writes must not pass on recycled memory
+    gpu_pipe.apply_device(torch.from_numpy(frames).cuda(), pattern, out=out)
+    torch.cuda.synchronize()
+    out = out.cpu().numpy()
+    for i in range(n):
+        assert_images_equal(out[i], flip(mht_reference(frames[i], pattern), angle), "%s frame %d/%d" % (what, i, n))
+
+
+@pytest.mark.parametrize("angle", ANGLES)
+@pytest.mark.parametrize("n", [4, 5, 8, 9, 13])
+@pytest.mark.parametrize("size", [(328, 200), (645, 483)])
+def test_frame_groups(gpu_pipe, size, n, angle):
+    """The tile kernel takes four frames per workgroup visit: ceil(n / 4) frame groups, a workgroup of group g walks frames
+    g, g + groups, ... and prefetches the next one of ITS group into registers on interior tiles.  n = 5: frames 0 2 4 / 1 3
+    (uneven groups); 8: two even groups; 9 and 13: three and four groups, the last frame alone in its stride.  328 x 200 has
+    6 x 7 tiles with interior ones and aligned dword stores, 645 x 483 stores bytes."""
+    w, h = size
+    pattern = PATTERNS[(n + angle // 90) % 4]
+    batch_against_reference(gpu_pipe, w, h, n, pattern, angle, 500 + 20 * n, "groups %s n %d %s flip %d" % (size, n, pattern, angle))
+
+
+TILE_EDGE_SIZES = [(w, h) for w in (61, 63, 64, 65, 67, 68, 127, 129, 132) for h in (31, 32, 33, 34, 63, 65)]
+
+
+@pytest.mark.parametrize("angle", ANGLES)
+@pytest.mark.parametrize("size", TILE_EDGE_SIZES)
+def test_tile_edges(gpu_pipe, size, angle):
+    """Widths and heights around one and two 64 x 32 tiles: partial last tiles of 1 to 4 columns / rows, the reflect-101 halo
+    inside a tile next to the edge tile, dword stores that depend on cols % 4 (flip 180) and rows % 4 (flip 90), the
+    quarter turns' transposed tile whose first destination column is negative on the last partial tile."""
+    w, h = size
+    pattern = PATTERNS[TILE_EDGE_SIZES.index(size) % 4]
+    batch_against_reference(gpu_pipe, w, h, 2, pattern, angle, 700 + w + h, "edges %s %s flip %d" % (size, pattern, angle))
+
+
 # ---- the full chain: MHT handle vs a bgr8 handle fed the MHT images -----------------------------------------------------
 def chain_cfg(w, h, wb_method, **kw):
     base = dict(flip=True, flip_angle=180, wb=True, wb_method=wb_method, wb_temporal=wb_method == "ccc", cc=True, gamma=True,

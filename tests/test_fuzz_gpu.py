@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from raw_image_pipeline_amd import synth
-from helpers import assert_images_equal, cfg, configure, oracle_run
+from helpers import assert_images_equal, cfg, configure, expected_mht, oracle_run
 
 import os
 
@@ -91,11 +91,9 @@ def test_random_configuration_on_colour_and_mono_input(gpu_pipe, oracle, seed):
             assert_images_equal(out[i].reshape(ref.shape), ref, what + " batch frame %d/%d" % (i, n))
 
 
-@pytest.mark.parametrize("seed", range(max(1, N_BAYER // 3)))
-def test_random_ccc_sequences(gpu_pipe, oracle, seed):
-    """Convolutional colour constancy on random sizes (720x540 takes the 2x2 area path of the resize), flips,
-    thresholds and Kalman models; a short sequence per case so the filter state carries from frame to frame,
-    every other case as one resident batch."""
+def run_ccc_sequence(gpu_pipe, oracle, seed, method="bilinear"):
+    """One case of the ccc generator under a debayer method.  "mht": the expectation is the oracle on the numpy restatement of
+    the demosaic (helpers.expected_mht), the estimator's resize then reads the handle's MHT image."""
     import torch
     rng = np.random.default_rng(12000 + seed)
     if rng.random() < 0.3:
@@ -114,11 +112,13 @@ def test_random_ccc_sequences(gpu_pipe, oracle, seed):
             wb_temporal=bool(rng.random() < 0.7), flip=bool(rng.random() < 0.5), flip_angle=angle,
             gamma=bool(rng.random() < 0.5), gamma_k=0.9, ce=bool(rng.random() < 0.5), ce_sat=1.2)
     configure(gpu_pipe, c)
+    if method != "bilinear":
+        gpu_pipe.set_debayer_method(method)
     gpu_pipe.reset_white_balance_temporal_consistency()
     occ.reset()
     n = int(rng.integers(2, 6))
     frames = [synth.gen_frame(w, h, pattern, seed=31 * seed + i, kind="scene", tint=(0.6 + 0.08 * i, 1.0, 0.5 + 0.05 * i)) for i in range(n)]
-    what = "ccc seed %d: %dx%d %s kalman %s %s" % (seed, w, h, pattern, kal, {k: c[k] for k in ("wb_bright", "wb_dark", "wb_temporal", "flip", "flip_angle")})
+    what = "ccc %s seed %d: %dx%d %s kalman %s %s" % (method, seed, w, h, pattern, kal, {k: c[k] for k in ("wb_bright", "wb_dark", "wb_temporal", "flip", "flip_angle")})
     if seed % 2:
         out = gpu_pipe.apply_device(torch.from_numpy(np.stack(frames)).cuda(), pattern)
         torch.cuda.synchronize()
@@ -126,5 +126,22 @@ def test_random_ccc_sequences(gpu_pipe, oracle, seed):
     else:
         got = [gpu_pipe.process(f, pattern) for f in frames]
     for i in range(n):
-        ref, _ = oracle_run(oracle, c, frames[i], pattern, ccc=occ)
+        if method == "mht":
+            ref, _ = expected_mht(oracle, c, frames[i], pattern, ccc=occ)
+        else:
+            ref, _ = oracle_run(oracle, c, frames[i], pattern, ccc=occ)
         assert_images_equal(got[i], ref, what + " frame %d/%d" % (i, n))
+
+
+@pytest.mark.parametrize("seed", range(max(1, N_BAYER // 3)))
+def test_random_ccc_sequences(gpu_pipe, oracle, seed):
+    """Convolutional colour constancy on random sizes (720x540 takes the 2x2 area path of the resize), flips,
+    thresholds and Kalman models; a short sequence per case so the filter state carries from frame to frame,
+    every other case as one resident batch."""
+    run_ccc_sequence(gpu_pipe, oracle, seed)
+
+
+@pytest.mark.parametrize("seed", range(max(1, N_BAYER // 9)))
+def test_random_ccc_sequences_mht(gpu_pipe, oracle, seed):
+    """The same generator, a third as many cases, with debayer method "mht" against the CPU expectation of the MHT image."""
+    run_ccc_sequence(gpu_pipe, oracle, seed, method="mht")

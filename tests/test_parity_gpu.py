@@ -179,13 +179,47 @@ def test_undistortion_batch_through_the_lds_ring(gpu_pipe, oracle, monkeypatch, 
         assert_images_equal(out[i], ref, "ring frame %d (fov %g, %d stages)" % (i, fov, stages))
 
 
+DEAL_SWEEP = [(0, 0, 0), (1, 1, 1), (2, 2, 2), (5, 3, 5), (7, 1, 3), (64, 9, 0), (3, 0, 4), (0, 1, 16)]  # chain_deal, remap_deal, remap_frames
+
+
+def sweep_the_deals(pipe, O, c, frames, encoding, what):
+    """The batch under the default deals against the oracle (last frame), then byte-identical under every entry of DEAL_SWEEP.
+    Every call writes into a tensor filled with a sentinel beforehand: a tile or chunk no workgroup took must not pass on what
+    an earlier call left in recycled memory."""
+    import torch
+    n = len(frames)
+    configure(pipe, c)
+    dev = torch.from_numpy(frames).cuda()
+    shape = pipe.apply_device(dev, encoding).shape
+
+    def run():
+        out = torch.full(tuple(shape), 0x5A, dtype=torch.uint8, device="cuda")
+        pipe.apply_device(dev, encoding, out=out)
+        return out.cpu().numpy()
+
+    base = run()
+    ref, _ = oracle_run(O, c, frames[n - 1], encoding)
+    assert_images_equal(base[n - 1].reshape(ref.shape), ref, "default deals vs oracle %s" % what)
+    for chain_deal, remap_deal, frames_per_visit in DEAL_SWEEP:
+        pipe.set_tunable("chain_deal", chain_deal)
+        pipe.set_tunable("remap_deal", remap_deal)
+        pipe.set_tunable("remap_frames", frames_per_visit)
+        assert np.array_equal(run(), base), "chain_deal %d remap_deal %d frames %d changes the image at %s" % (chain_deal, remap_deal, frames_per_visit, what)
+    return dev
+
+
 @pytest.mark.parametrize("size,n", [((448, 272), 7), ((1000, 752), 13), ((2448, 2048), 4), ((640, 482), 1)])
 def test_the_deals_of_tiles_and_chunks_to_the_xcds_do_not_change_a_byte(gpu_pipe, oracle, size, n):
     """Round 6: the remap's tiles and the chain's chunks are dealt to the XCDs round-robin in runs (RIP_REMAP_DEAL /
     RIP_CHAIN_DEAL) instead of one contiguous range each.  The deal decides WHICH workgroup takes a tile / chunk, never what
-    it computes: every run length -- contiguous (0), the defaults, run lengths that leave ragged last runs and XCD shares
-    without work (tile / chunk counts that are no multiples of 8 x run) -- gives the image of the default deal, and that one
-    equals the oracle's (full chain of config 2: statistics, fused chain with the Lab round trip, ring remap)."""
+    it computes.  remap_deal is a run length in tile rows: contiguous (0), the default, run lengths that leave ragged last runs
+    and XCD shares without work (tile counts that are no multiples of 8 x run); chain_deal is a MODE (0 contiguous, 1 the
+    remap's order, >= 2 the same as 2), no run length of the chain is varied.  Every setting gives the image of the default
+    deal, and that one equals the oracle's.  Three configurations, because each sends the tiles through another kernel:
+    the full chain of config 2 (statistics, fused chain with the Lab round trip, ring remap behind an intermediate image);
+    debayer + gains + matrix + gamma + undistortion without a tap (the remap's tiles colour their own source rectangles,
+    remap_bayer_fused_kernel: no chain launch at all where the Bayer pitch is a multiple of 16); mono8 with flip 180 + gamma +
+    undistortion (the LUT ring kernel)."""
     import torch
     w, h = size
     c = cfg(flip=True, flip_angle=180, wb=True, wb_method="grey_world", cc=True, gamma=True, gamma_k=0.8, vig=True, undistort=True,
@@ -196,12 +230,39 @@ def test_the_deals_of_tiles_and_chunks_to_the_xcds_do_not_change_a_byte(gpu_pipe
     base = gpu_pipe.apply_device(dev, "bayer_rggb8").cpu().numpy()
     ref, _ = oracle_run(oracle, c, frames[n - 1], "bayer_rggb8")
     assert_images_equal(base[n - 1], ref, "default deals vs oracle %s" % (size,))
-    for chain_deal, remap_deal, frames_per_visit in [(0, 0, 0), (1, 1, 1), (2, 2, 2), (5, 3, 5), (7, 1, 3), (64, 9, 0), (3, 0, 4), (0, 1, 16)]:
+    for chain_deal, remap_deal, frames_per_visit in DEAL_SWEEP:
         gpu_pipe.set_tunable("chain_deal", chain_deal)
         gpu_pipe.set_tunable("remap_deal", remap_deal)
         gpu_pipe.set_tunable("remap_frames", frames_per_visit)
         got = gpu_pipe.apply_device(dev, "bayer_rggb8").cpu().numpy()
         assert np.array_equal(got, base), "chain_deal %d remap_deal %d frames %d changes the image at %s" % (chain_deal, remap_deal, frames_per_visit, size)
+
+
+@pytest.mark.parametrize("size,n", [((448, 272), 7), ((1000, 752), 13), ((2448, 2048), 4), ((640, 482), 1)])
+def test_the_deals_in_the_fused_remap_and_the_mono_ring(rip_lib, oracle, size, n):
+    """The sweep of the test above on the two other kernels that deal tiles (see its docstring), each on a fresh handle."""
+    from raw_image_pipeline_amd import RawImagePipeline
+    w, h = size
+    cam = synth.camera_model(w, h)
+    # the remap's tiles demosaic and colour their own source rectangles (rip_fused.hip): TileDeal inside remap_bayer_fused_kernel
+    pipe = RawImagePipeline(False, "", "", "", device=0)
+    c = cfg(flip=True, flip_angle=180, wb=True, wb_method="grey_world", cc=True, gamma=True, gamma_k=0.8, undistort=True, cam=cam)
+    frames = np.stack([synth.gen_frame(w, h, "bayer_rggb8", seed=900 + i, kind="scene") for i in range(n)])
+    dev = sweep_the_deals(pipe, oracle, c, frames, "bayer_rggb8", "fused remap %s" % (size,))
+    if w % 16 == 0:  # every size of the sweep but 1000 x 752: one fused kernel, the chain is never launched
+        for remap_deal in (0, 3):
+            pipe.set_tunable("remap_deal", remap_deal)
+            pipe.profile_begin(16)
+            pipe.apply_device(dev, "bayer_rggb8")
+            launches = {k: cnt for k, (_, cnt) in pipe.profile_end().items()}
+            assert launches["chain"] == 0 and launches["remap"] >= 1, (size, remap_deal, launches)
+    del dev, pipe
+    # mono8: flip 180 and the gamma table applied by the ring kernel as it gathers (mono_ops)
+    pipe = RawImagePipeline(False, "", "", "", device=0)
+    c = cfg(flip=True, flip_angle=180, gamma=True, gamma_k=0.8, undistort=True, cam=cam)
+    rng = np.random.default_rng(w + n)
+    frames = np.stack([rng.integers(0, 256, (h, w), dtype=np.uint8) for i in range(n)])
+    sweep_the_deals(pipe, oracle, c, frames, "mono8", "mono8 ring %s" % (size,))
 
 
 @pytest.mark.parametrize("size,balance,fov", [((2448, 2048), 0.0, 1.0), ((1920, 1200), 1.0, 0.8), ((450, 270), 0.5, 3.6), ((131, 97), 1.0, 0.6)])
