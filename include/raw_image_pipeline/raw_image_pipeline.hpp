@@ -17,6 +17,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../rip.h"
@@ -197,6 +198,18 @@ class RawImagePipeline {
   // cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT), debayer.cpp:93-108), rip.h rip_set_debayer_method
   void setDebayerMethod(const std::string& method) { check(rip_set_debayer_method(h_, method.c_str())); }
   std::string getDebayerMethod() const { return str(&rip_get_debayer_method); }
+  // not in the reference: bayer_*16 frames (rip.h rip_set_debayer_16bit / rip_set_debayer_16bit_range).  The input is a
+  // one-channel Mat of 16-bit samples (CV_16UC1; the stand-in Mat: the wrapping constructor with step = cols * 2).  With a
+  // range 0 <= black < white <= 65535 the frame is demosaiced at 16 bits, narrowed to 8 bits and runs through the whole
+  // pipeline: apply / process / submit / collect / submitTo return ordinary uint8 "bgr8" Mats.  Range (0, 0) = off: the
+  // result would be bgr16, which these uint8 Mats cannot carry (use the C interface for it).
+  void setDebayer16Bit(bool enabled) { check(rip_set_debayer_16bit(h_, enabled)); }
+  void setDebayer16BitRange(int black, int white) { check(rip_set_debayer_16bit_range(h_, black, white)); }
+  std::pair<int, int> getDebayer16BitRange() const {
+    int black = 0, white = 0;
+    check(rip_get_debayer_16bit_range(h_, &black, &white));
+    return {black, white};
+  }
 
   void setFlip(bool enabled) { check(rip_set_flip(h_, enabled)); }
   void setFlipAngle(int angle) { check(rip_set_flip_angle(h_, angle)); }

@@ -219,10 +219,29 @@ rip_status rip_set_debayer(rip_pipeline* p, int enabled);                       
 rip_status rip_set_debayer_encoding(rip_pipeline* p, const char* encoding);       /* hpp:67 */
 /* Extension beyond the reference, off by default.  DebayerModule lists bayer_{rggb,bggr,gbrg,grbg}16 (debayer.hpp:73-80)
  * and throws for them (debayer.cpp:76-78; so does this library).  With the extension on such frames (one channel of
- * uint16, pitches in bytes) are demosaiced with the 8-bit path's formulas on 16-bit samples -- what cv::demosaicing does
- * for CV_16UC1 -- and flipped; the result is 3 x uint16 per pixel, encoding "bgr16", rows * cols * 6 bytes.  Every other
- * stage is an 8-bit stage in the reference and must be disabled (RIP_ERR_ASSERT otherwise); no taps are kept. */
+ * uint16, pitches in bytes) are accepted.  What happens to them depends on the 16-bit range (below):
+ *   range (0, 0), the default: demosaiced with the 8-bit path's formulas on 16-bit samples -- what cv::demosaicing does for
+ *     CV_16UC1 -- and flipped; the result is 3 x uint16 per pixel, encoding "bgr16", rows * cols * 6 bytes.  Every other
+ *     stage is an 8-bit stage in the reference and must be disabled (RIP_ERR_ASSERT otherwise); no taps are kept.
+ *   range (black, white): demosaiced at 16 bits, narrowed to 8 bits, then the whole pipeline; "bgr8" out, taps kept. */
 rip_status rip_set_debayer_16bit(rip_pipeline* p, int enabled);
+/* Extension: black and white level of bayer_*16 frames.  (0, 0) (default) = off.  With rip_set_debayer_16bit(1) and
+ * 0 <= black < white <= 65535 a bayer_*16 frame is (1) demosaiced at 16 bits by the method of rip_set_debayer_method
+ * ("bilinear": the formulas and border rule above; "mht": the PARITY.md filters on 16-bit samples, clamped to [0, 65535],
+ * reflect-101), (2) narrowed, every channel value v, in integers, with R = white - black:
+ *     n(v) = min(255, floor((510 * max(v - black, 0) + R) / (2 * R)))
+ * -- 255 (v - black) / R rounded half up; values below black give 0, values at or above white 255 -- and (3) processed from
+ * there on exactly like a bgr8 frame holding the narrowed image: flip, white balance (ccc track included), colour matrix,
+ * gamma, vignetting, enhancer, undistortion, the three taps (DEBAYERED = the flipped narrowed image), debug dumps,
+ * rip_get_white_balance_info; the result is 3 x uint8 per pixel, encoding "bgr8".  Input pitches stay in bytes of uint16 rows.
+ * Cost: as for "mht" -- a pass of its own, and without a DEBAYERED tap n_frames x rows x cols x 3 bytes of device memory
+ * (rows padded to 16 bytes) kept by the handle.  Without rip_set_debayer_16bit(1) the range has no effect (the names throw).
+ * Invalid ranges (black < 0, white > 65535, black >= white other than (0, 0)): RIP_ERR_INVALID_ARGUMENT, nothing changed.
+ * Works on RIP_DEVICE_NONE handles.  Params YAML: `debayer: accept_16bit:` (bool, default false), `debayer: black_level:`,
+ * `debayer: white_level:` (ints, default 0); rip_load_params re-creates the modules, so absent keys mean off, and fails with
+ * RIP_ERR_INVALID_ARGUMENT on an invalid range, leaving the parameters as they were. */
+rip_status rip_set_debayer_16bit_range(rip_pipeline* p, int black, int white);
+rip_status rip_get_debayer_16bit_range(const rip_pipeline* p, int* black, int* white); /* either pointer may be null */
 /* Extension beyond the reference: the demosaic of bayer_{rggb,bggr,gbrg,grbg}8 frames (and of bayer_*16 frames under
  * rip_set_debayer_16bit, clamped to [0, 65535]).  "bilinear" (default): the CPU path (debayer.cpp:49-70), what every other
  * function here describes.  "mht": Malvar-He-Cutler, the 5 x 5 gradient-corrected filter the reference's CUDA path runs
@@ -338,6 +357,9 @@ rip_status rip_debug_plan_info(rip_pipeline* p, int src_rows, int src_cols, int 
  * host-built maps); on device handles it compiles the plan as a frame would. */
 rip_status rip_debug_chain_footprint(rip_pipeline* p, int src_rows, int src_cols, int flip_angle, int info[4], int* intervals,
                                      int capacity_pairs);
+/* Test hook: the narrowing of rip_set_debayer_16bit_range on n values, computed on the host with the launch constants and the
+ * arithmetic of the kernel (a multiplication and two shifts instead of the division).  No device, no handle. */
+rip_status rip_debug_raw16_narrow(int black, int white, const uint16_t* in, uint8_t* out, size_t n);
 /* Test hook for the debug dumps: writes image (rows x cols x channels bytes, channels 1 or 3 = BGR) to path as the PNG
  * writer of rip_set_debug does, after the reference's min-max normalisation when normalize != 0.  No device needed;
  * p may be NULL. */

@@ -118,7 +118,12 @@ bool is_bayer16(const std::string& e) {
 // What one frame geometry/encoding turns into
 struct Plan {
   int src_kind = rip::SRC_BGR, ry = 0, rx = 0;
-  int elem_bytes = 1;     // 2: the 16-bit Bayer extension (debayer + flip only, bgr16 out)
+  int in_elem_bytes = 1;   // bytes per input sample: 2 for bayer_*16 frames (rip_set_debayer_16bit)
+  int out_elem_bytes = 1;  // bytes per output sample: 2 = the 16-bit extension with the range off (debayer + flip only, bgr16 out)
+  // bayer_*16 frames with a 16-bit range (rip_set_debayer_16bit_range): demosaiced at 16 bits, narrowed to 8 bits with
+  // (black, white) and flipped by one pass of its own (rip_raw16.hip), then the whole chain as for a bgr8 frame
+  bool raw16 = false;
+  int black = 0, white = 0;
   bool mht = false;       // Bayer input demosaiced by Malvar-He-Cutler (rip_set_debayer_method "mht") instead of bilinear
   int channels = 3;       // channels after the debayer stage
   int flip_angle = 0;     // effective
@@ -799,9 +804,17 @@ Plan make_plan(const rip_pipeline* p, int rows, int cols, int channels, const st
     std::string e8 = encoding.substr(0, encoding.size() - 2) + "8";
     parse_bayer(e8, pl.ry, pl.rx);
     pl.src_kind = rip::SRC_BAYER;
-    pl.elem_bytes = 2;
+    pl.in_elem_bytes = 2;
     pl.channels = 3;
-    pl.encoding_out = "bgr16";
+    if (m.raw16_white > 0) {  // narrowed right after the demosaic: an 8-bit frame from there on
+      pl.raw16 = true;
+      pl.black = m.raw16_black;
+      pl.white = m.raw16_white;
+      pl.encoding_out = "bgr8";
+    } else {
+      pl.out_elem_bytes = 2;
+      pl.encoding_out = "bgr16";
+    }
   } else if (encoding == "rgb8") {
     if (channels != 3) throw AssertError("cvtColor(RGB2BGR): rgb8 input must have three channels");
     pl.src_kind = rip::SRC_RGB;  // swapped to BGR; the encoding string stays "rgb8" (debayer.cpp:72-73)
@@ -843,7 +856,7 @@ Plan make_plan(const rip_pipeline* p, int rows, int cols, int channels, const st
   }
   if (m.ce_enabled && pl.channels == 3) pl.stage_bits |= rip::ST_HSV;
   pl.remap = m.und_enabled && m.und_available && m.dist_model != "none";
-  if (pl.elem_bytes == 2 && (pl.wb_mode != rip::WB_NONE || pl.stage_bits != 0 || pl.remap))
+  if (pl.out_elem_bytes == 2 && (pl.wb_mode != rip::WB_NONE || pl.stage_bits != 0 || pl.remap))
     // every later module of the reference works on 8-bit images (cv::LUT, xphoto white balance, 8-bit Lab / HSV tables)
     // and would assert on CV_16UC3
     throw AssertError("16-bit Bayer frames go through debayer and flip only: disable white balance, colour calibration, gamma, "
@@ -865,6 +878,49 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
   // image -- the DEBAYERED tap (flip.cpp:60-62), into the caller's tap buffer when one was requested -- and the rest of the
   // chain runs on that image exactly as on a bgr8 frame holding it, with no flip left to do.  16-bit frames: the kernel writes
   // the bgr16 result and that is all.
+  // 16-bit frames with a range (rip_set_debayer_16bit_range, rip_raw16.hip) take the same route with either method: demosaic at
+  // 16 bits + narrowing + flip in one pass, into the same destination, and the chain on the narrowed image.
+  if (pl.raw16) {
+    rip::Raw16Params d = {};
+    d.src = d_in;
+    d.src_step = in_step;
+    d.src_frame_stride = in_frame_stride;
+    d.rows = rows;
+    d.cols = cols;
+    d.bayer_ry = pl.ry;
+    d.bayer_rx = pl.rx;
+    d.mht = pl.mht ? 1 : 0;
+    d.black = pl.black;
+    d.white = pl.white;
+    d.flip_angle = pl.flip_angle;
+    d.n_frames = n;
+    if (d_tap_deb) {
+      d.dst = d_tap_deb;
+      d.dst_step = (size_t)pl.mid_cols * 3;
+      d.dst_frame_stride = d.dst_step * pl.mid_rows;
+    } else {
+      // 16-byte aligned rows and frames: what launch_remap_tiled asks of the image it gathers from
+      d.dst_step = ((size_t)pl.mid_cols * 3 + 15) & ~(size_t)15;
+      d.dst_frame_stride = d.dst_step * pl.mid_rows;
+      p->d_mht.reserve(d.dst_frame_stride * (size_t)n);
+      d.dst = p->d_mht.as<uint8_t>();
+    }
+    {
+      ProfScope ps(p, RIP_KERNEL_CHAIN, p->stream);
+      rip::launch_raw16(d, p->stream);
+    }
+    hipError_t ler = hipGetLastError();
+    if (ler != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(ler));
+    Plan s = pl;
+    s.raw16 = s.mht = false;
+    s.in_elem_bytes = 1;
+    s.src_kind = rip::SRC_BGR;
+    s.ry = s.rx = 0;
+    s.flip_angle = 0;
+    run_batch(p, s, d.dst, d.dst_step, d.dst_frame_stride, n, pl.mid_rows, pl.mid_cols, d_out, out_step, out_frame_stride, nullptr,
+              d_tap_col, reuse_wb);
+    return;
+  }
   if (pl.mht) {
     rip::MhtParams d = {};
     d.src = d_in;
@@ -874,12 +930,12 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
     d.cols = cols;
     d.bayer_ry = pl.ry;
     d.bayer_rx = pl.rx;
-    d.elem_bytes = pl.elem_bytes;
+    d.elem_bytes = pl.in_elem_bytes;
     d.drows = pl.mid_rows;
     d.dcols = pl.mid_cols;
     d.flip_angle = pl.flip_angle;
     d.n_frames = n;
-    if (pl.elem_bytes == 2) {
+    if (pl.out_elem_bytes == 2) {
       d.dst = d_out;
       d.dst_step = out_step ? out_step : (size_t)pl.out_cols * 6;
       d.dst_frame_stride = out_frame_stride ? out_frame_stride : d.dst_step * pl.out_rows;
@@ -900,7 +956,7 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
     }
     hipError_t lem = hipGetLastError();
     if (lem != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(lem));
-    if (pl.elem_bytes == 2) {
+    if (pl.out_elem_bytes == 2) {
       p->last_batch_frames = 0;  // no white balance ran (as on the bilinear 16-bit path)
       return;
     }
@@ -913,7 +969,7 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
               d_tap_col, reuse_wb);
     return;
   }
-  if (pl.elem_bytes == 2) {  // 16-bit Bayer extension: one kernel, no taps
+  if (pl.out_elem_bytes == 2) {  // 16-bit Bayer extension with the range off: one kernel, no taps
     rip::Debayer16Params d = {};
     d.src = d_in;
     d.src_step = in_step;
@@ -1560,10 +1616,11 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     if (n_frames < 0) throw InvalidArgument("negative frame count");
     if (n_frames == 0) return;
     Plan pl = make_plan(p, rows, cols, channels, encoding);
-    const size_t eb = (size_t)pl.elem_bytes;
-    if (in_step == 0) in_step = (size_t)cols * channels * eb;
+    const size_t ib = (size_t)pl.in_elem_bytes, eb = (size_t)pl.out_elem_bytes;
+    if (in_step == 0) in_step = (size_t)cols * channels * ib;
     if (in_frame_stride == 0) in_frame_stride = in_step * rows;
-    if (in_step < (size_t)cols * channels * eb) throw InvalidArgument("input row pitch smaller than a row");
+    if (in_step < (size_t)cols * channels * ib) throw InvalidArgument("input row pitch smaller than a row");
+    // bgr16 results (the 16-bit range is off); with a range the frame is an 8-bit one after the demosaic and keeps its taps
     if (eb == 2 && (d_tap_debayered || d_tap_color)) throw InvalidArgument("16-bit Bayer frames have no taps");
     // several kernels put the frame index on gridDim.y (<= 65535): longer batches go through in slices.  The
     // frames of a stream are processed in order either way (the ccc Kalman state lives on the device).
@@ -1574,7 +1631,7 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     // express (and pitches that would make rows or frames overlap) instead of writing somewhere else
     if (o_step < (size_t)pl.out_cols * pl.channels * eb) throw InvalidArgument("output row pitch smaller than a row");
     if (o_stride < o_step * (size_t)pl.out_rows) throw InvalidArgument("output frame stride smaller than a frame");
-    if (in_frame_stride < in_step * (size_t)(rows - 1) + (size_t)cols * channels * eb) throw InvalidArgument("input frame stride smaller than a frame");
+    if (in_frame_stride < in_step * (size_t)(rows - 1) + (size_t)cols * channels * ib) throw InvalidArgument("input frame stride smaller than a frame");
     if (in_step >= (1u << 24) || o_step >= (1u << 24) || (unsigned long long)in_step * rows >= (1ull << 32) ||
         (unsigned long long)o_step * pl.out_rows >= (1ull << 32))
       throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
@@ -1597,9 +1654,9 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     if (!image || !out || !encoding) throw InvalidArgument("null buffer or encoding");
     Plan pl = make_plan(p, rows, cols, channels, encoding);
     DeviceGuard device_guard(p->device);
-    const size_t eb = (size_t)pl.elem_bytes;
-    if (step == 0) step = (size_t)cols * channels * eb;
-    const size_t in_pitch = ((size_t)cols * channels * eb + 3) & ~(size_t)3;  // dword-aligned rows on the device
+    const size_t ib = (size_t)pl.in_elem_bytes, eb = (size_t)pl.out_elem_bytes;
+    if (step == 0) step = (size_t)cols * channels * ib;
+    const size_t in_pitch = ((size_t)cols * channels * ib + 3) & ~(size_t)3;  // dword-aligned rows on the device
     const size_t in_bytes = in_pitch * rows;
     const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb;
     const size_t mid_bytes = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
@@ -1616,7 +1673,7 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
       p->d_tap_col.reserve(mid_bytes);
       tap_col = p->d_tap_col.as<uint8_t>();
     }
-    HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, in_pitch, image, step, (size_t)cols * channels * eb, (size_t)rows, hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, in_pitch, image, step, (size_t)cols * channels * ib, (size_t)rows, hipMemcpyHostToDevice, p->stream));
     run_batch(p, pl, p->d_in.as<uint8_t>(), in_pitch, in_bytes, 1, rows, cols, p->d_out.as<uint8_t>(), 0, 0, tap_deb, tap_col);
     HIP_CHECK(hipMemcpyAsync(out, p->d_out.ptr, out_bytes, hipMemcpyDeviceToHost, p->stream));
     HIP_CHECK(hipStreamSynchronize(p->stream));
@@ -1662,7 +1719,7 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     if (!image || !encoding || !ticket) throw InvalidArgument("null buffer, encoding or ticket");
     Plan pl = make_plan(p, rows, cols, channels, encoding);
     {  // destinations given by the caller (rip_submit_to): checked before anything is enqueued or any slot is touched
-      const size_t eb0 = (size_t)pl.elem_bytes;
+      const size_t eb0 = (size_t)pl.out_elem_bytes;
       const size_t out_need = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb0, mid_need = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
       if (ext_out && ext_out_capacity < out_need) throw CapacityError("rip_submit_to: result buffer too small: need " + std::to_string(out_need) + " bytes");
       if ((ext_deb || ext_col) && ext_tap_capacity < mid_need) throw CapacityError("rip_submit_to: tap buffer too small: need " + std::to_string(mid_need) + " bytes");
@@ -1702,9 +1759,9 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
       for (int i = 0; i < 3; i++)
         if (p->last_buf[i] == &sl.d_tap_deb || p->last_buf[i] == &sl.d_tap_col || p->last_buf[i] == &sl.d_out) p->last_valid[i] = false;
     }
-    const size_t eb = (size_t)pl.elem_bytes;
-    if (step == 0) step = (size_t)cols * channels * eb;
-    const size_t in_pitch = ((size_t)cols * channels * eb + 3) & ~(size_t)3;  // dword-aligned rows on the device
+    const size_t ib = (size_t)pl.in_elem_bytes, eb = (size_t)pl.out_elem_bytes;
+    if (step == 0) step = (size_t)cols * channels * ib;
+    const size_t in_pitch = ((size_t)cols * channels * ib + 3) & ~(size_t)3;  // dword-aligned rows on the device
     const size_t in_bytes = in_pitch * rows;
     const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb;
     const size_t mid_bytes = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
@@ -1728,7 +1785,7 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     // untouched until its ticket is collected.  Anything else is copied into the slot's pinned staging buffer first, so the
     // caller's buffer is free again when this call returns whatever the runtime does with an asynchronous 2-D copy from
     // pageable memory (above its staging threshold it pins the pages in place and copies after the call has returned).
-    const size_t row_bytes = (size_t)cols * channels * eb;
+    const size_t row_bytes = (size_t)cols * channels * ib;
     inflight_gate().forget(sl.gate_device, sl.ev_done);  // the slot's previous frame (collected, or it would not have been picked)
     inflight_gate().admit(p->device);
     if (sl.ev_start) HIP_CHECK(hipEventRecord(sl.ev_start, p->ul_stream));
@@ -1787,7 +1844,7 @@ rip_status rip_collect(rip_pipeline* p, uint64_t ticket, uint8_t* out, size_t ou
       if (s->busy && s->ticket == ticket) sl = s.get();
     if (!sl) throw InvalidArgument("rip_collect: ticket " + std::to_string(ticket) + " is not in flight");
     const Plan& pl = sl->pl;
-    const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * (size_t)pl.elem_bytes;
+    const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * (size_t)pl.out_elem_bytes;
     if (out && out_capacity < out_bytes) throw CapacityError("output buffer too small: need " + std::to_string(out_bytes) + " bytes");
     DeviceGuard device_guard(p->device);
     HIP_CHECK(hipEventSynchronize(sl->ev_done));
@@ -1810,7 +1867,7 @@ rip_status rip_collect(rip_pipeline* p, uint64_t ticket, uint8_t* out, size_t ou
     for (auto& c : p->ring) c->held = false;  // the frame collected before this one lets go of its slot
     sl->busy = false;
     sl->held = true;
-    const bool eb1 = pl.elem_bytes == 1;
+    const bool eb1 = pl.out_elem_bytes == 1;
     auto remember = [&](int which, DevBuf* buf, const void* host, int r, int c, bool on) {
       p->last_valid[which] = on;
       p->last_buf[which] = buf;
@@ -2030,6 +2087,8 @@ rip_status rip_set_debug(rip_pipeline* p, int v) {
 
 RIP_SETTER(rip_set_debayer, (rip_pipeline * p, int v), p->m.debayer_enabled = v != 0)
 RIP_SETTER(rip_set_debayer_16bit, (rip_pipeline * p, int v), p->m.debayer_16bit = v != 0)
+RIP_SETTER(rip_set_debayer_16bit_range, (rip_pipeline * p, int black, int white), rip::check_debayer_16bit_range(black, white);
+           p->m.raw16_black = black; p->m.raw16_white = white)
 RIP_SETTER(rip_set_debayer_encoding, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.debayer_encoding = s)
 RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            rip::check_debayer_method(s); p->m.debayer_method = s)
@@ -2100,6 +2159,30 @@ rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t cap) 
   return guarded(p, [&] {
     need(p);
     copy_string(p->m.debayer_method, out, cap);
+  });
+}
+
+rip_status rip_get_debayer_16bit_range(const rip_pipeline* p, int* black, int* white) {
+  return guarded(p, [&] {
+    need(p);
+    if (black) *black = p->m.raw16_black;
+    if (white) *white = p->m.raw16_white;
+  });
+}
+
+rip_status rip_debug_raw16_narrow(int black, int white, const uint16_t* in, uint8_t* out, size_t n) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    rip::check_debayer_16bit_range(black, white);
+    if ((black == 0 && white == 0) || (n && (!in || !out))) throw InvalidArgument("rip_debug_raw16_narrow: a range and buffers are needed");
+    uint32_t mul;
+    int shift;
+    rip::raw16_narrow_constants(black, white, &mul, &shift);
+    const int range = white - black;
+    for (size_t i = 0; i < n; i++) {  // Narrow::operator() of rip_raw16.hip, statement for statement
+      const int t = std::min(std::max((int)in[i] - black, 0), range);
+      const uint32_t num = (uint32_t)t * 510u + (uint32_t)range;
+      out[i] = (uint8_t)((uint32_t)(((uint64_t)(num << 6) * mul) >> 32) >> shift);
+    }
   });
 }
 

@@ -292,7 +292,14 @@ void params_from_node(Modules& m, const YamlNode& node) {
   // fails the load and leaves every parameter as it was.
   const std::string debayer_method = node["debayer"].get("method", std::string("bilinear"));
   check_debayer_method(debayer_method);
+  // extension keys debayer: accept_16bit: / black_level: / white_level: (rip_set_debayer_16bit, rip_set_debayer_16bit_range);
+  // loadParams re-creates the modules, so absent keys mean off.  An invalid range fails the load like an unknown method.
+  const int black_level = node["debayer"].get("black_level", 0), white_level = node["debayer"].get("white_level", 0);
+  check_debayer_16bit_range(black_level, white_level);
   m.debayer_method = debayer_method;
+  m.debayer_16bit = node["debayer"].get("accept_16bit", false);
+  m.raw16_black = black_level;
+  m.raw16_white = white_level;
   // raw_image_pipeline.cpp:54-160, defaults as written there
   m.debayer_enabled = node["debayer"].get("enabled", true);
   m.debayer_encoding = node["debayer"].get("encoding", std::string("auto"));
@@ -370,6 +377,13 @@ void apply_example_params(Modules& m) {
 void check_debayer_method(const std::string& method) {
   if (method != "bilinear" && method != "mht")
     throw std::invalid_argument("Debayer method [" + method + "] not supported. Supported methods: 'bilinear', 'mht'");
+}
+
+void check_debayer_16bit_range(int black, int white) {
+  if (black == 0 && white == 0) return;  // off
+  if (black < 0 || white > 65535 || black >= white)
+    throw std::invalid_argument("16-bit range (" + std::to_string(black) + ", " + std::to_string(white) +
+                                ") not supported: (0, 0) switches it off, otherwise 0 <= black < white <= 65535");
 }
 
 bool load_params_file(Modules& m, const std::string& path) {

@@ -51,6 +51,9 @@ struct Modules {
   bool debayer_enabled = true;
   std::string debayer_encoding = "auto";
   bool debayer_16bit = false;  // extension (rip_set_debayer_16bit): accept bayer_*16 instead of throwing like the reference
+  // extension (rip_set_debayer_16bit_range): black and white level of bayer_*16 frames; (0, 0) = off (bgr16 out, no other
+  // stage); 0 <= black < white <= 65535: narrowed to 8 bits right after the demosaic, then the whole chain (PARITY.md)
+  int raw16_black = 0, raw16_white = 0;
   // extension (rip_set_debayer_method): "bilinear" (the CPU path, debayer.cpp:49-70) or "mht" (Malvar-He-Cutler, what the
   // CUDA path's cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT) computes, debayer.cpp:93-108)
   std::string debayer_method = "bilinear";
@@ -93,6 +96,8 @@ void apply_example_params(Modules& m);  // the values of config/pipeline_params_
 bool load_params_file(Modules& m, const std::string& path);             // raw_image_pipeline.cpp:44-165
 // the demosaic methods rip_set_debayer_method accepts; throws std::invalid_argument naming them for any other name
 void check_debayer_method(const std::string& method);
+// the 16-bit ranges rip_set_debayer_16bit_range accepts: (0, 0) or 0 <= black < white <= 65535; throws std::invalid_argument
+void check_debayer_16bit_range(int black, int white);
 bool load_camera_calibration_file(Modules& m, const std::string& path); // undistortion.cpp:157-195
 bool load_color_calibration_file(Modules& m, const std::string& path);  // color_calibration.cpp:52-76
 void apply_example_camera_calibration(Modules& m);  // values of config/alphasense_calib_example.yaml

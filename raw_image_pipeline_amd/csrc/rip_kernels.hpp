@@ -137,6 +137,24 @@ struct MhtParams {
   int src_aligned4, dst_aligned4, frame_groups;  // set by the launcher
 };
 
+// rip_raw16.hip: bayer_*16 frames with a 16-bit range (rip_set_debayer_16bit_range): demosaic at 16 bits (bilinear or
+// Malvar-He-Cutler) + narrowing to 8 bits + flip in one pass, interleaved BGR of uint8 out.  Pitches and strides in BYTES.
+struct Raw16Params {
+  const uint8_t* src;
+  size_t src_step, src_frame_stride;
+  int rows, cols, bayer_ry, bayer_rx;
+  int mht;           // 0: bilinear (debayer16_kernel's formulas and border rule), 1: Malvar-He-Cutler (reflect-101)
+  int black, white;  // 0 <= black < white <= 65535
+  uint8_t* dst;
+  size_t dst_step, dst_frame_stride;
+  int flip_angle, n_frames;
+  // set by the launcher: n(v) = (((510 * clamp(v - black, 0, range) + range) << 6) * mul) >> (32 + shift)
+  int range;
+  uint32_t mul;
+  int shift;
+  int src_aligned4, dst_aligned4, frame_groups;
+};
+
 struct StatsParams {
   const uint8_t* src;
   size_t src_step, src_frame_stride;
@@ -294,6 +312,10 @@ bool launch_remap_fused_fc1(const RemapTiledParams& p, const ChainParams& c, int
                             bool dry_run);
 void launch_debayer16(const Debayer16Params& p, hipStream_t stream);
 void launch_demosaic_mht(const MhtParams& p, hipStream_t stream);
+void launch_raw16(const Raw16Params& p, hipStream_t stream);
+// the launch constants of the narrowing n(v) = min(255, floor((510 * max(v - black, 0) + R) / (2 R))), R = white - black: a
+// multiplier and a shift that replace the division exactly for every numerator below 2^26 (host code; the tests check it)
+void raw16_narrow_constants(int black, int white, uint32_t* mul, int* shift);
 // which kernel launch_demosaic_mht takes: 1 the LDS-tiled 8-bit kernel (every flip), 0 one thread per pixel (16-bit)
 int mht_uses_tile_path(const MhtParams& p);
 // builds the image ChainParams::vig_image points to (vig_image_bytes() bytes) from the handle's tables

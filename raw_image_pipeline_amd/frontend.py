@@ -19,6 +19,8 @@ NODE_DEFAULTS = OrderedDict([
     ("use_gpu", True), ("debug", False),
     ("debayer/enabled", True), ("debayer/encoding", "auto"),
     ("debayer/method", "bilinear"),  # extension: "mht" selects the CUDA path's Malvar-He-Cutler demosaic (rip.h)
+    # extension: bayer_*16 frames (rip.h rip_set_debayer_16bit / rip_set_debayer_16bit_range); levels (0, 0) = no range
+    ("debayer/accept_16bit", False), ("debayer/black_level", 0), ("debayer/white_level", 0),
     ("flip/enabled", False), ("flip/angle", 0),
     ("white_balance/enabled", False), ("white_balance/method", "simple"), ("white_balance/clipping_percentile", 10.0),
     ("white_balance/saturation_bright_thr", 0.9), ("white_balance/saturation_dark_thr", 0.1),
@@ -85,6 +87,8 @@ class CameraStream:
         pipe.set_debayer(p["debayer/enabled"])
         pipe.set_debayer_encoding(p["debayer/encoding"])
         pipe.set_debayer_method(p["debayer/method"])
+        pipe.set_debayer_16bit(p["debayer/accept_16bit"])
+        pipe.set_debayer_16bit_range(p["debayer/black_level"], p["debayer/white_level"])
         pipe.set_flip(p["flip/enabled"])
         pipe.set_flip_angle(p["flip/angle"])
         pipe.set_white_balance(p["white_balance/enabled"])
@@ -180,7 +184,7 @@ class CameraStream:
             rows, cols = img.shape[:2]
             cn = 1 if img.ndim == 2 else img.shape[2]
             r, c, k, enc_out = self.pipe.query_output(rows, cols, cn, encoding)
-            if not enc_out.endswith("16"):
+            if not enc_out.endswith("16"):  # bgr16 results (bayer_*16 without a range) have no taps and no pool arrays
                 dst["out"] = self._pinned_pool.take((r, c) if k == 1 else (r, c, k), or_none=True)
                 tr, tc, tk = self.pipe.query_taps(rows, cols, cn, encoding)
                 if self._tap_mask & TAP_DEBAYERED:

@@ -216,7 +216,9 @@ class RawImagePipeline:
     def process(self, image, encoding):
         """cv::Mat process(const cv::Mat&, std::string&): returns a new array; input untouched."""
         img = np.asarray(image)
-        wide = img.dtype == np.uint16  # 16-bit Bayer extension (set_debayer_16bit): uint16 in, uint16 BGR out
+        # 16-bit Bayer extension (set_debayer_16bit): uint16 in; uint16 BGR out, or -- with a 16-bit range
+        # (set_debayer_16bit_range) -- the whole pipeline and uint8 bgr8 out
+        wide = img.dtype == np.uint16
         if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3):
             raise ValueError("image must be uint8 (or uint16 Bayer), HxW or HxWxC")
         if img.strides[-1] != img.itemsize or (img.ndim == 3 and img.strides[1] != img.shape[2] * img.itemsize):
@@ -224,10 +226,10 @@ class RawImagePipeline:
         rows, cols = img.shape[:2]
         cn = 1 if img.ndim == 2 else img.shape[2]
         orows, ocols, ocn, oenc = self.query_output(rows, cols, cn, encoding)
-        if wide != oenc.endswith("16"):
+        if wide != encoding.endswith("16"):
             raise ValueError("dtype %s does not match encoding %s" % (img.dtype, encoding))
         oshape = (orows, ocols) if ocn == 1 else (orows, ocols, ocn)
-        odtype = np.uint16 if wide else np.uint8
+        odtype = np.uint16 if oenc.endswith("16") else np.uint8
         out = self.out_pool.take(oshape, odtype) if self.out_pool is not None else np.empty(oshape, odtype)
         r, c, k = C.c_int(), C.c_int(), C.c_int()
         enc = C.create_string_buffer(32)
@@ -262,6 +264,8 @@ class RawImagePipeline:
             img = np.ascontiguousarray(img)
         rows, cols = img.shape[:2]
         cn = 1 if img.ndim == 2 else img.shape[2]
+        if (img.dtype == np.uint16) != encoding.endswith("16"):
+            raise ValueError("dtype %s does not match encoding %s" % (img.dtype, encoding))
         t = C.c_uint64()
         given = (out, tap_debayered, tap_color)
         if all(g is None for g in given):
@@ -311,11 +315,21 @@ class RawImagePipeline:
     def apply_device(self, frames, encoding, out=None, tap_debayered=None, tap_color=None):
         """Device-resident batch (rip_apply_device).  ``frames``: uint8 CUDA tensor [n, rows, cols]
         or [n, rows, cols, c] (torch) already in HBM; returns the output tensor [n, R, C(, 3)].
-        Asynchronous on the handle's stream."""
+        Asynchronous on the handle's stream.
+
+        bayer_*16 frames (``set_debayer_16bit``): the uint8 view [n, rows, cols * 2] of the uint16 rows, pitches in bytes.
+        With a 16-bit range (``set_debayer_16bit_range``) the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be
+        given; without one it is bgr16 as bytes, [n, R, C, 6]."""
         import torch
         if frames.dtype != torch.uint8 or not frames.is_cuda:
             raise ValueError("frames must be a uint8 CUDA tensor")
-        if frames.dim() == 3:
+        wide = encoding.endswith("16")
+        if wide:
+            if frames.dim() != 3 or frames.shape[2] % 2:
+                raise ValueError("16-bit frames must be the uint8 view [n, rows, cols * 2] of uint16 rows")
+            n, rows, cols = frames.shape[0], frames.shape[1], frames.shape[2] // 2
+            cn = 1
+        elif frames.dim() == 3:
             n, rows, cols = frames.shape
             cn = 1
         elif frames.dim() == 4:
@@ -327,7 +341,7 @@ class RawImagePipeline:
         in_step = frames.stride(1)
         in_frame = frames.stride(0) if n > 1 else in_step * rows
         orows, ocols, ocn, enc = self.query_output(rows, cols, cn, encoding)
-        shape = (n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn)
+        shape = (n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn * (2 if enc.endswith("16") else 1))
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
         elif tuple(out.shape) != shape or not out.is_contiguous():
@@ -468,8 +482,21 @@ class RawImagePipeline:
         self._call("rip_set_debayer", int(bool(enabled)))
 
     def set_debayer_16bit(self, enabled):
-        """Extension: accept bayer_*16 frames (debayer + flip only, bgr16 out) instead of raising like the reference."""
+        """Extension: accept bayer_*16 frames instead of raising like the reference: debayer + flip only and bgr16 out, or --
+        with ``set_debayer_16bit_range`` -- the whole pipeline and bgr8 out."""
         self._call("rip_set_debayer_16bit", int(bool(enabled)))
+
+    def set_debayer_16bit_range(self, black, white):
+        """Extension: black and white level of bayer_*16 frames; (0, 0) = off.  With ``set_debayer_16bit(True)`` and
+        0 <= black < white <= 65535 such a frame is demosaiced at 16 bits, narrowed to 8 bits (255 (v - black) / (white - black),
+        rounded half up, clamped) and then processed like a bgr8 frame: every stage, the taps, uint8 ``bgr8`` out.
+        include/rip.h rip_set_debayer_16bit_range."""
+        self._call("rip_set_debayer_16bit_range", int(black), int(white))
+
+    def get_debayer_16bit_range(self):
+        b, w = C.c_int(), C.c_int()
+        self._call("rip_get_debayer_16bit_range", C.byref(b), C.byref(w))
+        return b.value, w.value
 
     def set_debayer_encoding(self, encoding):
         self._call("rip_set_debayer_encoding", encoding.encode())
