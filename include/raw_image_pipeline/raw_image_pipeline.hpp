@@ -140,7 +140,7 @@ class RawImagePipeline {
   // copy), valid until the next collect*() on this object.
   uint64_t submit(const Mat& image, const std::string& encoding) {
     uint64_t ticket = 0;
-    check(rip_submit(h_, detail::bytes(image), image.rows, image.cols, image.channels(), detail::step_of(image), encoding.c_str(), &ticket));
+    check(rip_submit(h_, detail::bytes(image), image.rows, pixel_cols(image, encoding), image.channels(), detail::step_of(image), encoding.c_str(), &ticket));
     return ticket;
   }
   // submit() with the destinations named by the caller (rip_submit_to): `out` -- and the taps the object keeps, when given --
@@ -151,7 +151,7 @@ class RawImagePipeline {
   uint64_t submitTo(const Mat& image, const std::string& encoding, Mat& out, Mat* tap_debayered = nullptr, Mat* tap_color = nullptr) {
     uint64_t ticket = 0;
     const Mat* tap = tap_debayered ? tap_debayered : tap_color;
-    check(rip_submit_to(h_, detail::bytes(image), image.rows, image.cols, image.channels(), detail::step_of(image), encoding.c_str(),
+    check(rip_submit_to(h_, detail::bytes(image), image.rows, pixel_cols(image, encoding), image.channels(), detail::step_of(image), encoding.c_str(),
                         detail::bytes(out), (size_t)out.rows * out.cols * out.channels(), tap_debayered ? detail::bytes(*tap_debayered) : nullptr,
                         tap_color ? detail::bytes(*tap_color) : nullptr, tap ? (size_t)tap->rows * tap->cols * tap->channels() : 0, &ticket));
     return ticket;
@@ -210,6 +210,16 @@ class RawImagePipeline {
     check(rip_get_debayer_16bit_range(h_, &black, &white));
     return {black, white};
   }
+
+  // not in the reference: packed 10- / 12-bit Bayer frames (rip.h "Packed Bayer frames": bayer_*10p, *12p, *10_csi2, *12_csi2).
+  // The input is a one-channel uint8 Mat (CV_8UC1) of rows x ROW BYTES; apply / process / submit / submitTo return ordinary
+  // uint8 "bgr8" Mats.  The pixels per row are setDebayerPackedWidth(); 0 (default) infers 8 * row bytes / B, which is exact
+  // for Mats whose columns are the tight rows of any width -- set the width when the Mat's rows carry padding columns.
+  void setDebayerPackedWidth(int width) {
+    if (width < 0) throw std::invalid_argument("setDebayerPackedWidth: the width must be positive, or 0 to infer it");
+    packed_width_ = width;
+  }
+  int getDebayerPackedWidth() const { return packed_width_; }
 
   void setFlip(bool enabled) { check(rip_set_flip(h_, enabled)); }
   void setFlipAngle(int angle) { check(rip_set_flip_angle(h_, angle)); }
@@ -324,12 +334,25 @@ class RawImagePipeline {
   void check(rip_status st) const {
     if (st != RIP_OK) raise(st, rip_last_error(h_));
   }
+  // bits per sample of a packed Bayer encoding, 0 for every other name
+  static int packed_bits(const std::string& e) {
+    if (e.size() < 13 || e.compare(0, 6, "bayer_") != 0) return 0;
+    const std::string s = e.substr(10);
+    return s == "10p" || s == "10_csi2" ? 10 : s == "12p" || s == "12_csi2" ? 12 : 0;
+  }
+  // the `cols` of the C interface: pixels, where a packed frame's Mat counts row bytes
+  int pixel_cols(const Mat& in, const std::string& encoding) const {
+    const int bits = packed_bits(encoding);
+    if (!bits) return in.cols;
+    return packed_width_ ? packed_width_ : (int)(8 * (long long)in.cols / bits);
+  }
   Mat run(const Mat& in, std::string& encoding) {
     int rows = 0, cols = 0, cn = 0;
     char enc[32] = {0};
-    check(rip_query_output(h_, in.rows, in.cols, in.channels(), encoding.c_str(), &rows, &cols, &cn, enc));
+    const int in_cols = pixel_cols(in, encoding);
+    check(rip_query_output(h_, in.rows, in_cols, in.channels(), encoding.c_str(), &rows, &cols, &cn, enc));
     Mat out = detail::make_u8(rows, cols, cn);
-    check(rip_apply(h_, detail::bytes(in), in.rows, in.cols, in.channels(), detail::step_of(in), encoding.c_str(), detail::bytes(out),
+    check(rip_apply(h_, detail::bytes(in), in.rows, in_cols, in.channels(), detail::step_of(in), encoding.c_str(), detail::bytes(out),
                     (size_t)rows * cols * cn, &rows, &cols, &cn, enc));
     encoding = enc;
     return out;
@@ -362,6 +385,7 @@ class RawImagePipeline {
   }
 
   rip_pipeline* h_ = nullptr;
+  int packed_width_ = 0;
 };
 
 }  // namespace raw_image_pipeline

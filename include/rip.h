@@ -79,7 +79,23 @@ rip_status rip_set_stream(rip_pipeline* p, void* hip_stream);
  * uploads `image` (rows x cols x channels, `step` bytes per row), runs the chain, downloads
  * into `out` (tightly packed, capacity in bytes) and rewrites the encoding ("bayer_*8" ->
  * "bgr8").  The reference re-seats the caller's Mat; here the caller passes the output
- * buffer, whose geometry is returned (90/270 flips swap rows/cols).  Synchronous. */
+ * buffer, whose geometry is returned (90/270 flips swap rows/cols).  Synchronous.
+ *
+ * Packed Bayer frames (extension beyond the reference): bayer_{rggb,bggr,gbrg,grbg} followed by one of
+ *   10p       PFNC lsb-first bit stream (BayerRG10p ...): sample x of a row is bits [10 x, 10 x + 10) of its bytes read as a
+ *             little-endian bit string
+ *   12p       the same with 12 bits (BayerRG12p ...): even x: b[k] | (b[k+1] & 15) << 8, odd x: b[k] >> 4 | b[k+1] << 4, k = 12 x >> 3
+ *   10_csi2   MIPI CSI-2 RAW10: groups of 4 samples in 5 bytes, g = x >> 2, j = x & 3: b[5g+j] << 2 | (b[5g+4] >> 2j) & 3
+ *   12_csi2   MIPI CSI-2 RAW12: groups of 2 samples in 3 bytes, g = x >> 1: even x: b[3g] << 4 | b[3g+2] & 15,
+ *             odd x: b[3g+1] << 4 | b[3g+2] >> 4
+ * `rows` and `cols` count PIXELS, channels is 1, and a row occupies ceil(cols * B / 8) bytes (B = 10 or 12) from
+ * image + y * step; `step` is in bytes, 0 = tight, smaller than a row: RIP_ERR_INVALID_ARGUMENT.  Bits of a row's last byte
+ * beyond its last pixel and bytes beyond its payload are never interpreted.  The p layouts take any cols >= 3; 10_csi2 needs
+ * cols % 4 == 0 and 12_csi2 cols % 2 == 0 (whole groups; RIP_ERR_INVALID_ARGUMENT otherwise); rows >= 3.  The bytes are
+ * unpacked inside the demosaic kernel, and the frame produces exactly what the bayer_<pattern>16 frame holding the unpacked
+ * samples produces under rip_set_debayer_16bit(1) and the effective range: the one of rip_set_debayer_16bit_range when one is
+ * set, else the format's natural range (0, 2^B - 1).  The result is always "bgr8" (never bgr16), with taps, and does not
+ * depend on rip_set_debayer_16bit. */
 rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, int channels, size_t step,
                      const char* encoding, uint8_t* out, size_t out_capacity, int* out_rows, int* out_cols,
                      int* out_channels, char encoding_out[32]);
@@ -100,7 +116,10 @@ rip_status rip_query_taps(rip_pipeline* p, int rows, int cols, int channels, con
  * d_out (frame stride out_frame_stride, row pitch out_step bytes; 0 = tightly packed).
  * Asynchronous on the handle's stream; frames are processed in order (the ccc Kalman state
  * advances frame by frame).  d_tap_debayered / d_tap_color (may be NULL) receive the
- * per-frame taps, tightly packed, same frame count. */
+ * per-frame taps, tightly packed, same frame count.  Packed Bayer frames (rip_apply): rows / cols in pixels, in_step in
+ * bytes (0 = ceil(cols * B / 8)); tiles of a 4-aligned d_in / in_step / in_frame_stride are read in aligned dwords -- the last
+ * dword of a row's span may reach into the pitch, never beyond it and never beyond the last row's payload --, any other
+ * alignment is read byte by byte. */
 rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, size_t in_frame_stride,
                             int n_frames, int rows, int cols, int channels, const char* encoding, void* d_out,
                             size_t out_step, size_t out_frame_stride, void* d_tap_debayered, void* d_tap_color);
@@ -360,6 +379,10 @@ rip_status rip_debug_chain_footprint(rip_pipeline* p, int src_rows, int src_cols
 /* Test hook: the narrowing of rip_set_debayer_16bit_range on n values, computed on the host with the launch constants and the
  * arithmetic of the kernel (a multiplication and two shifts instead of the division).  No device, no handle. */
 rip_status rip_debug_raw16_narrow(int black, int white, const uint16_t* in, uint8_t* out, size_t n);
+/* Test hook: unpacks a packed Bayer frame (rip_apply "Packed Bayer frames": the encoding names the layout; rows of `step`
+ * bytes, 0 = tight) into rows x cols uint16 samples, tightly packed, on the host with the extract functions the kernel's byte
+ * path uses.  Width rule and pitch check as for rip_apply.  No device, no handle. */
+rip_status rip_debug_unpack(const char* encoding, const uint8_t* in, size_t step, int rows, int cols, uint16_t* out);
 /* Test hook for the debug dumps: writes image (rows x cols x channels bytes, channels 1 or 3 = BGR) to path as the PNG
  * writer of rip_set_debug does, after the reference's min-max normalisation when normalize != 0.  No device needed;
  * p may be NULL. */

@@ -24,6 +24,7 @@
 
 #include "rip_host.hpp"
 #include "rip_kernels.hpp"
+#include "rip_unpack.hpp"
 
 namespace {
 
@@ -114,6 +115,20 @@ int parse_bayer(const std::string& e, int& ry, int& rx) {
 bool is_bayer16(const std::string& e) {
   return e == "bayer_bggr16" || e == "bayer_gbrg16" || e == "bayer_grbg16" || e == "bayer_rggb16";
 }
+// bayer_<pattern><suffix> of the packed 10- / 12-bit formats (rip.h "Packed Bayer frames"): the R sample's phase and the layout
+// (rip::PackedLayout), or 0
+int parse_packed(const std::string& e, int& ry, int& rx) {
+  static const struct { const char* suffix; int layout; } kSuffixes[] = {
+      {"10p", rip::PACKED_10P}, {"12p", rip::PACKED_12P}, {"10_csi2", rip::PACKED_10_CSI2}, {"12_csi2", rip::PACKED_12_CSI2}};
+  if (e.size() < 13 || e.compare(0, 6, "bayer_") != 0) return 0;
+  const std::string suffix = e.substr(10);
+  for (const auto& k : kSuffixes)
+    if (suffix == k.suffix && parse_bayer(e.substr(0, 10) + "8", ry, rx)) return k.layout;
+  return 0;
+}
+
+struct Plan;
+size_t row_bytes(const Plan& pl, int cols, int channels);
 
 // What one frame geometry/encoding turns into
 struct Plan {
@@ -124,6 +139,9 @@ struct Plan {
   // (black, white) and flipped by one pass of its own (rip_raw16.hip), then the whole chain as for a bgr8 frame
   bool raw16 = false;
   int black = 0, white = 0;
+  // packed 10- / 12-bit frames (rip::PackedLayout; 0: none): a raw16 plan whose rows are unpacked by the kernel's tile staging
+  // (rip_packed.hip), with the handle's range or the format's natural one
+  int packed_layout = 0;
   bool mht = false;       // Bayer input demosaiced by Malvar-He-Cutler (rip_set_debayer_method "mht") instead of bilinear
   int channels = 3;       // channels after the debayer stage
   int flip_angle = 0;     // effective
@@ -134,6 +152,12 @@ struct Plan {
   int stage_bits = 0;
   std::string encoding_out;
 };
+
+// payload bytes of one input row: ceil(cols * B / 8) for a packed format, cols * channels samples otherwise
+size_t row_bytes(const Plan& pl, int cols, int channels) {
+  if (pl.packed_layout) return rip::packed_row_bytes(pl.packed_layout, cols);
+  return (size_t)cols * (size_t)channels * (size_t)pl.in_elem_bytes;
+}
 
 // Host-side copies of whole frames (the deep copies the reference's API promises: process() and every image getter return a
 // clone, raw_image_pipeline.cpp:182-236): a 15 MB memcpy out of the pinned result buffer into freshly allocated pages takes
@@ -815,6 +839,26 @@ Plan make_plan(const rip_pipeline* p, int rows, int cols, int channels, const st
       pl.out_elem_bytes = 2;
       pl.encoding_out = "bgr16";
     }
+  } else if (const int layout = parse_packed(encoding, pl.ry, pl.rx)) {
+    // no reference behaviour to override: accepted whatever rip_set_debayer_16bit says
+    if (channels != 1) throw AssertError("cv::demosaicing: Bayer input must have one channel");
+    if (rows < 3 || cols < 3) throw AssertError("cv::demosaicing: image too small");
+    const int mult = rip::packed_cols_multiple(layout);
+    if (cols % mult != 0)
+      throw InvalidArgument("Encoding [" + encoding + "]: the width must be a multiple of " + std::to_string(mult) + " (whole CSI-2 groups of " +
+                            std::to_string(mult) + " pixels in " + std::to_string(mult * rip::packed_bits(layout) / 8) + " bytes), got " + std::to_string(cols));
+    pl.src_kind = rip::SRC_BAYER;
+    pl.channels = 3;
+    pl.packed_layout = layout;
+    pl.raw16 = true;  // narrowed right after the demosaic, never bgr16
+    if (m.raw16_white > 0) {
+      pl.black = m.raw16_black;
+      pl.white = m.raw16_white;
+    } else {  // the format's natural range
+      pl.black = 0;
+      pl.white = (1 << rip::packed_bits(layout)) - 1;
+    }
+    pl.encoding_out = "bgr8";
   } else if (encoding == "rgb8") {
     if (channels != 3) throw AssertError("cvtColor(RGB2BGR): rgb8 input must have three channels");
     pl.src_kind = rip::SRC_RGB;  // swapped to BGR; the encoding string stays "rgb8" (debayer.cpp:72-73)
@@ -907,13 +951,15 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
     }
     {
       ProfScope ps(p, RIP_KERNEL_CHAIN, p->stream);
-      rip::launch_raw16(d, p->stream);
+      if (pl.packed_layout) rip::launch_packed(d, pl.packed_layout, p->stream);
+      else rip::launch_raw16(d, p->stream);
     }
     hipError_t ler = hipGetLastError();
     if (ler != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(ler));
     Plan s = pl;
     s.raw16 = s.mht = false;
     s.in_elem_bytes = 1;
+    s.packed_layout = 0;
     s.src_kind = rip::SRC_BGR;
     s.ry = s.rx = 0;
     s.flip_angle = 0;
@@ -1616,10 +1662,10 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     if (n_frames < 0) throw InvalidArgument("negative frame count");
     if (n_frames == 0) return;
     Plan pl = make_plan(p, rows, cols, channels, encoding);
-    const size_t ib = (size_t)pl.in_elem_bytes, eb = (size_t)pl.out_elem_bytes;
-    if (in_step == 0) in_step = (size_t)cols * channels * ib;
+    const size_t eb = (size_t)pl.out_elem_bytes, in_row = row_bytes(pl, cols, channels);
+    if (in_step == 0) in_step = in_row;
     if (in_frame_stride == 0) in_frame_stride = in_step * rows;
-    if (in_step < (size_t)cols * channels * ib) throw InvalidArgument("input row pitch smaller than a row");
+    if (in_step < in_row) throw InvalidArgument("input row pitch smaller than a row");
     // bgr16 results (the 16-bit range is off); with a range the frame is an 8-bit one after the demosaic and keeps its taps
     if (eb == 2 && (d_tap_debayered || d_tap_color)) throw InvalidArgument("16-bit Bayer frames have no taps");
     // several kernels put the frame index on gridDim.y (<= 65535): longer batches go through in slices.  The
@@ -1631,7 +1677,7 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     // express (and pitches that would make rows or frames overlap) instead of writing somewhere else
     if (o_step < (size_t)pl.out_cols * pl.channels * eb) throw InvalidArgument("output row pitch smaller than a row");
     if (o_stride < o_step * (size_t)pl.out_rows) throw InvalidArgument("output frame stride smaller than a frame");
-    if (in_frame_stride < in_step * (size_t)(rows - 1) + (size_t)cols * channels * ib) throw InvalidArgument("input frame stride smaller than a frame");
+    if (in_frame_stride < in_step * (size_t)(rows - 1) + in_row) throw InvalidArgument("input frame stride smaller than a frame");
     if (in_step >= (1u << 24) || o_step >= (1u << 24) || (unsigned long long)in_step * rows >= (1ull << 32) ||
         (unsigned long long)o_step * pl.out_rows >= (1ull << 32))
       throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
@@ -1654,9 +1700,10 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     if (!image || !out || !encoding) throw InvalidArgument("null buffer or encoding");
     Plan pl = make_plan(p, rows, cols, channels, encoding);
     DeviceGuard device_guard(p->device);
-    const size_t ib = (size_t)pl.in_elem_bytes, eb = (size_t)pl.out_elem_bytes;
-    if (step == 0) step = (size_t)cols * channels * ib;
-    const size_t in_pitch = ((size_t)cols * channels * ib + 3) & ~(size_t)3;  // dword-aligned rows on the device
+    const size_t eb = (size_t)pl.out_elem_bytes, in_row = row_bytes(pl, cols, channels);
+    if (step == 0) step = in_row;
+    if (pl.packed_layout && step < in_row) throw InvalidArgument("input row pitch smaller than a row");
+    const size_t in_pitch = (in_row + 3) & ~(size_t)3;  // dword-aligned rows on the device
     const size_t in_bytes = in_pitch * rows;
     const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb;
     const size_t mid_bytes = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
@@ -1673,7 +1720,7 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
       p->d_tap_col.reserve(mid_bytes);
       tap_col = p->d_tap_col.as<uint8_t>();
     }
-    HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, in_pitch, image, step, (size_t)cols * channels * ib, (size_t)rows, hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, in_pitch, image, step, in_row, (size_t)rows, hipMemcpyHostToDevice, p->stream));
     run_batch(p, pl, p->d_in.as<uint8_t>(), in_pitch, in_bytes, 1, rows, cols, p->d_out.as<uint8_t>(), 0, 0, tap_deb, tap_col);
     HIP_CHECK(hipMemcpyAsync(out, p->d_out.ptr, out_bytes, hipMemcpyDeviceToHost, p->stream));
     HIP_CHECK(hipStreamSynchronize(p->stream));
@@ -1759,9 +1806,10 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
       for (int i = 0; i < 3; i++)
         if (p->last_buf[i] == &sl.d_tap_deb || p->last_buf[i] == &sl.d_tap_col || p->last_buf[i] == &sl.d_out) p->last_valid[i] = false;
     }
-    const size_t ib = (size_t)pl.in_elem_bytes, eb = (size_t)pl.out_elem_bytes;
-    if (step == 0) step = (size_t)cols * channels * ib;
-    const size_t in_pitch = ((size_t)cols * channels * ib + 3) & ~(size_t)3;  // dword-aligned rows on the device
+    const size_t eb = (size_t)pl.out_elem_bytes, in_row = row_bytes(pl, cols, channels);
+    if (step == 0) step = in_row;
+    if (pl.packed_layout && step < in_row) throw InvalidArgument("input row pitch smaller than a row");
+    const size_t in_pitch = (in_row + 3) & ~(size_t)3;  // dword-aligned rows on the device
     const size_t in_bytes = in_pitch * rows;
     const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb;
     const size_t mid_bytes = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
@@ -1785,7 +1833,7 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     // untouched until its ticket is collected.  Anything else is copied into the slot's pinned staging buffer first, so the
     // caller's buffer is free again when this call returns whatever the runtime does with an asynchronous 2-D copy from
     // pageable memory (above its staging threshold it pins the pages in place and copies after the call has returned).
-    const size_t row_bytes = (size_t)cols * channels * ib;
+    const size_t row_bytes = in_row;
     inflight_gate().forget(sl.gate_device, sl.ev_done);  // the slot's previous frame (collected, or it would not have been picked)
     inflight_gate().admit(p->device);
     if (sl.ev_start) HIP_CHECK(hipEventRecord(sl.ev_start, p->ul_stream));
@@ -2182,6 +2230,32 @@ rip_status rip_debug_raw16_narrow(int black, int white, const uint16_t* in, uint
       const int t = std::min(std::max((int)in[i] - black, 0), range);
       const uint32_t num = (uint32_t)t * 510u + (uint32_t)range;
       out[i] = (uint8_t)((uint32_t)(((uint64_t)(num << 6) * mul) >> 32) >> shift);
+    }
+  });
+}
+
+rip_status rip_debug_unpack(const char* encoding, const uint8_t* in, size_t step, int rows, int cols, uint16_t* out) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    int ry, rx;
+    const int layout = encoding ? parse_packed(encoding, ry, rx) : 0;
+    if (!layout) throw InvalidArgument("rip_debug_unpack: not a packed Bayer encoding");
+    if (rows < 0 || cols < 0 || (rows && cols && (!in || !out))) throw InvalidArgument("rip_debug_unpack: buffers are needed");
+    const int mult = rip::packed_cols_multiple(layout);
+    if (cols % mult != 0) throw InvalidArgument("rip_debug_unpack: the width must be a multiple of " + std::to_string(mult));
+    const size_t in_row = rip::packed_row_bytes(layout, cols);
+    if (step == 0) step = in_row;
+    if (step < in_row) throw InvalidArgument("input row pitch smaller than a row");
+    for (int y = 0; y < rows; y++) {
+      const uint8_t* row = in + (size_t)y * step;
+      uint16_t* o = out + (size_t)y * cols;
+      for (int x = 0; x < cols; x++) {  // StagePacked::sample of rip_raw16_dev.hpp: the same functions of rip_unpack.hpp
+        switch (layout) {
+          case rip::PACKED_10P: o[x] = (uint16_t)rip::unpack_sample<rip::PACKED_10P>(row, x); break;
+          case rip::PACKED_12P: o[x] = (uint16_t)rip::unpack_sample<rip::PACKED_12P>(row, x); break;
+          case rip::PACKED_10_CSI2: o[x] = (uint16_t)rip::unpack_sample<rip::PACKED_10_CSI2>(row, x); break;
+          default: o[x] = (uint16_t)rip::unpack_sample<rip::PACKED_12_CSI2>(row, x); break;
+        }
+      }
     }
   });
 }

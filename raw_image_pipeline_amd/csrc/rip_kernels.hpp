@@ -313,6 +313,8 @@ bool launch_remap_fused_fc1(const RemapTiledParams& p, const ChainParams& c, int
 void launch_debayer16(const Debayer16Params& p, hipStream_t stream);
 void launch_demosaic_mht(const MhtParams& p, hipStream_t stream);
 void launch_raw16(const Raw16Params& p, hipStream_t stream);
+// rip_packed.hip: the same pass on packed 10- / 12-bit rows (layout: PackedLayout of rip_unpack.hpp; src_step in bytes)
+void launch_packed(const Raw16Params& p, int layout, hipStream_t stream);
 // the launch constants of the narrowing n(v) = min(255, floor((510 * max(v - black, 0) + R) / (2 R))), R = white - black: a
 // multiplier and a shift that replace the division exactly for every numerator below 2^26 (host code; the tests check it)
 void raw16_narrow_constants(int black, int white, uint32_t* mul, int* shift);

@@ -157,19 +157,21 @@ class CameraStream:
             self.pipe.set_tap_download(mask)  # every kept tap is published: let it travel with the result of a submit()
             self._tap_mask = mask
 
-    def on_image(self, image, encoding, stamp=0.0, frame_id="camera"):
+    def on_image(self, image, encoding, stamp=0.0, frame_id="camera", width=None):
         """Processes one frame and returns the messages the node would publish, in publishing order:
-        a list of dicts {topic, image, encoding, camera_info | None}."""
+        a list of dicts {topic, image, encoding, camera_info | None}.  ``width``: pixels per row of a packed Bayer frame
+        (bayer_*10p / 12p / 10_csi2 / 12_csi2: a 2-D uint8 array [rows, row bytes]; ``RawImagePipeline.process``).  The
+        debayer/black_level and debayer/white_level parameters apply to such frames as they do to 16-bit ones."""
         img = np.asarray(image)
         if img.size == 0:
             return []  # ROS_WARN("image empty")
         if self.transport != "raw":
             encoding = "bgr8"  # cv_bridge::toCvCopy(image_msg, "bgr8") for compressed transports
         self._sync_taps()
-        processed = self.pipe.apply(img.copy(), encoding)
+        processed = self.pipe.apply(img.copy(), encoding, **({} if width is None else {"width": width}))
         return self._messages(processed, self.pipe.last_encoding, stamp, frame_id)
 
-    def submit(self, image, encoding, stamp=0.0, frame_id="camera"):
+    def submit(self, image, encoding, stamp=0.0, frame_id="camera", width=None):
         """First half of the callback: enqueues upload, kernels and the download of the result AND of the taps the node
         publishes (rip_submit) and returns at once.  The frame is read before the call returns.  False for an empty image."""
         img = np.ascontiguousarray(image)
@@ -181,8 +183,7 @@ class CameraStream:
         dst = {}
         if self._pinned_pool is not None:
             from .pipeline import TAP_COLOR, TAP_DEBAYERED
-            rows, cols = img.shape[:2]
-            cn = 1 if img.ndim == 2 else img.shape[2]
+            rows, cols, cn = self.pipe._packed_geometry(img, encoding, width) if self.transport == "raw" else (img.shape[0], img.shape[1], 1 if img.ndim == 2 else img.shape[2])
             r, c, k, enc_out = self.pipe.query_output(rows, cols, cn, encoding)
             if not enc_out.endswith("16"):  # bgr16 results (bayer_*16 without a range) have no taps and no pool arrays
                 dst["out"] = self._pinned_pool.take((r, c) if k == 1 else (r, c, k), or_none=True)
@@ -191,6 +192,8 @@ class CameraStream:
                     dst["tap_debayered"] = self._pinned_pool.take((tr, tc) if tk == 1 else (tr, tc, tk), or_none=True)
                 if self._tap_mask & TAP_COLOR:
                     dst["tap_color"] = self._pinned_pool.take((tr, tc) if tk == 1 else (tr, tc, tk), or_none=True)
+        if width is not None:
+            dst["width"] = width
         ticket = self.pipe.submit(img, encoding, **{key: arr for key, arr in dst.items() if arr is not None})
         self._inflight = getattr(self, "_inflight", [])
         self._inflight.append((ticket, stamp, frame_id))
@@ -207,13 +210,13 @@ class CameraStream:
         processed = self.pipe.collect(ticket, copy=copy)
         return self._messages(processed, self.pipe.last_encoding, stamp, frame_id, copy=copy)
 
-    def on_image_pipelined(self, image, encoding, stamp=0.0, frame_id="camera", copy=True):
+    def on_image_pipelined(self, image, encoding, stamp=0.0, frame_id="camera", copy=True, width=None):
         """The same callback with one frame kept in flight (rip_submit / rip_collect): uploads, kernels and downloads of
         neighbouring frames overlap, and the call returns the messages of the PREVIOUS frame (an empty list for the first
         one; flush() delivers the last).  Frames are processed in arrival order, so the white-balance filter sees the
         same sequence as with on_image()."""
         had = len(getattr(self, "_inflight", []))
-        if not self.submit(image, encoding, stamp, frame_id):
+        if not self.submit(image, encoding, stamp, frame_id, width=width):
             return []
         return self.collect(copy=copy) if had else []
 

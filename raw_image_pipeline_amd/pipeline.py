@@ -20,6 +20,23 @@ TAP_DEBAYERED, TAP_COLOR, TAP_PROCESSED = 1, 2, 4
 IMAGE_DEBAYERED, IMAGE_COLOR, IMAGE_PROCESSED, IMAGE_RECT_MASK = 0, 1, 2, 3
 
 
+PACKED_SUFFIXES = {"10p": 10, "12p": 12, "10_csi2": 10, "12_csi2": 12}
+
+
+def packed_bits(encoding):
+    """Bits per sample of a packed Bayer encoding (bayer_<pattern>{10p,12p,10_csi2,12_csi2}, include/rip.h "Packed Bayer
+    frames"), 0 for every other name."""
+    if encoding.startswith("bayer_") and encoding[6:10] in ("rggb", "bggr", "gbrg", "grbg"):
+        return PACKED_SUFFIXES.get(encoding[10:], 0)
+    return 0
+
+
+def packed_width(row_bytes, bits):
+    """The pixels a tight packed row of ``row_bytes`` bytes holds: exact for tight rows of every width (the last byte of a
+    row holds fewer than ``bits`` bits of padding); pitched rows need the width spelled out."""
+    return 8 * int(row_bytes) // bits
+
+
 class RipError(RuntimeError):
     """HIP/device failure (RIP_ERR_DEVICE, RIP_ERR_CAPACITY)."""
 
@@ -213,8 +230,26 @@ class RawImagePipeline:
         self._call("rip_query_taps", int(rows), int(cols), int(channels), encoding.encode(), C.byref(tr), C.byref(tc), C.byref(tcn))
         return tr.value, tc.value, tcn.value
 
-    def process(self, image, encoding):
-        """cv::Mat process(const cv::Mat&, std::string&): returns a new array; input untouched."""
+    @staticmethod
+    def _packed_geometry(img, encoding, width):
+        """(rows, cols, channels) of a host frame: for the packed Bayer encodings a 2-D uint8 array [rows, row bytes] whose
+        pixel count per row is ``width`` (default: what a tight row of that many bytes holds)."""
+        bits = packed_bits(encoding)
+        if not bits:
+            if width is not None:
+                raise ValueError("width is for the packed Bayer encodings only")
+            return img.shape[0], img.shape[1], 1 if img.ndim == 2 else img.shape[2]
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise ValueError("a %s frame is a 2-D uint8 array [rows, row bytes]" % encoding)
+        cols = packed_width(img.shape[1], bits) if width is None else int(width)
+        if (cols * bits + 7) // 8 > img.shape[1]:
+            raise ValueError("rows of %d bytes do not hold %d pixels of %d bits" % (img.shape[1], cols, bits))
+        return img.shape[0], cols, 1
+
+    def process(self, image, encoding, width=None):
+        """cv::Mat process(const cv::Mat&, std::string&): returns a new array; input untouched.  Packed Bayer encodings
+        (bayer_*10p / 12p / 10_csi2 / 12_csi2): ``image`` is the 2-D uint8 array [rows, row bytes], ``width`` the pixels per row
+        (default ``8 * row_bytes // bits``: exact for tight rows; pass it for pitched ones)."""
         img = np.asarray(image)
         # 16-bit Bayer extension (set_debayer_16bit): uint16 in; uint16 BGR out, or -- with a 16-bit range
         # (set_debayer_16bit_range) -- the whole pipeline and uint8 bgr8 out
@@ -223,8 +258,7 @@ class RawImagePipeline:
             raise ValueError("image must be uint8 (or uint16 Bayer), HxW or HxWxC")
         if img.strides[-1] != img.itemsize or (img.ndim == 3 and img.strides[1] != img.shape[2] * img.itemsize):
             img = np.ascontiguousarray(img)
-        rows, cols = img.shape[:2]
-        cn = 1 if img.ndim == 2 else img.shape[2]
+        rows, cols, cn = self._packed_geometry(img, encoding, width)
         orows, ocols, ocn, oenc = self.query_output(rows, cols, cn, encoding)
         if wide != encoding.endswith("16"):
             raise ValueError("dtype %s does not match encoding %s" % (img.dtype, encoding))
@@ -241,29 +275,28 @@ class RawImagePipeline:
         shape = (r.value, c.value) if k.value == 1 else (r.value, c.value, k.value)
         return out if out.shape == shape else out.reshape(shape)
 
-    def apply(self, image, encoding):
+    def apply(self, image, encoding, width=None):
         """bool apply(cv::Mat&, std::string&): returns the processed image; when it has the input's
         shape the input array is overwritten too (the reference re-seats the caller's Mat)."""
-        out = self.process(image, encoding)
+        out = self.process(image, encoding, width)
         if isinstance(image, np.ndarray) and image.shape == out.shape and image.flags.writeable:
             image[...] = out
         return out
 
     # ---- asynchronous host frames (rip_submit / rip_collect; no counterpart in the reference's binding) -------------
-    def submit(self, image, encoding, out=None, tap_debayered=None, tap_color=None):
+    def submit(self, image, encoding, out=None, tap_debayered=None, tap_color=None, width=None):
         """Enqueues upload + chain + download of one host frame and returns its ticket without waiting (rip_submit).  Up to
         ``set_ring_depth`` (default 3) frames may be in flight; frames are processed in submission order.
 
         ``out`` / ``tap_debayered`` / ``tap_color``: page-locked arrays (``host_alloc``, a pinned ``OutputPool``) of the
         result's / the taps' shape -- the downloads are written straight into them (rip_submit_to) and ``collect`` / the image
-        getters return these very arrays: deep-copy semantics without a copy."""
+        getters return these very arrays: deep-copy semantics without a copy.  ``width``: as for ``process``."""
         img = np.asarray(image)
         if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3):
             raise ValueError("image must be uint8 (or uint16 Bayer), HxW or HxWxC")
         if img.strides[-1] != img.itemsize or (img.ndim == 3 and img.strides[1] != img.shape[2] * img.itemsize):
             img = np.ascontiguousarray(img)
-        rows, cols = img.shape[:2]
-        cn = 1 if img.ndim == 2 else img.shape[2]
+        rows, cols, cn = self._packed_geometry(img, encoding, width)
         if (img.dtype == np.uint16) != encoding.endswith("16"):
             raise ValueError("dtype %s does not match encoding %s" % (img.dtype, encoding))
         t = C.c_uint64()
@@ -312,19 +345,33 @@ class RawImagePipeline:
     def set_ring_depth(self, depth):
         self._call("rip_set_ring_depth", int(depth))
 
-    def apply_device(self, frames, encoding, out=None, tap_debayered=None, tap_color=None):
+    def apply_device(self, frames, encoding, out=None, tap_debayered=None, tap_color=None, width=None):
         """Device-resident batch (rip_apply_device).  ``frames``: uint8 CUDA tensor [n, rows, cols]
         or [n, rows, cols, c] (torch) already in HBM; returns the output tensor [n, R, C(, 3)].
         Asynchronous on the handle's stream.
 
         bayer_*16 frames (``set_debayer_16bit``): the uint8 view [n, rows, cols * 2] of the uint16 rows, pitches in bytes.
         With a 16-bit range (``set_debayer_16bit_range``) the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be
-        given; without one it is bgr16 as bytes, [n, R, C, 6]."""
+        given; without one it is bgr16 as bytes, [n, R, C, 6].
+
+        Packed Bayer encodings: [n, rows, row bytes] uint8 tensors, ``width`` pixels per row (default
+        ``8 * row_bytes // bits``); the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be given."""
         import torch
         if frames.dtype != torch.uint8 or not frames.is_cuda:
             raise ValueError("frames must be a uint8 CUDA tensor")
         wide = encoding.endswith("16")
-        if wide:
+        bits = packed_bits(encoding)
+        if width is not None and not bits:
+            raise ValueError("width is for the packed Bayer encodings only")
+        if bits:
+            if frames.dim() != 3:
+                raise ValueError("packed frames must be [n, rows, row bytes]")
+            n, rows = frames.shape[0], frames.shape[1]
+            cols = packed_width(frames.shape[2], bits) if width is None else int(width)
+            if (cols * bits + 7) // 8 > frames.shape[2]:
+                raise ValueError("rows of %d bytes do not hold %d pixels of %d bits" % (frames.shape[2], cols, bits))
+            cn = 1
+        elif wide:
             if frames.dim() != 3 or frames.shape[2] % 2:
                 raise ValueError("16-bit frames must be the uint8 view [n, rows, cols * 2] of uint16 rows")
             n, rows, cols = frames.shape[0], frames.shape[1], frames.shape[2] // 2
