@@ -4,7 +4,7 @@ construct the pipeline from three YAML files, print the calibration it holds, ru
 copy) and apply() (re-seats the input) on a colour image, and write both results as PNG when Pillow is
 available (the reference uses cv2 / rospkg and its bundled alphasense.png, which are not shipped here).
 
-usage: python examples/apply_pipeline.py [--device 0] [--out-dir .]
+usage: python examples/apply_pipeline.py [--device 0] [--out-dir .] [--model equidistant|plumb_bob|rational_polynomial]
 """
 import argparse
 import os
@@ -18,10 +18,17 @@ import numpy as np  # noqa: E402
 
 from raw_image_pipeline_amd import RawImagePipeline, synth  # noqa: E402
 
+# example coefficients of the pinhole models (k1 k2 p1 p2 k3 [k4 k5 k6])
+PINHOLE_EXAMPLES = {"plumb_bob": [-0.28, 0.07, 2e-4, -3e-4, 0.0],
+                    "rational_polynomial": [0.9, 0.25, 3e-4, -2e-4, 0.01, 1.25, 0.55, 0.05]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out-dir", default=".")
+    ap.add_argument("--model", default="equidistant", choices=sorted(PINHOLE_EXAMPLES) + ["equidistant"],
+                    help="distortion model of the synthetic calibration (the pinhole models report 5 / 8 coefficients)")
     args = ap.parse_args()
 
     w, h = 720, 540  # the size of the reference's example calibration
@@ -31,7 +38,10 @@ def main():
     color_calib_file = os.path.join(tmp, "color_calib.yaml")
     param_file = os.path.join(tmp, "params.yaml")
     with open(calib_file, "w") as f:
-        f.write(synth.calibration_yaml(synth.camera_model(w, h)))
+        if args.model in PINHOLE_EXAMPLES:
+            f.write(synth.calibration_yaml(synth.pinhole_camera_model(w, h, PINHOLE_EXAMPLES[args.model]), args.model))
+        else:
+            f.write(synth.calibration_yaml(synth.camera_model(w, h)))
     with open(color_calib_file, "w") as f:
         f.write("matrix:\n  rows: 3\n  cols: 3\n  data: %s\nbias:\n  rows: 3\n  cols: 1\n  data: [0.0, 0.0, 0.0]\n" % synth.COLOR_MATRIX)
     with open(param_file, "w") as f:

@@ -284,7 +284,8 @@ class RawImagePipeline {
   int getDistImageWidth() const { return rip_get_dist_image_width(h_); }
   std::string getDistDistortionModel() const { return str(&rip_get_dist_distortion_model); }
   Mat getDistCameraMatrix() const { return matrix(&rip_get_dist_camera_matrix, 3, 3); }
-  Mat getDistDistortionCoefficients() const { return matrix(&rip_get_dist_distortion_coefficients, 1, 4); }
+  // 1 x n: n = 5 for plumb_bob and radtan, 8 for rational_polynomial, 4 for every other model (rip.h)
+  Mat getDistDistortionCoefficients() const { return coefficients(0); }
   Mat getDistRectificationMatrix() const { return matrix(&rip_get_dist_rectification_matrix, 3, 3); }
   Mat getDistProjectionMatrix() const { return matrix(&rip_get_dist_projection_matrix, 3, 4); }
 
@@ -292,7 +293,7 @@ class RawImagePipeline {
   int getRectImageWidth() const { return rip_get_rect_image_width(h_); }
   std::string getRectDistortionModel() const { return str(&rip_get_rect_distortion_model); }
   Mat getRectCameraMatrix() const { return matrix(&rip_get_rect_camera_matrix, 3, 3); }
-  Mat getRectDistortionCoefficients() const { return matrix(&rip_get_rect_distortion_coefficients, 1, 4); }
+  Mat getRectDistortionCoefficients() const { return coefficients(1); }
   Mat getRectRectificationMatrix() const { return matrix(&rip_get_rect_rectification_matrix, 3, 3); }
   Mat getRectProjectionMatrix() const { return matrix(&rip_get_rect_projection_matrix, 3, 4); }
 
@@ -376,6 +377,14 @@ class RawImagePipeline {
   Mat matrix(rip_status (*fn)(const rip_pipeline*, double*), int rows, int cols) const {
     Mat m = detail::make_f64(rows, cols);
     check(fn(h_, detail::doubles(m)));
+    return m;
+  }
+  Mat coefficients(int rect) const {
+    int n = 0;
+    double d[8] = {0};
+    check(rip_get_distortion_coefficients_n(h_, rect, d, 8, &n));
+    Mat m = detail::make_f64(1, n);
+    for (int i = 0; i < n; i++) detail::doubles(m)[i] = d[i];
     return m;
   }
   std::string str(rip_status (*fn)(const rip_pipeline*, char*, size_t)) const {

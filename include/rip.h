@@ -302,7 +302,19 @@ rip_status rip_set_undistortion_new_image_size(rip_pipeline* p, int width, int h
 rip_status rip_set_undistortion_balance(rip_pipeline* p, double balance);         /* hpp:98 */
 rip_status rip_set_undistortion_fov_scale(rip_pipeline* p, double fov_scale);     /* hpp:99 */
 rip_status rip_set_undistortion_camera_matrix(rip_pipeline* p, const double* k, int n);            /* hpp:100, n >= 9 */
+/* n >= 4; the first min(n, 8) values are kept and the rest taken as 0.  What they mean is the model's business (below). */
 rip_status rip_set_undistortion_distortion_coefficients(rip_pipeline* p, const double* d, int n);  /* hpp:101, n >= 4 */
+/* Distortion models.  "none": no remap.  "plumb_bob", "radtan", "rational_polynomial": the pinhole (Brown-Conrady) models of
+ * ROS camera_calibration / Kalibr -- the new camera matrix follows cv::getOptimalNewCameraMatrix (alpha = balance clamped to
+ * [0, 1]: 0 crops to valid pixels, 1 keeps every source pixel) and the maps cv::initUndistortRectifyMap, both restated in
+ * double (PARITY.md "Pinhole distortion models"; not pinned against an OpenCV binary):
+ *   plumb_bob            D = k1 k2 p1 p2 k3              (5 coefficients reported; k4..k6 taken as 0)
+ *   radtan               D = k1 k2 p1 p2, k3 = 0         (5 coefficients reported)
+ *   rational_polynomial  D = k1 k2 p1 p2 k3 k4 k5 k6     (8 coefficients reported)
+ * Missing trailing coefficients are 0; thin-prism and tilt terms are not supported (the calibration loader refuses a
+ * distortion_coefficients list whose values beyond the eighth are not all zero with RIP_ERR_INVALID_ARGUMENT).
+ * Every other name -- "equidistant" among them -- builds fisheye (Kannala-Brandt, cv::fisheye) maps from the first four
+ * coefficients, as the reference does for any model string. */
 rip_status rip_set_undistortion_distortion_model(rip_pipeline* p, const char* model);              /* hpp:102 */
 rip_status rip_set_undistortion_rectification_matrix(rip_pipeline* p, const double* r, int n);     /* hpp:103, n >= 9 */
 rip_status rip_set_undistortion_projection_matrix(rip_pipeline* p, const double* pm, int n);       /* hpp:104, n >= 12 */
@@ -335,6 +347,12 @@ rip_status rip_get_rect_camera_matrix(const rip_pipeline* p, double out[9]);    
 rip_status rip_get_rect_distortion_coefficients(const rip_pipeline* p, double out[4]);/* hpp:130 */
 rip_status rip_get_rect_rectification_matrix(const rip_pipeline* p, double out[9]);   /* hpp:131 */
 rip_status rip_get_rect_projection_matrix(const rip_pipeline* p, double out[12]);     /* hpp:132 */
+/* Not in the reference: the distortion coefficients in the length the model reports -- *n = 5 for plumb_bob and radtan, 8 for
+ * rational_polynomial, 4 for every other model (what the two 4-value getters above return, unchanged).  rect = 0: the
+ * coefficients of the distorted camera as the model evaluates them (radtan: k3 = 0); rect = 1: those of the rectified
+ * image, n zeros once the undistortion has been initialised.  out = NULL just queries n; RIP_ERR_CAPACITY when
+ * capacity < n. */
+rip_status rip_get_distortion_coefficients_n(const rip_pipeline* p, int rect, double* out, int capacity, int* n);
 
 /* ---- introspection used by tests / bench (no reference counterpart) --------------------------- */
 /* Host copy of the undistortion maps (float32, map_rows x map_cols each); NULL pointers

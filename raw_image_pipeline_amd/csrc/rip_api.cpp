@@ -472,10 +472,17 @@ struct ProfScope {
 void und_init(rip_pipeline* p) {
   rip::Modules& m = p->m;
   double newK[9];
-  rip::fisheye_estimate_new_camera_matrix(m.dist_K, m.dist_D, m.dist_w, m.dist_h, m.dist_R, m.balance, m.rect_w, m.rect_h,
-                                          m.fov_scale, newK);
+  if (rip::is_pinhole_model(m.dist_model)) {
+    // plumb_bob / radtan / rational_polynomial: cv::getOptimalNewCameraMatrix with alpha = balance (not in the reference)
+    double k[8];
+    rip::pinhole_coefficients(m.dist_model, m.dist_D, k);
+    rip::pinhole_estimate_new_camera_matrix(m.dist_K, k, m.dist_w, m.dist_h, m.balance, m.rect_w, m.rect_h, m.fov_scale, newK);
+  } else {
+    rip::fisheye_estimate_new_camera_matrix(m.dist_K, m.dist_D, m.dist_w, m.dist_h, m.dist_R, m.balance, m.rect_w, m.rect_h,
+                                            m.fov_scale, newK);
+  }
   std::memcpy(m.rect_K, newK, sizeof(newK));
-  for (int i = 0; i < 4; i++) m.rect_D[i] = 0;
+  for (int i = 0; i < 8; i++) m.rect_D[i] = 0;
   const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   std::memcpy(m.rect_R, eye, sizeof(eye));
   for (int i = 0; i < 3; i++)
@@ -495,19 +502,24 @@ void ensure_host_maps(rip_pipeline* p) {
   const size_t n = (size_t)m.dist_w * m.dist_h * 2;
   p->h_map.resize(n);
   // maps have the *dist* image size even after setNewImageSize (undistortion.cpp:216)
+  const bool pinhole = rip::is_pinhole_model(m.dist_model);  // every other name builds fisheye maps, as the reference does
   if (maps_on_device(p)) {
     DeviceGuard device_guard(p->device);
-    rip::FisheyeMapParams fp = {};
+    rip::UndistortMapParams fp = {};
     std::memcpy(fp.K, m.dist_K, sizeof(fp.K));
-    std::memcpy(fp.D, m.dist_D, sizeof(fp.D));
+    fp.pinhole = pinhole ? 1 : 0;
+    if (pinhole)
+      rip::pinhole_coefficients(m.dist_model, m.dist_D, fp.D);
+    else
+      std::memcpy(fp.D, m.dist_D, 4 * sizeof(double));
     rip::fisheye_inverse_PR(m.rect_K, m.dist_R, fp.iR);
     fp.w = m.dist_w;
     fp.h = m.dist_h;
     p->d_map.reserve(n * sizeof(float));
     fp.map_xy = p->d_map.as<float>();
-    p->d_map_ckpt.reserve(rip::fisheye_ckpt_bytes(fp.w, fp.h));
+    p->d_map_ckpt.reserve(rip::undistort_ckpt_bytes(fp.w, fp.h));
     fp.ckpt = p->d_map_ckpt.as<double>();
-    rip::launch_fisheye_maps(fp, p->stream);
+    rip::launch_undistort_maps(fp, p->stream);
     // no host copy yet: the remap-plan compiler runs on the device too; need_host_map() fetches the floats for
     // rip_get_undistortion_maps or for a plan compiled on the host
     p->map_dirty = false;
@@ -516,7 +528,13 @@ void ensure_host_maps(rip_pipeline* p) {
     p->plan.valid = false;
     return;
   }
-  rip::fisheye_init_undistort_rectify_map(m.dist_K, m.dist_D, m.dist_R, m.rect_K, m.dist_w, m.dist_h, p->h_map.data());
+  if (pinhole) {
+    double k[8];
+    rip::pinhole_coefficients(m.dist_model, m.dist_D, k);
+    rip::pinhole_init_undistort_rectify_map(m.dist_K, k, m.dist_R, m.rect_K, m.dist_w, m.dist_h, p->h_map.data());
+  } else {
+    rip::fisheye_init_undistort_rectify_map(m.dist_K, m.dist_D, m.dist_R, m.rect_K, m.dist_w, m.dist_h, p->h_map.data());
+  }
   p->map_dirty = false;
   p->map_uploaded = false;
   p->h_map_valid = true;
@@ -2179,7 +2197,7 @@ RIP_SETTER(rip_set_undistortion_camera_matrix, (rip_pipeline * p, const double* 
            for (int i = 0; i < 9; i++) p->m.dist_K[i] = p->m.rect_K[i] = v[i]; und_init(p))
 RIP_SETTER(rip_set_undistortion_distortion_coefficients, (rip_pipeline * p, const double* v, int n),
            if (!v || n < 4) throw InvalidArgument("distortion coefficients need 4 values");
-           for (int i = 0; i < 4; i++) p->m.dist_D[i] = p->m.rect_D[i] = v[i]; und_init(p))
+           for (int i = 0; i < 8; i++) p->m.dist_D[i] = p->m.rect_D[i] = i < n ? v[i] : 0.0; und_init(p))
 RIP_SETTER(rip_set_undistortion_distortion_model, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            p->m.dist_model = p->m.rect_model = s; und_init(p))
 RIP_SETTER(rip_set_undistortion_rectification_matrix, (rip_pipeline * p, const double* v, int n),
@@ -2294,6 +2312,27 @@ RIP_GET_VEC(rip_get_rect_camera_matrix, rect_K, 9)
 RIP_GET_VEC(rip_get_rect_distortion_coefficients, rect_D, 4)
 RIP_GET_VEC(rip_get_rect_rectification_matrix, rect_R, 9)
 RIP_GET_VEC(rip_get_rect_projection_matrix, rect_P, 12)
+
+rip_status rip_get_distortion_coefficients_n(const rip_pipeline* p, int rect, double* out, int capacity, int* n) {
+  return guarded(p, [&] {
+    need(p);
+    if (rect != 0 && rect != 1) throw InvalidArgument("rect must be 0 (dist) or 1 (rect)");
+    const rip::Modules& m = p->m;
+    const int count = rip::distortion_coefficient_count(rect ? m.rect_model : m.dist_model);
+    if (n) *n = count;
+    if (!out) return;  // the count alone
+    if (capacity < count) throw CapacityError("coefficient buffer too small");
+    if (rect) {
+      for (int i = 0; i < count; i++) out[i] = m.rect_D[i];
+    } else if (rip::is_pinhole_model(m.dist_model)) {
+      double k[8];
+      rip::pinhole_coefficients(m.dist_model, m.dist_D, k);  // what the model evaluates: radtan reports k3 = 0
+      for (int i = 0; i < count; i++) out[i] = k[i];
+    } else {
+      for (int i = 0; i < count; i++) out[i] = m.dist_D[i];
+    }
+  });
+}
 
 // ---- introspection -------------------------------------------------------------------------------
 rip_status rip_get_undistortion_maps(rip_pipeline* p, float* map_x, float* map_y, size_t cap, int* rows, int* cols) {

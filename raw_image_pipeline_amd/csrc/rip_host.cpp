@@ -338,8 +338,14 @@ void set_camera(Modules& m, int w, int h, const std::vector<double>& K, const st
   m.dist_h = m.rect_h = h;
   if (K.size() < 9 || D.size() < 4 || R.size() < 9 || P.size() < 12)
     throw YamlError("camera calibration: camera_matrix needs 9, distortion_coefficients 4, rectification_matrix 9 and projection_matrix 12 values");
+  // ROS's 12 / 14-value vectors (thin-prism s1..s4, tilt tauX tauY) load as long as those terms are zero
+  for (size_t i = 8; i < D.size(); i++)
+    if (D[i] != 0)
+      throw std::invalid_argument("camera calibration: distortion_coefficients has " + std::to_string(D.size()) +
+                                  " values with a non-zero thin-prism / tilt term (value " + std::to_string(i + 1) +
+                                  "); only k1 k2 p1 p2 k3 k4 k5 k6 are supported");
   for (int i = 0; i < 9; i++) m.dist_K[i] = m.rect_K[i] = K[i];
-  for (int i = 0; i < 4; i++) m.dist_D[i] = m.rect_D[i] = D[i];
+  for (int i = 0; i < 8; i++) m.dist_D[i] = m.rect_D[i] = i < (int)D.size() ? D[i] : 0.0;
   m.dist_model = m.rect_model = model;
   for (int i = 0; i < 9; i++) m.dist_R[i] = m.rect_R[i] = R[i];
   for (int i = 0; i < 12; i++) m.dist_P[i] = m.rect_P[i] = P[i];
@@ -711,6 +717,25 @@ void fisheye_inverse_PR(const double P[9], const double R[9], double iR_out[9]) 
   for (int i = 0; i < 9; i++) iR_out[i] = iR.v[i];
 }
 
+namespace {
+// rows [0, h) of a w x h map on up to 16 threads; small maps on the caller's
+template <typename RowsFn>
+void for_map_rows(int w, int h, const RowsFn& rows_fn) {
+  int nthreads = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u);
+  if ((size_t)w * h < (1u << 18) || nthreads == 1) {
+    rows_fn(0, h);
+    return;
+  }
+  std::vector<std::thread> pool;
+  int chunk = (h + nthreads - 1) / nthreads;
+  for (int t = 0; t < nthreads; t++) {
+    int r0 = t * chunk, r1 = std::min(h, r0 + chunk);
+    if (r0 < r1) pool.emplace_back(rows_fn, r0, r1);
+  }
+  for (auto& th : pool) th.join();
+}
+}  // namespace
+
 void fisheye_init_undistort_rectify_map(const double K[9], const double D[4], const double R[9],
                                         const double P[9], int w, int h, float* map_xy) {
   Mat3 iR = inverse3(mul3(P, R));
@@ -734,18 +759,102 @@ void fisheye_init_undistort_rectify_map(const double K[9], const double D[4], co
       }
     }
   };
-  int nthreads = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u);
-  if ((size_t)w * h < (1u << 18) || nthreads == 1) {
-    rows_fn(0, h);
-    return;
+  for_map_rows(w, h, rows_fn);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pinhole models (plumb_bob, radtan, rational_polynomial)
+// ---------------------------------------------------------------------------------------------
+bool is_pinhole_model(const std::string& model) {
+  return model == "plumb_bob" || model == "radtan" || model == "rational_polynomial";
+}
+
+int distortion_coefficient_count(const std::string& model) {
+  if (model == "rational_polynomial") return 8;
+  return is_pinhole_model(model) ? 5 : 4;
+}
+
+void pinhole_coefficients(const std::string& model, const double D[8], double k[8]) {
+  const int n = model == "rational_polynomial" ? 8 : model == "plumb_bob" ? 5 : 4;
+  for (int i = 0; i < 8; i++) k[i] = i < n ? D[i] : 0.0;
+}
+
+// cv::getOptimalNewCameraMatrix: a 9 x 9 grid of source points is undistorted (20 fixed-point iterations, no R); the
+// inner rectangle holds only valid pixels, the outer one every source pixel, and balance blends the two cameras
+void pinhole_estimate_new_camera_matrix(const double K[9], const double k[8], int w, int h, double balance, int new_w,
+                                        int new_h, double fov_scale, double newK[9]) {
+  balance = std::min(std::max(balance, 0.0), 1.0);
+  const double k1 = k[0], k2 = k[1], p1 = k[2], p2 = k[3], k3 = k[4], k4 = k[5], k5 = k[6], k6 = k[7];
+  constexpr int N = 9;
+  double px[N][N], py[N][N];
+  for (int gy = 0; gy < N; gy++)
+    for (int gx = 0; gx < N; gx++) {
+      const double u = gx * (double)(w - 1) / 8, v = gy * (double)(h - 1) / 8;
+      const double x0 = (u - K[2]) / K[0], y0 = (v - K[5]) / K[4];
+      double x = x0, y = y0;
+      for (int it = 0; it < 20; it++) {
+        const double r2 = x * x + y * y;
+        const double icd = (1 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
+        const double dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
+        const double dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
+        x = (x0 - dx) * icd;
+        y = (y0 - dy) * icd;
+      }
+      px[gy][gx] = x;
+      py[gy][gx] = y;
+    }
+  double il = -DBL_MAX, ir = DBL_MAX, it_ = -DBL_MAX, ib = DBL_MAX;  // inner: left, right, top, bottom
+  double ol = DBL_MAX, or_ = -DBL_MAX, ot = DBL_MAX, ob = -DBL_MAX;  // outer
+  for (int a = 0; a < N; a++) {
+    il = std::max(il, px[a][0]);
+    ir = std::min(ir, px[a][N - 1]);
+    it_ = std::max(it_, py[0][a]);
+    ib = std::min(ib, py[N - 1][a]);
+    for (int b = 0; b < N; b++) {
+      ol = std::min(ol, px[a][b]);
+      or_ = std::max(or_, px[a][b]);
+      ot = std::min(ot, py[a][b]);
+      ob = std::max(ob, py[a][b]);
+    }
   }
-  std::vector<std::thread> pool;
-  int chunk = (h + nthreads - 1) / nthreads;
-  for (int t = 0; t < nthreads; t++) {
-    int r0 = t * chunk, r1 = std::min(h, r0 + chunk);
-    if (r0 < r1) pool.emplace_back(rows_fn, r0, r1);
+  const double nw = new_w, nh = new_h;
+  const double fx0 = (nw - 1) / (ir - il), fy0 = (nh - 1) / (ib - it_), cx0 = -fx0 * il, cy0 = -fy0 * it_;
+  const double fx1 = (nw - 1) / (or_ - ol), fy1 = (nh - 1) / (ob - ot), cx1 = -fx1 * ol, cy1 = -fy1 * ot;
+  double fx = fx0 * (1 - balance) + fx1 * balance, fy = fy0 * (1 - balance) + fy1 * balance;
+  const double cx = cx0 * (1 - balance) + cx1 * balance, cy = cy0 * (1 - balance) + cy1 * balance;
+  if (fov_scale > 0) {
+    fx = fx / fov_scale;
+    fy = fy / fov_scale;
   }
-  for (auto& th : pool) th.join();
+  const double out[9] = {fx, 0, cx, 0, fy, cy, 0, 0, 1};
+  std::memcpy(newK, out, sizeof(out));
+}
+
+// cv::initUndistortRectifyMap (CV_32FC1) in double, statement for statement what rip_maps.hip pinhole_maps_kernel does
+void pinhole_init_undistort_rectify_map(const double K[9], const double k[8], const double R[9], const double P[9], int w,
+                                        int h, float* map_xy) {
+  const Mat3 iR = inverse3(mul3(P, R));
+  const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+  const double k1 = k[0], k2 = k[1], p1 = k[2], p2 = k[3], k3 = k[4], k4 = k[5], k5 = k[6], k6 = k[7];
+  auto rows_fn = [&](int r0, int r1) {
+    for (int i = r0; i < r1; i++) {
+      double X = i * iR.v[1] + iR.v[2], Y = i * iR.v[4] + iR.v[5], W = i * iR.v[7] + iR.v[8];
+      float* out = map_xy + (size_t)i * w * 2;
+      for (int j = 0; j < w; j++) {
+        const double wi = 1.0 / W, x = X * wi, y = Y * wi;
+        const double x2 = x * x, y2 = y * y, r2 = x2 + y2, xy2 = 2 * x * y;
+        const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+        const double xd = x * kr + p1 * xy2 + p2 * (r2 + 2 * x2);
+        const double yd = y * kr + p1 * (r2 + 2 * y2) + p2 * xy2;
+        out[2 * j] = (float)(fx * xd + cx);
+        out[2 * j + 1] = (float)(fy * yd + cy);
+        X += iR.v[0];  // accumulated along the row, as OpenCV does
+        Y += iR.v[3];
+        W += iR.v[6];
+      }
+    }
+  };
+  for_map_rows(w, h, rows_fn);
 }
 
 // ---------------------------------------------------------------------------------------------

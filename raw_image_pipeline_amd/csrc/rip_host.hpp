@@ -83,7 +83,8 @@ struct Modules {
   bool und_enabled = false, und_available = false;
   std::string dist_model = "none", rect_model = "none";
   double dist_K[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, rect_K[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  double dist_D[4] = {0, 0, 0, 0}, rect_D[4] = {0, 0, 0, 0};
+  // as given (up to 8, the rest 0): the fisheye builder reads the first four, the pinhole models what pinhole_coefficients() keeps
+  double dist_D[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rect_D[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double dist_R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, rect_R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   double dist_P[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, rect_P[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   int dist_w = 320, dist_h = 240, rect_w = 320, rect_h = 240;
@@ -147,6 +148,23 @@ void fisheye_estimate_new_camera_matrix(const double K[9], const double D[4], in
 void fisheye_inverse_PR(const double P[9], const double R[9], double iR_out[9]);
 void fisheye_init_undistort_rectify_map(const double K[9], const double D[4], const double R[9],
                                         const double P[9], int w, int h, float* map_xy);
+
+// ---------------------------------------------------------------------------------------------
+// Pinhole undistortion (distortion models plumb_bob, radtan, rational_polynomial: cv::getOptimalNewCameraMatrix and
+// cv::initUndistortRectifyMap restated in double, PARITY.md "Pinhole distortion models"); not in the reference, which
+// builds fisheye maps whatever the model says
+// ---------------------------------------------------------------------------------------------
+bool is_pinhole_model(const std::string& model);
+// the length of the coefficient vector a model reports: 5 for plumb_bob and radtan, 8 for rational_polynomial, 4 otherwise
+int distortion_coefficient_count(const std::string& model);
+// the coefficients a pinhole model evaluates, (k1 k2 p1 p2 k3 k4 k5 k6): radtan takes k3 = 0, only rational_polynomial keeps k4..k6
+void pinhole_coefficients(const std::string& model, const double D[8], double k[8]);
+// alpha = balance clamped to [0, 1]: 0 crops to valid pixels, 1 keeps every source pixel.  Never throws.
+void pinhole_estimate_new_camera_matrix(const double K[9], const double k[8], int w, int h, double balance, int new_w,
+                                        int new_h, double fov_scale, double newK[9]);
+// Interleaved float2 map like the fisheye one; iR = fisheye_inverse_PR(P, R)
+void pinhole_init_undistort_rectify_map(const double K[9], const double k[8], const double R[9], const double P[9], int w,
+                                        int h, float* map_xy);
 
 // ---------------------------------------------------------------------------------------------
 // Compiled remap plan.  cv::remap(INTER_LINEAR) quantises every map entry to 1/32 px before

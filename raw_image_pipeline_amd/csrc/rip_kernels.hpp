@@ -234,15 +234,17 @@ struct RemapTiledParams {
   int exp;                     // timing-only experiment switches (Tunables::remap_exp); read by -DRIP_EXPERIMENTS builds only
 };
 
-// Fisheye maps on the device (rip_maps.hip): iR = (P R)^-1 from the host, K / D of the distorted camera.
-struct FisheyeMapParams {
-  double K[9], D[4], iR[9];
-  int w, h;
+// Undistortion maps on the device (rip_maps.hip): iR = (P R)^-1 from the host, K / D of the distorted camera.  pinhole == 0:
+// fisheye (D[0..3] = k1..k4 of Kannala-Brandt); pinhole != 0: D = (k1 k2 p1 p2 k3 k4 k5 k6) as rip::pinhole_coefficients
+// leaves them (plumb_bob, radtan, rational_polynomial).
+struct UndistortMapParams {
+  double K[9], D[8], iR[9];
+  int w, h, pinhole;
   float* map_xy;  // [h][w] interleaved (x, y)
-  double* ckpt;   // scratch: fisheye_ckpt_bytes(w, h) bytes -- the row accumulators (X, Y, W) at every 32nd column
+  double* ckpt;   // scratch: undistort_ckpt_bytes(w, h) bytes -- the row accumulators (X, Y, W) at every 32nd column
 };
-size_t fisheye_ckpt_bytes(int w, int h);
-void launch_fisheye_maps(const FisheyeMapParams& p, hipStream_t stream);
+size_t undistort_ckpt_bytes(int w, int h);
+void launch_undistort_maps(const UndistortMapParams& p, hipStream_t stream);
 void launch_atan_probe(const double* in, double* out, int n, hipStream_t stream);  // test hook: the kernel's atan
 
 // Remap-plan compiler on the device (host counterpart and format: rip_host.cpp compile_remap_plan): one workgroup per

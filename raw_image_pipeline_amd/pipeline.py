@@ -638,7 +638,10 @@ class RawImagePipeline:
         self._set_vec("rip_set_undistortion_camera_matrix", m)
 
     def set_undistortion_distortion_coeffs(self, d):
+        """All values given are passed on: 4 for the fisheye models, 5 for plumb_bob, 8 for rational_polynomial."""
         self._set_vec("rip_set_undistortion_distortion_coefficients", d)
+
+    set_undistortion_distortion_coefficients = set_undistortion_distortion_coeffs
 
     def set_undistortion_distortion_model(self, model):
         self._call("rip_set_undistortion_distortion_model", model.encode())
@@ -715,8 +718,14 @@ class RawImagePipeline:
     def get_dist_camera_matrix(self):
         return self._matrix("rip_get_dist_camera_matrix", (3, 3))
 
+    def _coefficients(self, rect):
+        # 1 x n: n = 5 for plumb_bob and radtan, 8 for rational_polynomial, 4 for every other model (include/rip.h)
+        buf, n = (C.c_double * 8)(), C.c_int()
+        self._call("rip_get_distortion_coefficients_n", int(rect), buf, 8, C.byref(n))
+        return np.array(buf[:n.value], dtype=np.float64).reshape(1, n.value)
+
     def get_dist_distortion_coefficients(self):
-        return self._matrix("rip_get_dist_distortion_coefficients", (1, 4))
+        return self._coefficients(0)
 
     def get_dist_rectification_matrix(self):
         return self._matrix("rip_get_dist_rectification_matrix", (3, 3))
@@ -728,7 +737,7 @@ class RawImagePipeline:
         return self._matrix("rip_get_rect_camera_matrix", (3, 3))
 
     def get_rect_distortion_coefficients(self):
-        return self._matrix("rip_get_rect_distortion_coefficients", (1, 4))
+        return self._coefficients(1)
 
     def get_rect_rectification_matrix(self):
         return self._matrix("rip_get_rect_rectification_matrix", (3, 3))

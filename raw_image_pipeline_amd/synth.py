@@ -67,6 +67,17 @@ def camera_model(width, height):
     return dict(K=K, D=list(DIST_COEFFS), R=R, P=P, width=width, height=height)
 
 
+def pinhole_camera_model(width, height, D):
+    """Pinhole camera for the plumb_bob / radtan / rational_polynomial models at any W x H: a 60-degree-class lens with the
+    principal point of camera_model() and the coefficients D = (k1 k2 p1 p2 [k3 [k4 k5 k6]])."""
+    fx, cx = 0.6 * width, 0.49431 * width
+    fy, cy = 0.5994 * width, 0.48593 * height
+    K = [fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0]
+    R = [1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0]
+    P = [fx, 0.0, cx, 0.0, 0.0, fy, cy, 0.0, 0.0, 0.0, 1.0, 0.0]
+    return dict(K=K, D=[float(v) for v in D], R=R, P=P, width=width, height=height)
+
+
 def calibration_yaml(cam, model="equidistant"):
     """Camera calibration file text in the ROS camera_calibration_parsers layout the reference reads
     (undistortion.cpp:165-170)."""
@@ -75,10 +86,10 @@ def calibration_yaml(cam, model="equidistant"):
     return ("image_width: %d\nimage_height: %d\ncamera_name: synthetic\n"
             "camera_matrix:\n  rows: 3\n  cols: 3\n  data: %s\n"
             "distortion_model: %s\n"
-            "distortion_coefficients:\n  rows: 1\n  cols: 4\n  data: %s\n"
+            "distortion_coefficients:\n  rows: 1\n  cols: %d\n  data: %s\n"
             "rectification_matrix:\n  rows: 3\n  cols: 3\n  data: %s\n"
             "projection_matrix:\n  rows: 3\n  cols: 4\n  data: %s\n"
-            % (cam["width"], cam["height"], seq(cam["K"]), model, seq(cam["D"]), seq(cam["R"]), seq(cam["P"])))
+            % (cam["width"], cam["height"], seq(cam["K"]), model, len(cam["D"]), seq(cam["D"]), seq(cam["R"]), seq(cam["P"])))
 
 
 def load_camera(pipe, cam, model="equidistant"):
