@@ -386,6 +386,17 @@ rip_status rip_debug_atan(rip_pipeline* p, const double* in, double* out, int n)
  * border pixels, largest LDS footprint of a tile's source rectangle in bytes, largest rectangle width, height, 1 if the
  * plan was compiled on the device, tile width, tile height}.  Needs a loaded calibration and a device. */
 rip_status rip_debug_plan_info(rip_pipeline* p, int src_rows, int src_cols, int info[9]);
+/* Test hook: the launch record.  While on, every kernel launch of the product path made by a call on this handle (frames,
+ * batches, the lazily built maps / plan / tables; not the re-runs of the debug stage dumps, not the probes) appends one line
+ *   <kernel> fc=<0|1> grid=<x>,<y> block=<threads> frames=<n>
+ * <kernel>: the kernel's name with its template arguments as a demangler prints them, without namespaces, e.g.
+ * "chain_fast_kernel<7, 1, 512, false>"; fc: the floating-point model it was compiled under (rip_set_fp_contraction; the
+ * twins share a name); frames: the batch the launch serves (0 for the map, plan and table builders).  enable != 0 clears the
+ * log and switches it on, 0 switches it off and keeps the text.  Off, a launch pays one null test. */
+rip_status rip_debug_launch_log(rip_pipeline* p, int enable);
+/* The record as NUL-terminated text.  *needed (optional) receives the bytes it takes, terminator included; a smaller
+ * capacity returns RIP_ERR_CAPACITY and copies nothing. */
+rip_status rip_debug_get_launch_log(rip_pipeline* p, char* out, size_t capacity, size_t* needed);
 /* Test hook: the part of a src_rows x src_cols intermediate image the undistortion reads, as the fused Bayer chain kernel
  * walks it in front of the remap (items of 4 x 2 pixels in its input's coordinates, flipped by flip_angle, 0 or 180):
  * info = {items of the whole frame, items in the footprint, row pairs with a footprint, items per frame the last chain

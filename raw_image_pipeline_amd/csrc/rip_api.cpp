@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -345,6 +346,23 @@ struct RingSlot {
 
 }  // namespace
 
+// Launch record (rip_kernels.hpp): the text of a handle's log, one launch per line
+namespace rip {
+struct LaunchLog {
+  std::string text;
+};
+__thread LaunchLog* t_launch_log = nullptr;
+void launch_log_add(LaunchLog* log, int fc, unsigned grid_x, unsigned grid_y, unsigned block, int frames, const char* fmt, ...) {
+  char name[160], line[256];
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(name, sizeof(name), fmt, ap);
+  va_end(ap);
+  std::snprintf(line, sizeof(line), "%s fc=%d grid=%u,%u block=%u frames=%d\n", name, fc, grid_x, grid_y, block, frames);
+  log->text += line;
+}
+}  // namespace rip
+
 struct rip_pipeline {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -420,6 +438,9 @@ struct rip_pipeline {
   std::vector<hipEvent_t> prof_events;  // pairs
   std::vector<int> prof_ids;
   size_t prof_used = 0;
+  // rip_debug_launch_log: which kernels the handle's calls launched
+  bool launch_log_on = false;
+  rip::LaunchLog launch_log;
   // host-apply staging and last-frame taps
   DevBuf d_in, d_out, d_tap_deb, d_tap_col, d_dbg;
   int last_rows[3] = {0, 0, 0}, last_cols[3] = {0, 0, 0}, last_cn[3] = {0, 0, 0};
@@ -465,6 +486,15 @@ struct ProfScope {
   }
 };
 
+// RAII: points this thread's launch-record sink at the handle's log (when that is on) around the code that launches kernels
+struct LaunchLogScope {
+  rip::LaunchLog* before;
+  explicit LaunchLogScope(rip_pipeline* p) : before(rip::t_launch_log) { rip::t_launch_log = p->launch_log_on ? &p->launch_log : nullptr; }
+  ~LaunchLogScope() { rip::t_launch_log = before; }
+  LaunchLogScope(const LaunchLogScope&) = delete;
+  LaunchLogScope& operator=(const LaunchLogScope&) = delete;
+};
+
 // ------------------------------------------------------------------------------------------------
 // undistortion bookkeeping: UndistortionModule::init() (undistortion.cpp:197-238) minus the map
 // generation, which is deferred until a frame (or rip_init_undistortion) needs it.
@@ -505,6 +535,7 @@ void ensure_host_maps(rip_pipeline* p) {
   const bool pinhole = rip::is_pinhole_model(m.dist_model);  // every other name builds fisheye maps, as the reference does
   if (maps_on_device(p)) {
     DeviceGuard device_guard(p->device);
+    LaunchLogScope log_scope(p);
     rip::UndistortMapParams fp = {};
     std::memcpy(fp.K, m.dist_K, sizeof(fp.K));
     fp.pinhole = pinhole ? 1 : 0;
@@ -558,6 +589,7 @@ static_assert(sizeof(rip::RemapTile) == sizeof(rip::RemapTileDesc), "tile descri
 
 void ensure_plan(rip_pipeline* p, int src_rows, int src_cols) {
   ensure_maps(p);
+  LaunchLogScope log_scope(p);
   const rip::Modules& m = p->m;
   if (!p->plan.valid || p->plan.src_rows != src_rows || p->plan.src_cols != src_cols || p->plan.drows != m.dist_h ||
       p->plan.dcols != m.dist_w) {
@@ -685,6 +717,7 @@ void ensure_maps(rip_pipeline* p) {
 
 void ensure_tables(rip_pipeline* p) {
   if (!p->tabs_dirty) return;
+  LaunchLogScope log_scope(p);
   rip::DevTables& t = p->h_tabs;
   const rip::ColorTables& c = rip::color_tables();
   rip::build_gamma_lut(p->m.gamma_k, t.gamma_lut);
@@ -936,6 +969,7 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
                bool reuse_wb = false) {
   p->work_enqueued = true;  // from here on something may sit on p->stream
   DeviceGuard device_guard(p->device);
+  LaunchLogScope log_scope(p);
   // Malvar-He-Cutler demosaic (rip_set_debayer_method "mht", rip_demosaic.hip): one pass of its own writes the post-flip BGR
   // image -- the DEBAYERED tap (flip.cpp:60-62), into the caller's tap buffer when one was requested -- and the rest of the
   // chain runs on that image exactly as on a bgr8 frame holding it, with no flip left to do.  16-bit frames: the kernel writes
@@ -1421,12 +1455,15 @@ void write_debug_dumps(rip_pipeline* p, const Plan& pl, size_t in_pitch, size_t 
   const std::string& dir = p->debug_dir;
   std::vector<uint8_t> host;
   // the re-runs below are not launches of the caller's frame: keep them out of an active rip_profile_begin/end session
-  // (they would skew its per-class averages and use up its event slots)
+  // (they would skew its per-class averages and use up its event slots), and out of the launch record (rip_debug_launch_log)
   struct ProfPause {
     rip_pipeline* p;
-    bool was;
-    explicit ProfPause(rip_pipeline* pp) : p(pp), was(pp->prof_on) { p->prof_on = false; }
-    ~ProfPause() { p->prof_on = was; }
+    bool was, log_was;
+    explicit ProfPause(rip_pipeline* pp) : p(pp), was(pp->prof_on), log_was(pp->launch_log_on) { p->prof_on = p->launch_log_on = false; }
+    ~ProfPause() {
+      p->prof_on = was;
+      p->launch_log_on = log_was;
+    }
   } prof_pause(p);
   std::string failed;
   for (int k = 0; k < 8; k++) {
@@ -2423,6 +2460,25 @@ rip_status rip_profile_end(rip_pipeline* p, double ms_sum[RIP_KERNEL_COUNT], int
     p->prof_on = false;
     p->prof_used = 0;
     p->prof_ids.clear();
+  });
+}
+
+rip_status rip_debug_launch_log(rip_pipeline* p, int enable) {
+  return guarded(p, [&] {
+    need(p);
+    if (enable) p->launch_log.text.clear();
+    p->launch_log_on = enable != 0;
+  });
+}
+
+rip_status rip_debug_get_launch_log(rip_pipeline* p, char* out, size_t capacity, size_t* needed) {
+  return guarded(p, [&] {
+    need(p);
+    const std::string& t = p->launch_log.text;
+    if (needed) *needed = t.size() + 1;
+    if (capacity < t.size() + 1) throw CapacityError("launch log: " + std::to_string(t.size() + 1) + " bytes needed");
+    if (!out) throw InvalidArgument("null buffer");
+    std::memcpy(out, t.c_str(), t.size() + 1);
   });
 }
 

@@ -724,24 +724,34 @@ bool launch_ccc_estimate(const CccParams& p, const Tunables& tn, hipStream_t str
   q.hist_split = lds_hist ? std::max(1, p.hist_split) : 1;  // the caller's split: its buffer is sized for it
   q.hist_zero_after = lds_hist ? 0 : 1;
   if (lds_hist) {
+    RIP_LOG_LAUNCH(dim3(p.n_frames * q.hist_split), kHistLdsThreads, p.n_frames, "ccc_hist_lds_kernel");
     hipLaunchKernelGGL(ccc_hist_lds_kernel, dim3(p.n_frames * q.hist_split), dim3(kHistLdsThreads), lds, stream, q);
   } else {
     if (!p.hist_is_clean && hipMemsetAsync(p.hist_counts, 0, (size_t)p.n_frames * 65536 * sizeof(unsigned), stream) != hipSuccess) return false;
+    RIP_LOG_LAUNCH(dim3(kHistBlocks, p.n_frames), kBlock, p.n_frames, "ccc_hist_kernel");
     hipLaunchKernelGGL(ccc_hist_kernel, dim3(kHistBlocks, p.n_frames), dim3(kBlock), 0, stream, q);
   }
   // a histogram that was not launched leaves stale counts behind: stop before anything consumes them (the caller must
   // not advance the Kalman state either)
   if (hipGetLastError() != hipSuccess) return false;
   if (p.n_frames <= kFftFewFrames) {  // a few frames: 64 one-wave workgroups per frame instead of 16 four-wave ones
+    if (t_launch_log != nullptr)
+      for (const char* k : {"ccc_fft_rows16_kernel", "ccc_fft_cols_kernel", "ccc_ifft_rows16_kernel"}) RIP_LOG_LAUNCH(dim3(64, p.n_frames), 64, p.n_frames, "%s<4>", k);
     hipLaunchKernelGGL(ccc_fft_rows16_kernel<4>, dim3(64, p.n_frames), dim3(64), 0, stream, q);
     hipLaunchKernelGGL(ccc_fft_cols_kernel<4>, dim3(64, p.n_frames), dim3(64), 0, stream, p);
     hipLaunchKernelGGL(ccc_ifft_rows16_kernel<4>, dim3(64, p.n_frames), dim3(64), 0, stream, p);
   } else {
+    if (t_launch_log != nullptr)
+      for (const char* k : {"ccc_fft_rows16_kernel", "ccc_fft_cols_kernel", "ccc_ifft_rows16_kernel"})
+        RIP_LOG_LAUNCH(dim3(256 / kFftCols, p.n_frames), 16 * kFftCols, p.n_frames, "%s<%d>", k, kFftCols);
     hipLaunchKernelGGL(ccc_fft_rows16_kernel<kFftCols>, dim3(256 / kFftCols, p.n_frames), dim3(16 * kFftCols), 0, stream, q);
     hipLaunchKernelGGL(ccc_fft_cols_kernel<kFftCols>, dim3(256 / kFftCols, p.n_frames), dim3(16 * kFftCols), 0, stream, p);
     hipLaunchKernelGGL(ccc_ifft_rows16_kernel<kFftCols>, dim3(256 / kFftCols, p.n_frames), dim3(16 * kFftCols), 0, stream, p);
   }
-  if (!ccc_argmax_in_finalize(p.n_frames)) hipLaunchKernelGGL(ccc_argmax_kernel, dim3(p.n_frames), dim3(256), 0, stream, p);
+  if (!ccc_argmax_in_finalize(p.n_frames)) {
+    RIP_LOG_LAUNCH(dim3(p.n_frames), 256, p.n_frames, "ccc_argmax_kernel");
+    hipLaunchKernelGGL(ccc_argmax_kernel, dim3(p.n_frames), dim3(256), 0, stream, p);
+  }
   const bool ok = hipGetLastError() == hipSuccess;
   if (ok && !lds_hist && hist_left_clean) *hist_left_clean = 1;
   return ok;

@@ -493,6 +493,7 @@ void launch_fast_as(const ChainParams& p, const ItemMap& im, int items, dim3 gri
     std::fprintf(stderr, "[rip] chain_fast_kernel<%d,%d,%d,%d>: %d workgroups/CU, %d VGPR, %zu B LDS, grid %u x %u\n", BITS, WB, NT, (int)LIST,
                  nb, fa.numRegs, fa.sharedSizeBytes, grid.x, grid.y);
   }
+  RIP_LOG_LAUNCH(grid, NT, p.n_frames, "chain_fast_kernel<%d, %d, %d, %s>", BITS, WB, NT, launch_log_bool(LIST));
   hipLaunchKernelGGL((chain_fast_kernel<BITS, WB, NT, LIST>), grid, dim3(NT), 0, stream, p, im, items);
 }
 template <int BITS, int WB>
@@ -506,6 +507,7 @@ void launch_fast(const ChainParams& p, const ItemMap& im, int items, dim3 grid, 
 template <int BITS, int WB>
 void launch_color(const ChainParams& p, const ItemMap& im, int items, dim3 grid, hipStream_t stream) {
   constexpr int NT = fast_threads<BITS>();
+  RIP_LOG_LAUNCH(grid, NT, p.n_frames, "chain_color_kernel<%d, %d, %d>", BITS, WB, NT);
   hipLaunchKernelGGL((chain_color_kernel<BITS, WB, NT>), grid, dim3(NT), 0, stream, p, im, items);
 }
 template <int BITS>
@@ -522,6 +524,7 @@ void launch_color_wb(const ChainParams& p, const ItemMap& im, int items, dim3 gr
 template <int BITS, int WB>
 void launch_rot(const ChainParams& p, int tiles_x, int tiles, dim3 grid, hipStream_t stream) {
   constexpr int NT = fast_threads<BITS>();
+  RIP_LOG_LAUNCH(grid, NT, p.n_frames, "chain_rot_kernel<%d, %d, %d>", BITS, WB, NT);
   hipLaunchKernelGGL((chain_rot_kernel<BITS, WB, NT>), grid, dim3(NT), 0, stream, p, tiles_x, tiles);
 }
 template <int BITS>
@@ -620,13 +623,16 @@ bool chain_uses_rot_path(const ChainParams& p);
 #else
 size_t vig_image_bytes() { return sizeof(VigTabs); }
 void launch_vig_image(const DevTables* tabs, uint32_t* image, hipStream_t stream) {
+  RIP_LOG_LAUNCH(dim3(1), 512, 0, "vig_image_kernel");
   hipLaunchKernelGGL(vig_image_kernel, dim3(1), dim3(512), 0, stream, tabs, image);
 }
 
 void launch_debayer16(const Debayer16Params& p, hipStream_t stream) {
   if (p.n_frames <= 0) return;
   const long long npix = (long long)p.drows * p.dcols;
-  hipLaunchKernelGGL(debayer16_kernel, dim3(grid_blocks_for(npix, 4096), p.n_frames), dim3(kBlock), 0, stream, p);
+  const dim3 grid(grid_blocks_for(npix, 4096), p.n_frames);
+  RIP_LOG_LAUNCH(grid, kBlock, p.n_frames, "debayer16_kernel");
+  hipLaunchKernelGGL(debayer16_kernel, grid, dim3(kBlock), 0, stream, p);
 }
 
 #endif  // RIP_FP_CONTRACT
@@ -709,11 +715,13 @@ void launch_chain(const ChainParams& p_in, const Tunables& tn, hipStream_t strea
     const int chunks = (items + kBlock - 1) / kBlock;
     const int blocks = std::min(8192, chunks);
     const int groups = frame_groups(p, tn, 8192, blocks);  // memory-rate: two (four with the gamma table) frames per visit
+    RIP_LOG_LAUNCH(dim3(blocks, groups), kBlock, p.n_frames, "chain_mono_kernel");
     hipLaunchKernelGGL(chain_mono_kernel, dim3(blocks, groups), dim3(kBlock), 0, stream, p, im, items);
     return;
   }
   long long npix = (long long)p.drows * p.dcols;
   dim3 grid(grid_blocks_for(npix, 2048), p.n_frames);
+  RIP_LOG_LAUNCH(grid, kBlock, p.n_frames, "chain_generic_kernel");
   hipLaunchKernelGGL(chain_generic_kernel, grid, dim3(kBlock), 0, stream, p);
 }
 

@@ -302,6 +302,7 @@ __global__ __launch_bounds__(kMhtBlock) void demosaic_mht_pixel_kernel(MhtParams
 
 template <int RY, int RX>
 void launch_tile(const MhtParams& p, dim3 grid, hipStream_t stream) {
+  RIP_LOG_LAUNCH(grid, kMhtBlock, p.n_frames, "demosaic_mht_tile_kernel<%d, %d, %d>", RY, RX, p.flip_angle);
   switch (p.flip_angle) {
     case 90: hipLaunchKernelGGL((demosaic_mht_tile_kernel<RY, RX, 90>), grid, dim3(kMhtBlock), 0, stream, p); break;
     case 180: hipLaunchKernelGGL((demosaic_mht_tile_kernel<RY, RX, 180>), grid, dim3(kMhtBlock), 0, stream, p); break;
@@ -340,6 +341,7 @@ void launch_demosaic_mht(const MhtParams& p_in, hipStream_t stream) {
   }
   const long long npix = (long long)p.drows * p.dcols;
   const int blocks = (int)std::max(1LL, std::min(4096LL, (npix + kMhtBlock - 1) / kMhtBlock));
+  RIP_LOG_LAUNCH(dim3(blocks, p.n_frames), kMhtBlock, p.n_frames, "demosaic_mht_pixel_kernel<unsigned short>");
   hipLaunchKernelGGL(demosaic_mht_pixel_kernel<uint16_t>, dim3(blocks, p.n_frames), dim3(kMhtBlock), 0, stream, p);
 }
 

@@ -328,14 +328,19 @@ __global__ __launch_bounds__(kBlock) void remap_border_bayer_kernel(RemapTiledPa
   o[2] = (uint8_t)((acc[2] + 512) >> 10);
 }
 
+template <int PRE, int BITS, int WB>
+void launch_fused_as(const RemapTiledParams& q, const ChainParams& c, unsigned bgr_off, unsigned bgr_bytes, dim3 grid, unsigned lds, hipStream_t stream) {
+  RIP_LOG_LAUNCH(grid, kRemapTileThreads, q.base.n_frames, "remap_bayer_ring_kernel<%d, %d, %d>", PRE, BITS, WB);
+  hipLaunchKernelGGL((remap_bayer_ring_kernel<PRE, BITS, WB>), grid, dim3(kRemapTileThreads), lds, stream, q, c, bgr_off, bgr_bytes);
+}
 template <int PRE, int BITS>
 void launch_fused_wb(const RemapTiledParams& q, const ChainParams& c, unsigned bgr_off, unsigned bgr_bytes, dim3 grid, unsigned lds, hipStream_t stream) {
   switch (c.wb_mode) {
-    case WB_Q8: hipLaunchKernelGGL((remap_bayer_ring_kernel<PRE, BITS, WB_Q8>), grid, dim3(kRemapTileThreads), lds, stream, q, c, bgr_off, bgr_bytes); break;
-    case WB_FLOAT: hipLaunchKernelGGL((remap_bayer_ring_kernel<PRE, BITS, WB_FLOAT>), grid, dim3(kRemapTileThreads), lds, stream, q, c, bgr_off, bgr_bytes); break;
-    case WB_PCA: hipLaunchKernelGGL((remap_bayer_ring_kernel<PRE, BITS, WB_PCA>), grid, dim3(kRemapTileThreads), lds, stream, q, c, bgr_off, bgr_bytes); break;
-    case WB_SIMPLE: hipLaunchKernelGGL((remap_bayer_ring_kernel<PRE, BITS, WB_SIMPLE>), grid, dim3(kRemapTileThreads), lds, stream, q, c, bgr_off, bgr_bytes); break;
-    default: hipLaunchKernelGGL((remap_bayer_ring_kernel<PRE, BITS, WB_NONE>), grid, dim3(kRemapTileThreads), lds, stream, q, c, bgr_off, bgr_bytes); break;
+    case WB_Q8: launch_fused_as<PRE, BITS, WB_Q8>(q, c, bgr_off, bgr_bytes, grid, lds, stream); break;
+    case WB_FLOAT: launch_fused_as<PRE, BITS, WB_FLOAT>(q, c, bgr_off, bgr_bytes, grid, lds, stream); break;
+    case WB_PCA: launch_fused_as<PRE, BITS, WB_PCA>(q, c, bgr_off, bgr_bytes, grid, lds, stream); break;
+    case WB_SIMPLE: launch_fused_as<PRE, BITS, WB_SIMPLE>(q, c, bgr_off, bgr_bytes, grid, lds, stream); break;
+    default: launch_fused_as<PRE, BITS, WB_NONE>(q, c, bgr_off, bgr_bytes, grid, lds, stream); break;
   }
 }
 template <int PRE>
@@ -414,7 +419,11 @@ bool launch_remap_fused(const RemapTiledParams& p, const ChainParams& c, int max
     launch_fused_bits<2>(q, c, bgr_off, bgr_bytes, grid, lds, stream);
   else
     launch_fused_bits<4>(q, c, bgr_off, bgr_bytes, grid, lds, stream);
-  if (q.n_border > 0) hipLaunchKernelGGL(remap_border_bayer_kernel, dim3((q.n_border + 255) / 256, b.n_frames), dim3(256), 0, stream, q, c);
+  if (q.n_border > 0) {
+    const dim3 border_grid((q.n_border + 255) / 256, b.n_frames);
+    RIP_LOG_LAUNCH(border_grid, 256, b.n_frames, "remap_border_bayer_kernel");
+    hipLaunchKernelGGL(remap_border_bayer_kernel, border_grid, dim3(256), 0, stream, q, c);
+  }
   return true;
 }
 

@@ -296,6 +296,25 @@ struct Tunables {
 };
 Tunables tunables_from_env();  // rip_api.cpp; called by rip_create
 
+// Launch record (rip_debug_launch_log, debug API): while a handle's log is on, the API entry points that enqueue kernels point
+// this thread's sink at it and every launch site of the product path appends one line,
+//   <kernel with its template arguments as the demangler prints them> fc=<0|1> grid=<x>,<y> block=<n> frames=<n>
+// fc: the floating-point model the translation unit was compiled under (the _fc1 twins share a kernel's name).  Off -- the sink
+// is null -- a launch site pays one null test: no formatting, no allocation, no lock.
+struct LaunchLog;                       // rip_api.cpp
+extern __thread LaunchLog* t_launch_log;  // null: off
+void launch_log_add(LaunchLog* log, int fc, unsigned grid_x, unsigned grid_y, unsigned block, int frames, const char* fmt, ...)
+    __attribute__((format(printf, 7, 8)));
+#ifndef RIP_FP_CONTRACT
+#define RIP_FP_CONTRACT 0
+#endif
+#define RIP_LOG_LAUNCH(grid, block, frames, ...)                                                                                \
+  do {                                                                                                                          \
+    if (::rip::t_launch_log != nullptr)                                                                                         \
+      ::rip::launch_log_add(::rip::t_launch_log, RIP_FP_CONTRACT, (grid).x, (grid).y, (unsigned)(block), (frames), __VA_ARGS__); \
+  } while (0)
+inline const char* launch_log_bool(bool b) { return b ? "true" : "false"; }
+
 // ---- launchers (asynchronous on `stream`) -------------------------------------------------------
 // Returns false (and launches nothing) when the geometry does not qualify for the tiled kernel.
 // dry_run: only answer (the API decides with it whether a mono8 chain can be folded into the gather).

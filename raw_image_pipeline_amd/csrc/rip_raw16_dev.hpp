@@ -42,6 +42,7 @@
 #include "rip_unpack.hpp"
 
 #include <algorithm>
+#include <cstdio>
 
 namespace rip {
 namespace {
@@ -95,6 +96,7 @@ __device__ __forceinline__ void bilinear_at(const uint16_t* s16, int r, int c, i
 // uint16 samples, two per dword: an interior tile's row is kLdsDwords aligned dwords (tx0 - 2 is even)
 struct StageU16 {
   static constexpr bool kPacked = false;
+  static constexpr int kLayout = 0;
   __device__ static __forceinline__ uint32_t sample(const uint8_t* row, int x) { return *reinterpret_cast<const uint16_t*>(row + (size_t)x * 2); }
 };
 
@@ -102,6 +104,7 @@ struct StageU16 {
 template <int LAYOUT>
 struct StagePacked {
   static constexpr bool kPacked = true;
+  static constexpr int kLayout = LAYOUT;
   static constexpr int kBits = LAYOUT == PACKED_10P || LAYOUT == PACKED_10_CSI2 ? 10 : 12;
   __device__ static __forceinline__ uint32_t sample(const uint8_t* row, int x) { return unpack_sample<LAYOUT>(row, x); }
   // dword of the row that holds the last byte the tile at tx0 needs (sample tx0 + kTileW + 1)
@@ -384,6 +387,12 @@ __global__ __launch_bounds__(kBlock16) void raw16_tile_kernel(Raw16Params p) {
 
 template <class L, bool MHT, int RY, int RX>
 void launch_angle(const Raw16Params& p, dim3 grid, hipStream_t stream) {
+  if (t_launch_log != nullptr) {  // the layout class as the demangler prints it
+    char layout[24];
+    if (L::kPacked) std::snprintf(layout, sizeof(layout), "StagePacked<%d>", L::kLayout);
+    else std::snprintf(layout, sizeof(layout), "StageU16");
+    RIP_LOG_LAUNCH(grid, kBlock16, p.n_frames, "raw16_tile_kernel<%s, %s, %d, %d, %d>", layout, launch_log_bool(MHT), RY, RX, p.flip_angle);
+  }
   switch (p.flip_angle) {
     case 90: hipLaunchKernelGGL((raw16_tile_kernel<L, MHT, RY, RX, 90>), grid, dim3(kBlock16), 0, stream, p); break;
     case 180: hipLaunchKernelGGL((raw16_tile_kernel<L, MHT, RY, RX, 180>), grid, dim3(kBlock16), 0, stream, p); break;

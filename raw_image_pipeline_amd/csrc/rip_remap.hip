@@ -438,6 +438,21 @@ __global__ __launch_bounds__(kBlock) void remap_generic_kernel(RemapParams p) {
   }
 }
 
+template <int PRE, int CN, bool LUT>
+void launch_ring(const RemapTiledParams& q, dim3 grid, unsigned lds, hipStream_t stream) {
+  RIP_LOG_LAUNCH(grid, kRemapTileThreads, q.base.n_frames, "remap_ring_kernel<%d, %d, %s>", PRE, CN, launch_log_bool(LUT));
+  hipLaunchKernelGGL((remap_ring_kernel<PRE, CN, LUT>), grid, dim3(kRemapTileThreads), lds, stream, q);
+}
+template <int CN, bool LUT>
+void launch_ring_pre(int pre, const RemapTiledParams& q, dim3 grid, unsigned lds, hipStream_t stream) {
+  if (pre == 1)
+    launch_ring<1, CN, LUT>(q, grid, lds, stream);
+  else if (pre == 2)
+    launch_ring<2, CN, LUT>(q, grid, lds, stream);
+  else
+    launch_ring<4, CN, LUT>(q, grid, lds, stream);
+}
+
 }  // namespace
 
 int remap_deal_run(int tiles_x, int tiles_y, const Tunables& tn) {
@@ -507,26 +522,12 @@ bool launch_remap_tiled(const RemapTiledParams& p, const Tunables& tn, hipStream
     int groups = std::max((256 * per_cu) / blocks, (b.n_frames + frames_per_visit - 1) / frames_per_visit);
     groups = std::max(1, std::min(b.n_frames, groups));
     const dim3 grid(blocks, groups);
-    if (b.channels == 1 && q.mono_lut) {
-      if (pre == 1)
-        hipLaunchKernelGGL((remap_ring_kernel<1, 1, true>), grid, dim3(kRemapTileThreads), lds, stream, q);
-      else if (pre == 2)
-        hipLaunchKernelGGL((remap_ring_kernel<2, 1, true>), grid, dim3(kRemapTileThreads), lds, stream, q);
-      else
-        hipLaunchKernelGGL((remap_ring_kernel<4, 1, true>), grid, dim3(kRemapTileThreads), lds, stream, q);
-    } else if (b.channels == 1) {
-      if (pre == 1)
-        hipLaunchKernelGGL((remap_ring_kernel<1, 1>), grid, dim3(kRemapTileThreads), lds, stream, q);
-      else if (pre == 2)
-        hipLaunchKernelGGL((remap_ring_kernel<2, 1>), grid, dim3(kRemapTileThreads), lds, stream, q);
-      else
-        hipLaunchKernelGGL((remap_ring_kernel<4, 1>), grid, dim3(kRemapTileThreads), lds, stream, q);
-    } else if (pre == 1)
-      hipLaunchKernelGGL((remap_ring_kernel<1, 3>), grid, dim3(kRemapTileThreads), lds, stream, q);
-    else if (pre == 2)
-      hipLaunchKernelGGL((remap_ring_kernel<2, 3>), grid, dim3(kRemapTileThreads), lds, stream, q);
+    if (b.channels == 1 && q.mono_lut)
+      launch_ring_pre<1, true>(pre, q, grid, lds, stream);
+    else if (b.channels == 1)
+      launch_ring_pre<1, false>(pre, q, grid, lds, stream);
     else
-      hipLaunchKernelGGL((remap_ring_kernel<4, 3>), grid, dim3(kRemapTileThreads), lds, stream, q);
+      launch_ring_pre<3, false>(pre, q, grid, lds, stream);
   } else {
     // rectangles larger than 4 * kRemapTileThreads chunks (strong local magnification) or RIP_REMAP_RING=0 (A/B runs)
     int pre = !ring_env && b.n_frames >= 2 && chunks <= 2u * kRemapTileThreads ? 2 : 0;
@@ -537,13 +538,17 @@ bool launch_remap_tiled(const RemapTiledParams& p, const Tunables& tn, hipStream
     blocks = std::max(8, blocks / 8 * 8);
     const int groups = std::max(1, std::min(b.n_frames, (256 * per_cu) / blocks));  // few tiles: split the batch too
     const dim3 grid(blocks, groups);
+    RIP_LOG_LAUNCH(grid, kRemapTileThreads, b.n_frames, "remap_tiled_kernel<%d>", pre);
     if (pre == 2)
       hipLaunchKernelGGL(remap_tiled_kernel<2>, grid, dim3(kRemapTileThreads), lds, stream, q);
     else
       hipLaunchKernelGGL(remap_tiled_kernel<0>, grid, dim3(kRemapTileThreads), lds, stream, q);
   }
-  if (q.n_border > 0)
-    hipLaunchKernelGGL(remap_border_kernel, dim3((q.n_border + 255) / 256, b.n_frames), dim3(256), 0, stream, q);
+  if (q.n_border > 0) {
+    const dim3 border_grid((q.n_border + 255) / 256, b.n_frames);
+    RIP_LOG_LAUNCH(border_grid, 256, b.n_frames, "remap_border_kernel");
+    hipLaunchKernelGGL(remap_border_kernel, border_grid, dim3(256), 0, stream, q);
+  }
   return true;
 }
 
@@ -559,11 +564,13 @@ bool launch_remap(const RemapParams& p, hipStream_t stream) {
     ItemMap im{p.dcols / 4, 1.0f / (float)(p.dcols / 4)};
     const int items = p.drows * (p.dcols / 4);
     int per_frame = grid_blocks_for(items, std::max(8, 8192 / std::max(1, std::min(p.n_frames, 16))));
+    RIP_LOG_LAUNCH(dim3(per_frame, p.n_frames), kBlock, p.n_frames, "remap_vec4_kernel");
     hipLaunchKernelGGL(remap_vec4_kernel, dim3(per_frame, p.n_frames), dim3(kBlock), 0, stream, p, im, items);
     return true;
   }
   long long npix = (long long)p.drows * p.dcols;
   dim3 grid(grid_blocks_for(npix, 4096), p.n_frames);
+  RIP_LOG_LAUNCH(grid, kBlock, p.n_frames, "remap_generic_kernel<%d>", p.channels == 3 ? 3 : 1);
   if (p.channels == 3)
     hipLaunchKernelGGL(remap_generic_kernel<3>, grid, dim3(kBlock), 0, stream, p);
   else

@@ -597,6 +597,7 @@ void launch_stats(const StatsParams& p, const Tunables& tn, hipStream_t stream) 
     const dim3 grid((task_blocks + 7) / 8 * 8, p.n_frames);  // a multiple of 8: one contiguous task range per XCD
     (void)items;
     (void)im;
+    RIP_LOG_LAUNCH(grid, kBlock, p.n_frames, "stats_fast_kernel<%d>", p.mode == WB_Q8 ? (int)WB_Q8 : (p.mode == WB_SIMPLE ? (int)WB_SIMPLE : (int)WB_PCA));
     if (p.mode == WB_Q8)
       hipLaunchKernelGGL(stats_fast_kernel<WB_Q8>, grid, dim3(kBlock), 0, stream, p, col_waves, pairs_per_task, n_tasks);
     else if (p.mode == WB_SIMPLE)
@@ -610,11 +611,13 @@ void launch_stats(const StatsParams& p, const Tunables& tn, hipStream_t stream) 
     const int items = p.rows * (p.cols / 4);
     int per_frame = grid_blocks_for(items, std::max(8, 2048 / std::max(1, std::min(p.n_frames, 16))));
     per_frame = std::max(per_frame, (int)((items + (1 << 20) - 1) >> 20));
+    RIP_LOG_LAUNCH(dim3(per_frame, p.n_frames), kBlock, p.n_frames, "stats_color_kernel");
     hipLaunchKernelGGL(stats_color_kernel, dim3(per_frame, p.n_frames), dim3(kBlock), stats_hist_lds_bytes(p.mode), stream, p, im, items);
     return;
   }
   long long npix = (long long)p.rows * p.cols;
   int blocks = std::max(grid_blocks_for(npix, 1024), (int)((npix + (1 << 22) - 1) >> 22));
+  RIP_LOG_LAUNCH(dim3(blocks, p.n_frames), kBlock, p.n_frames, "stats_generic_kernel");
   hipLaunchKernelGGL(stats_generic_kernel, dim3(blocks, p.n_frames), dim3(kBlock), stats_hist_lds_bytes(p.mode), stream, p);
 }
 
@@ -623,9 +626,11 @@ void launch_wb_finalize(int mode, const FrameStats* stats, const int* ccc_argmax
                         float simple_p, int simple_total, const float* ccc_row_best, int* ccc_argmax_out) {
   if (n_frames <= 0) return;
   if (mode == WB_FLOAT) {
+    RIP_LOG_LAUNCH(dim3(1), 256, n_frames, "wb_finalize_kernel");
     hipLaunchKernelGGL(wb_finalize_kernel, dim3(1), dim3(256), 0, stream, mode, stats, ccc_argmax, ccc_state, tabs, out, n_frames,
                        simple_hist, simple_p, simple_total, ccc_row_best, ccc_argmax_out);
   } else {
+    RIP_LOG_LAUNCH(dim3((n_frames + 63) / 64), 64, n_frames, "wb_finalize_kernel");
     hipLaunchKernelGGL(wb_finalize_kernel, dim3((n_frames + 63) / 64), dim3(64), 0, stream, mode, stats, ccc_argmax,
                        ccc_state, tabs, out, n_frames, simple_hist, simple_p, simple_total, nullptr, nullptr);
   }

@@ -152,6 +152,41 @@ class OutputPool:
         return arr
 
 
+class LaunchLog:
+    """The launch record of a pipeline handle (RawImagePipeline.launch_log): one line per kernel launch,
+    ``<kernel> fc=<0|1> grid=<x>,<y> block=<n> frames=<n>``."""
+
+    def __init__(self, pipe):
+        self._pipe = pipe
+        self.text = ""
+
+    def __enter__(self):
+        self._pipe._call("rip_debug_launch_log", 1)
+        return self
+
+    def __exit__(self, *exc):
+        self.text = self._pipe._launch_log_text()
+        self._pipe._call("rip_debug_launch_log", 0)
+        return False
+
+    def records(self):
+        """[{"name", "fc", "grid": (x, y), "block", "frames"}] in launch order (also inside the block)."""
+        out = []
+        for line in (self.text or self._pipe._launch_log_text()).splitlines():
+            name, rest = line.split(" fc=", 1)
+            f = dict(kv.split("=") for kv in ("fc=" + rest).split())
+            out.append({"name": name, "fc": int(f["fc"]), "grid": tuple(int(v) for v in f["grid"].split(",")),
+                        "block": int(f["block"]), "frames": int(f["frames"])})
+        return out
+
+    def names(self):
+        return [r["name"] for r in self.records()]
+
+    def keys(self):
+        """{(name, fc)} of the launches."""
+        return {(r["name"], r["fc"]) for r in self.records()}
+
+
 class RawImagePipeline:
     """Same surface as ``py_raw_image_pipeline.RawImagePipeline``.
 
@@ -782,6 +817,19 @@ class RawImagePipeline:
                    int(iv.shape[0]))
         keys = ("dense_items", "footprint_items", "row_pairs", "last_walked")
         return dict(zip(keys, [int(v) for v in info])), iv
+
+    def launch_log(self):
+        """Test hook (rip_debug_launch_log): ``with pipe.launch_log() as log:`` records every kernel launch the handle's
+        calls make inside the block; afterwards ``log.records()`` gives them as dicts and ``log.names()`` as the kernels'
+        names with their template arguments, e.g. ``chain_fast_kernel<7, 1, 512, false>``."""
+        return LaunchLog(self)
+
+    def _launch_log_text(self):
+        need = C.c_size_t(0)
+        self._lib.rip_debug_get_launch_log(self._h, None, C.c_size_t(0), C.byref(need))
+        buf = C.create_string_buffer(max(1, need.value))
+        self._call("rip_debug_get_launch_log", buf, C.c_size_t(len(buf)), C.byref(need))
+        return buf.value.decode()
 
     def set_tunable(self, name, value):
         """Launch tunable of this handle (rip_set_tunable: development / test hook; the library reads its environment

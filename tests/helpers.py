@@ -168,6 +168,22 @@ def assert_images_equal(got, ref, what="", tol=0):
     assert d.max() <= tol, "%s: max |diff| = %d on %d of %d values" % (what, d.max(), int((d > tol).sum()), d.size)
 
 
+# ---- which kernels ran (RawImagePipeline.launch_log) ---------------------------------------------------
+GENERIC_KERNELS = ("chain_generic_kernel", "remap_generic_kernel<?>", "stats_generic_kernel", "remap_vec4_kernel")
+
+
+def assert_launched(log, expected, forbidden=(), what=""):
+    """Every pattern of `expected` matches a kernel name of the launch log and no pattern of `forbidden` does.  Patterns are
+    fnmatch patterns over names such as ``chain_fast_kernel<7, 1, 512, false>``: ``?`` stands for one character."""
+    import fnmatch
+    names = log.names()
+    for pat in expected:
+        assert any(fnmatch.fnmatchcase(n, pat) for n in names), "%s: no launch of %s; launched: %s" % (what, pat, names)
+    for pat in forbidden:
+        hit = [n for n in names if fnmatch.fnmatchcase(n, pat)]
+        assert not hit, "%s: %s was launched; launched: %s" % (what, hit, names)
+
+
 # ---- debug stage dumps (raw_image_pipeline.hpp:143-186) ---------------------------------------------
 DUMP_NAMES = ("00_debayer", "01_flip", "02_white_balancing", "03_color_calibration", "04_gamma_correction",
               "05_vignetting_correction", "06_color_enhancer", "07_undistortion")

@@ -127,3 +127,33 @@ def test_copy_host_in_a_forked_child_copies_on_its_own_thread(rip_lib):
             raise AssertionError("the forked child hung in rip_copy_host")
         time.sleep(0.05)
     assert os.WIFEXITED(status) and os.WEXITSTATUS(status) == 0
+
+
+def test_launch_log_on_a_handle_without_a_device(rip_lib):
+    """rip_debug_launch_log / rip_debug_get_launch_log: a handle that launches nothing keeps an empty record; the getter
+    reports the size it needs (terminator included) and copies nothing into a buffer that is too small."""
+    from raw_image_pipeline_amd import RawImagePipeline
+    host = RawImagePipeline(False, "", "", "", device=-1)
+    with host.launch_log() as log:
+        host.set_gamma_correction(True)
+        assert log.names() == []
+    assert log.text == "" and log.records() == [] and log.keys() == set()
+    need = C.c_size_t(99)
+    assert rip_lib.rip_debug_get_launch_log(host._h, None, C.c_size_t(0), C.byref(need)) == 5   # RIP_ERR_CAPACITY
+    assert need.value == 1 and b"1 bytes" in rip_lib.rip_last_error(host._h)
+    buf = C.create_string_buffer(b"x", 4)
+    assert rip_lib.rip_debug_get_launch_log(host._h, buf, C.c_size_t(4), None) == 0 and buf.value == b""
+    assert rip_lib.rip_debug_launch_log(None, 1) == 1
+
+
+def test_launch_log_lines_are_parsed(rip_lib):
+    from raw_image_pipeline_amd import RawImagePipeline
+    log = RawImagePipeline(False, "", "", "", device=-1).launch_log()
+    log.text = ("raw16_tile_kernel<StagePacked<1>, true, 0, 1, 90> fc=0 grid=16,1 block=256 frames=3\n"
+                "demosaic_mht_pixel_kernel<unsigned short> fc=0 grid=9,3 block=256 frames=3\n"
+                "chain_fast_kernel<7, 1, 512, false> fc=1 grid=8,2 block=512 frames=3\n"
+                "map_prefix_kernel fc=0 grid=3,1 block=64 frames=0\n")
+    assert log.names() == ["raw16_tile_kernel<StagePacked<1>, true, 0, 1, 90>", "demosaic_mht_pixel_kernel<unsigned short>",
+                           "chain_fast_kernel<7, 1, 512, false>", "map_prefix_kernel"]
+    assert log.records()[2] == {"name": "chain_fast_kernel<7, 1, 512, false>", "fc": 1, "grid": (8, 2), "block": 512, "frames": 3}
+    assert ("chain_fast_kernel<7, 1, 512, false>", 1) in log.keys() and ("chain_fast_kernel<7, 1, 512, false>", 0) not in log.keys()

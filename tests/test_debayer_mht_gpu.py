@@ -9,7 +9,7 @@ import functools
 import numpy as np
 import pytest
 
-from helpers import DUMP_NAMES, assert_images_equal, cfg, configure, normalize_minmax, oracle_run, read_png
+from helpers import DUMP_NAMES, GENERIC_KERNELS, assert_images_equal, assert_launched, cfg, configure, normalize_minmax, oracle_run, read_png
 from mht_reference import flip, mht_reference, phase_of
 from raw_image_pipeline_amd import synth
 
@@ -164,9 +164,16 @@ def test_full_chain_batch_2448x2048(rip_lib, wb_method, fp_contract):
     tints = [(0.70, 1.00, 0.55), (0.55, 1.00, 0.80), (0.90, 0.95, 0.50)]
     frames = np.stack([synth.gen_frame(w, h, pattern, seed=60 + i, kind="scene", tint=tints[i]) for i in range(n)])
     images = np.stack([mht_reference(frames[i], pattern) for i in range(n)])
-    got = mht_pipe.apply_device(torch.from_numpy(frames).cuda(), pattern)
+    with mht_pipe.launch_log() as log:
+        got = mht_pipe.apply_device(torch.from_numpy(frames).cuda(), pattern)
     want = bgr_pipe.apply_device(torch.from_numpy(images).cuda(), "bgr8")
     torch.cuda.synchronize()
+    # the tile kernel writes the flipped MHT image, the colour chain (Lab + HSV stage set, 512 threads) of the chosen model and
+    # the ring remap follow; nothing falls back to a generic kernel
+    mode = {"grey_world": 1, "ccc": 2, "pca": 3, "simple": 4}[wb_method]
+    assert_launched(log, ["demosaic_mht_tile_kernel<0, 0, 180>", "chain_color_kernel<15, %d, 512>" % mode, "remap_ring_kernel<?, 3, false>"],
+                    GENERIC_KERNELS, "MHT full chain %s" % wb_method)
+    assert ("chain_color_kernel<15, %d, 512>" % mode, fp_contract) in log.keys(), log.text
     assert got.shape == want.shape
     for i in range(n):
         assert_images_equal(got[i].cpu().numpy(), want[i].cpu().numpy(), "%s fc%d frame %d" % (wb_method, fp_contract, i))

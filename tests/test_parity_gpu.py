@@ -5,7 +5,7 @@ an integer/IEEE restatement, so every test below in fact demands tol = 0."""
 import numpy as np
 import pytest
 
-from helpers import assert_images_equal, cfg, configure, oracle_run
+from helpers import GENERIC_KERNELS, assert_images_equal, assert_launched, cfg, configure, oracle_run
 from raw_image_pipeline_amd import RipAssertError, RipError, synth
 
 pytestmark = pytest.mark.gpu
@@ -16,9 +16,13 @@ TOL_INTERP = 0       # debayer, remap: north_star allows 1 LSB; the integer rest
 TOL_DECLARED = 0     # wb gains, colour matrix, hsv, vignetting: build declares 1 LSB; measured 0
 
 
-def run_both(pipe, O, c, frame, encoding, tol, ccc=None, what=""):
+def run_both(pipe, O, c, frame, encoding, tol, ccc=None, what="", launched=None, not_launched=()):
+    """launched / not_launched: kernel name patterns (helpers.assert_launched) the call must / must not have launched."""
     configure(pipe, c)
-    got = pipe.process(frame, encoding)
+    with pipe.launch_log() as log:
+        got = pipe.process(frame, encoding)
+    if launched is not None:
+        assert_launched(log, launched, not_launched, what)
     ref, enc = oracle_run(O, c, frame, encoding, ccc=ccc)
     assert pipe.last_encoding == enc
     assert_images_equal(got, ref, what, tol)
@@ -159,11 +163,28 @@ def test_undistortion_mono_and_map_size_differs_from_image(gpu_pipe, oracle):
     assert got.shape == (48, 64)
 
 
-@pytest.mark.parametrize("fov,stages,ring", [(0.6, 2, 1), (0.6, 4, 1), (1.0, 2, 1), (1.0, 3, 1), (1.0, 4, 1), (2.0, 2, 1),
-                                               (2.0, 3, 1), (3.6, 2, 1), (1.0, 2, 0), (2.0, 2, 0)])
+RING_CASES = [(0.6, 2, 1), (0.6, 4, 1), (1.0, 2, 1), (1.0, 3, 1), (1.0, 4, 1), (2.0, 2, 1), (2.0, 3, 1), (3.6, 2, 1), (1.0, 2, 0), (2.0, 2, 0)]
+# (fov, remap_ring) -> the kernel that gathers the 448 x 272 batch.  fov_scale widens the source rectangle of a 64 x 16 tile; the
+# plan's largest rectangle (three bytes per pixel, rows of whole 16-byte chunks) takes 2240 / 4928 / 11408 / 17024 / 47520 bytes at
+# 0.6 / 1.0 / 1.6 / 2.0 / 3.6, and the ring kernel holds 1, 2 or 4 chunks per lane: up to 4, 8 and 16 KiB.  Colour frames with
+# nothing to do before the undistortion are gathered as they lie.
+RING_KERNELS_BGR = {(0.6, 1): "remap_ring_kernel<1, 3, false>", (1.0, 1): "remap_ring_kernel<2, 3, false>", (1.6, 1): "remap_ring_kernel<4, 3, false>",
+                    (2.0, 1): "remap_tiled_kernel<0>", (3.6, 1): "remap_tiled_kernel<0>", (1.0, 0): "remap_tiled_kernel<2>", (2.0, 0): "remap_tiled_kernel<0>"}
+# Bayer frames with only the undistortion on run the demosaic inside the remap's tiles (rip_fused.hip), whose classes count the
+# chunks of the Bayer rectangle (100 / 203 / 280 at 0.6 / 1.0 / 1.3: PRE 1, 1, 2).  Where that kernel refuses -- two four-byte
+# colour images of the rectangle beside the ring exceed 60 KiB of LDS from 2.0 on, or the ring is switched off -- the fused chain
+# writes an intermediate image and the kernels above gather from it.
+RING_KERNELS_BAYER = {(0.6, 1): ["remap_bayer_ring_kernel<1, 0, 0>"], (1.0, 1): ["remap_bayer_ring_kernel<1, 0, 0>"],
+                      (1.3, 1): ["remap_bayer_ring_kernel<2, 0, 0>"],
+                      (2.0, 1): ["chain_fast_kernel<0, 0, 256, ?*>", "remap_tiled_kernel<0>"], (3.6, 1): ["chain_fast_kernel<0, 0, 256, ?*>", "remap_tiled_kernel<0>"],
+                      (1.0, 0): ["chain_fast_kernel<0, 0, 256, ?*>", "remap_tiled_kernel<2>"], (2.0, 0): ["chain_fast_kernel<0, 0, 256, ?*>", "remap_tiled_kernel<0>"]}
+
+
+@pytest.mark.parametrize("fov,stages,ring", RING_CASES + [(1.3, 3, 1)])
 def test_undistortion_batch_through_the_lds_ring(gpu_pipe, oracle, monkeypatch, fov, stages, ring):
-    """The tiled remap streams the frames of a batch through an LDS ring (LDS-DMA, `stages` buffers).  fov_scale
-    widens the source rectangle of a tile: 1 chunk per lane (0.6), 2 (1.0), 4 (2.0), then the unpipelined fallback kernel (3.6)."""
+    """The remap streams the frames of a batch through an LDS ring (LDS-DMA, `stages` buffers).  A Bayer batch with only the
+    undistortion on never reaches remap_ring_kernel<PRE, 3>: it takes the kernel that demosaics inside the tiles, or the fused
+    chain and the unpipelined kernel (RING_KERNELS_BAYER).  The bgr8 twin below runs remap_ring_kernel at every PRE."""
     import torch
     gpu_pipe.set_tunable("remap_stages", stages)
     gpu_pipe.set_tunable("remap_ring", ring)
@@ -171,21 +192,47 @@ def test_undistortion_batch_through_the_lds_ring(gpu_pipe, oracle, monkeypatch, 
     c = cfg(undistort=True, cam=synth.camera_model(w, h), fov_scale=fov)
     configure(gpu_pipe, c)
     frames = np.stack([synth.gen_frame(w, h, "bayer_grbg8", seed=300 + i, kind="uniform") for i in range(n)])
-    out = gpu_pipe.apply_device(torch.from_numpy(frames).cuda(), "bayer_grbg8")
-    torch.cuda.synchronize()
+    with gpu_pipe.launch_log() as log:
+        out = gpu_pipe.apply_device(torch.from_numpy(frames).cuda(), "bayer_grbg8")
+        torch.cuda.synchronize()
+    assert_launched(log, RING_KERNELS_BAYER[(fov, ring)], GENERIC_KERNELS, "Bayer batch fov %g ring %d" % (fov, ring))
     out = out.cpu().numpy()
     for i in range(n):
         ref, _ = oracle_run(oracle, c, frames[i], "bayer_grbg8")
         assert_images_equal(out[i], ref, "ring frame %d (fov %g, %d stages)" % (i, fov, stages))
 
 
+@pytest.mark.parametrize("fov,stages,ring", RING_CASES + [(1.6, 2, 1), (1.6, 4, 1)])
+def test_undistortion_batch_of_colour_frames_through_the_lds_ring(gpu_pipe, oracle, fov, stages, ring):
+    """The bgr8 twin of the test above: the ring kernel of three-byte pixels with 1 chunk per lane (0.6), 2 (1.0) and 4 (1.6), then
+    the unpipelined kernel (2.0, 3.6), and the register-pipelined one with the ring off."""
+    import torch
+    gpu_pipe.set_tunable("remap_stages", stages)
+    gpu_pipe.set_tunable("remap_ring", ring)
+    w, h, n = 448, 272, 7
+    c = cfg(undistort=True, cam=synth.camera_model(w, h), fov_scale=fov)
+    configure(gpu_pipe, c)
+    rng = np.random.default_rng(310)
+    frames = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
+    with gpu_pipe.launch_log() as log:
+        out = gpu_pipe.apply_device(torch.from_numpy(frames).cuda(), "bgr8")
+        torch.cuda.synchronize()
+    assert_launched(log, [RING_KERNELS_BGR[(fov, ring)]], GENERIC_KERNELS + ("chain_*",), "bgr8 batch fov %g ring %d" % (fov, ring))
+    records = [r for r in log.records() if r["name"] == RING_KERNELS_BGR[(fov, ring)]]
+    assert len(records) == 1 and records[0]["frames"] == n and records[0]["block"] == 256, records
+    out = out.cpu().numpy()
+    for i in range(n):
+        ref, _ = oracle_run(oracle, c, frames[i], "bgr8")
+        assert_images_equal(out[i], ref, "bgr8 ring frame %d (fov %g, %d stages)" % (i, fov, stages))
+
+
 DEAL_SWEEP = [(0, 0, 0), (1, 1, 1), (2, 2, 2), (5, 3, 5), (7, 1, 3), (64, 9, 0), (3, 0, 4), (0, 1, 16)]  # chain_deal, remap_deal, remap_frames
 
 
-def sweep_the_deals(pipe, O, c, frames, encoding, what):
+def sweep_the_deals(pipe, O, c, frames, encoding, what, launched=None, never=()):
     """The batch under the default deals against the oracle (last frame), then byte-identical under every entry of DEAL_SWEEP.
     Every call writes into a tensor filled with a sentinel beforehand: a tile or chunk no workgroup took must not pass on what
-    an earlier call left in recycled memory."""
+    an earlier call left in recycled memory.  launched / never: kernel name patterns (helpers.assert_launched) of every run."""
     import torch
     n = len(frames)
     configure(pipe, c)
@@ -204,7 +251,11 @@ def sweep_the_deals(pipe, O, c, frames, encoding, what):
         pipe.set_tunable("chain_deal", chain_deal)
         pipe.set_tunable("remap_deal", remap_deal)
         pipe.set_tunable("remap_frames", frames_per_visit)
-        assert np.array_equal(run(), base), "chain_deal %d remap_deal %d frames %d changes the image at %s" % (chain_deal, remap_deal, frames_per_visit, what)
+        with pipe.launch_log() as log:
+            got = run()
+        assert np.array_equal(got, base), "chain_deal %d remap_deal %d frames %d changes the image at %s" % (chain_deal, remap_deal, frames_per_visit, what)
+        if launched is not None:   # the sweep really runs the kernel it is meant for, under every deal
+            assert_launched(log, launched, GENERIC_KERNELS + tuple(never), "%s remap_deal %d" % (what, remap_deal))
     return dev
 
 
@@ -248,7 +299,8 @@ def test_the_deals_in_the_fused_remap_and_the_mono_ring(rip_lib, oracle, size, n
     pipe = RawImagePipeline(False, "", "", "", device=0)
     c = cfg(flip=True, flip_angle=180, wb=True, wb_method="grey_world", cc=True, gamma=True, gamma_k=0.8, undistort=True, cam=cam)
     frames = np.stack([synth.gen_frame(w, h, "bayer_rggb8", seed=900 + i, kind="scene") for i in range(n)])
-    dev = sweep_the_deals(pipe, oracle, c, frames, "bayer_rggb8", "fused remap %s" % (size,))
+    dev = sweep_the_deals(pipe, oracle, c, frames, "bayer_rggb8", "fused remap %s" % (size,),
+                          launched=["remap_bayer_ring_kernel<?, 3, 1>"] if w % 16 == 0 else ["chain_fast_kernel<3, 1, 256, ?*>", "remap_ring_kernel<?, 3, false>"])
     if w % 16 == 0:  # every size of the sweep but 1000 x 752: one fused kernel, the chain is never launched
         for remap_deal in (0, 3):
             pipe.set_tunable("remap_deal", remap_deal)
@@ -262,7 +314,16 @@ def test_the_deals_in_the_fused_remap_and_the_mono_ring(rip_lib, oracle, size, n
     c = cfg(flip=True, flip_angle=180, gamma=True, gamma_k=0.8, undistort=True, cam=cam)
     rng = np.random.default_rng(w + n)
     frames = np.stack([rng.integers(0, 256, (h, w), dtype=np.uint8) for i in range(n)])
-    sweep_the_deals(pipe, oracle, c, frames, "mono8", "mono8 ring %s" % (size,))
+    sweep_the_deals(pipe, oracle, c, frames, "mono8", "mono8 ring %s" % (size,), launched=["remap_ring_kernel<?, 1, true>"] if w % 16 == 0 else ["chain_mono_kernel", "remap_ring_kernel<?, 1, false>"],
+                    never=("chain_*",) if w % 16 == 0 else ())
+    if w * h > 640 * 482:
+        return
+    # debayer + undistortion only: the same kernel with no per-pixel stage between the demosaic and the gather
+    pipe = RawImagePipeline(False, "", "", "", device=0)
+    c = cfg(undistort=True, cam=cam)
+    frames = np.stack([synth.gen_frame(w, h, "bayer_rggb8", seed=940 + i, kind="uniform") for i in range(n)])
+    sweep_the_deals(pipe, oracle, c, frames, "bayer_rggb8", "debayer + undistortion %s" % (size,), launched=["remap_bayer_ring_kernel<?, 0, 0>"],
+                    never=("chain_*",))
 
 
 @pytest.mark.parametrize("size,balance,fov", [((2448, 2048), 0.0, 1.0), ((1920, 1200), 1.0, 0.8), ((450, 270), 0.5, 3.6), ((131, 97), 1.0, 0.6)])
@@ -359,9 +420,17 @@ def test_full_chain_on_colour_input(gpu_pipe, oracle, encoding, wb, size):
     img = synth.gen_scene_bgr(w, h, seed=31)
     cam = synth.camera_model(w, h)
     c = full_chain_cfg(w, h, wb_method=wb, ce=True, ce_sat=1.3, cam=cam)
-    run_both(gpu_pipe, oracle, c, img, encoding, 0, what="colour input %s %s %s" % (encoding, wb, size))
+    mode = {"grey_world": 1, "pca": 3}[wb]
+    if w % 4 == 0:   # four pixels per lane
+        first = ["stats_color_kernel", "chain_color_kernel<15, %d, 512>" % mode, "remap_ring_kernel<?, 3, false>"]
+        second, never = ["stats_color_kernel", "chain_color_kernel<3, %d, 256>" % mode], GENERIC_KERNELS
+    else:            # one pixel per lane, whatever the pitch; the remap's vector stores need a width that is a multiple of 4 too
+        first = ["stats_generic_kernel", "chain_generic_kernel", "remap_generic_kernel<3>"]
+        second, never = ["stats_generic_kernel", "chain_generic_kernel"], ("chain_color_kernel*", "stats_color_kernel", "remap_ring_kernel*")
+    run_both(gpu_pipe, oracle, c, img, encoding, 0, what="colour input %s %s %s" % (encoding, wb, size), launched=first, not_launched=never)
     c2 = full_chain_cfg(w, h, wb_method=wb, flip=False, undistort=False, vig=False)
-    run_both(gpu_pipe, oracle, c2, img, encoding, 0, what="colour input no-vignette %s %s %s" % (encoding, wb, size))
+    run_both(gpu_pipe, oracle, c2, img, encoding, 0, what="colour input no-vignette %s %s %s" % (encoding, wb, size), launched=second,
+             not_launched=never)
 
 
 @pytest.mark.parametrize("wb", ["grey_world", "pca", "simple", "none"])
@@ -452,7 +521,9 @@ def test_full_chain_full_size_2448x2048(gpu_pipe, oracle):
     """BASELINE configs[1] at its real size, against the oracle (a few seconds of CPU)."""
     w, h = 2448, 2048
     frame = synth.gen_frame(w, h, "bayer_rggb8", seed=1000, kind="scene")
-    run_both(gpu_pipe, oracle, full_chain_cfg(w, h), frame, "bayer_rggb8", 0, what="full chain 2448x2048")
+    # a host frame keeps its taps: the chain writes the whole intermediate image (no item list), the ring remap gathers from it
+    run_both(gpu_pipe, oracle, full_chain_cfg(w, h), frame, "bayer_rggb8", 0, what="full chain 2448x2048",
+             launched=["stats_fast_kernel<1>", "chain_fast_kernel<7, 1, 512, false>", "remap_ring_kernel<?, 3, false>"], not_launched=GENERIC_KERNELS)
 
 
 def test_device_batch_equals_per_frame_and_respects_pitch(gpu_pipe, oracle):
@@ -510,7 +581,8 @@ def test_config1_640x480_debayer_and_default_gamma(gpu_pipe, oracle):
     CPU path) only -- the plumbing case, through the same C-ABI call a reference caller makes."""
     frame = synth.gen_frame(640, 480, "bayer_rggb8", seed=0, kind="scene")
     c = cfg(gamma=True, gamma_method="default", gamma_k=0.8)
-    got = run_both(gpu_pipe, oracle, c, frame, "bayer_rggb8", TOL_EXACT, what="config 1")
+    got = run_both(gpu_pipe, oracle, c, frame, "bayer_rggb8", TOL_EXACT, what="config 1",
+                   launched=["chain_fast_kernel<2, 0, 256, false>"], not_launched=GENERIC_KERNELS)
     assert got.shape == (480, 640, 3) and gpu_pipe.last_encoding == "bgr8"
 
 
@@ -529,8 +601,11 @@ def test_config3_full_size_1920x1200_ccc_batch(gpu_pipe, oracle):
     gpu_pipe.reset_white_balance_temporal_consistency()
     frames = np.stack([synth.gen_frame(w, h, "bayer_gbrg8", seed=3000 + i, kind="scene", tint=(0.70 + 0.03 * i, 1.0, 0.55))
                        for i in range(n)])
-    out = gpu_pipe.apply_device(torch.from_numpy(frames).cuda(), "bayer_gbrg8")
-    torch.cuda.synchronize()
+    with gpu_pipe.launch_log() as log:
+        out = gpu_pipe.apply_device(torch.from_numpy(frames).cuda(), "bayer_gbrg8")
+        torch.cuda.synchronize()
+    assert_launched(log, ["ccc_hist_kernel", "ccc_fft_rows16_kernel<4>", "wb_finalize_kernel", "chain_fast_kernel<8, 2, 256, false>"],
+                    GENERIC_KERNELS, "config3")
     out = out.cpu().numpy()
     for i in range(n):
         ref, _ = oracle_run(oracle, c, frames[i], "bayer_gbrg8", ccc=occ)
@@ -632,7 +707,14 @@ def test_config5_full_size_3840x2160_debayer_undistort(gpu_pipe, oracle):
     w, h = 3840, 2160
     c = cfg(undistort=True, cam=synth.camera_model(w, h))
     frame = synth.gen_frame(w, h, "bayer_rggb8", seed=5, kind="scene")
-    run_both(gpu_pipe, oracle, c, frame, "bayer_rggb8", TOL_INTERP, what="config5 3840x2160")
+    run_both(gpu_pipe, oracle, c, frame, "bayer_rggb8", TOL_INTERP, what="config5 3840x2160",
+             launched=["chain_fast_kernel<0, 0, 256, false>", "remap_ring_kernel<?, 3, false>"], not_launched=GENERIC_KERNELS)
+    # the same frame as a resident batch of one, without taps: the remap's tiles demosaic their own source rectangles
+    import torch
+    with gpu_pipe.launch_log() as log:
+        out = gpu_pipe.apply_device(torch.from_numpy(frame[None]).cuda(), "bayer_rggb8").cpu().numpy()
+    assert_launched(log, ["remap_bayer_ring_kernel<?, 0, 0>"], GENERIC_KERNELS + ("chain_*",), "config5 resident")
+    assert np.array_equal(out[0], gpu_pipe.process(frame, "bayer_rggb8"))
 
 
 @pytest.mark.parametrize("pattern", PATTERNS)
