@@ -140,6 +140,7 @@ class RawImagePipeline {
   // copy), valid until the next collect*() on this object.
   uint64_t submit(const Mat& image, const std::string& encoding) {
     uint64_t ticket = 0;
+    need_u8_output();
     check(rip_submit(h_, detail::bytes(image), image.rows, pixel_cols(image, encoding), image.channels(), detail::step_of(image), encoding.c_str(), &ticket));
     return ticket;
   }
@@ -150,6 +151,7 @@ class RawImagePipeline {
   // ticket is collected.
   uint64_t submitTo(const Mat& image, const std::string& encoding, Mat& out, Mat* tap_debayered = nullptr, Mat* tap_color = nullptr) {
     uint64_t ticket = 0;
+    need_u8_output();
     const Mat* tap = tap_debayered ? tap_debayered : tap_color;
     check(rip_submit_to(h_, detail::bytes(image), image.rows, pixel_cols(image, encoding), image.channels(), detail::step_of(image), encoding.c_str(),
                         detail::bytes(out), (size_t)out.rows * out.cols * out.channels(), tap_debayered ? detail::bytes(*tap_debayered) : nullptr,
@@ -220,6 +222,17 @@ class RawImagePipeline {
     packed_width_ = width;
   }
   int getDebayerPackedWidth() const { return packed_width_; }
+
+  // not in the reference: the output stage (rip.h rip_set_output_format / rip_set_output_normalization).  "rgb8" and "mono8"
+  // flow through apply / process / submit / submitTo / collect as CV_8UC3 / CV_8UC1 Mats.  The planar float formats
+  // ("rgb_chw_f32", ...) can be set and read back here, but these uint8 Mats cannot carry their tensors: the frame calls of this
+  // class throw std::invalid_argument while one is set -- use the C interface (handle(), rip_apply / rip_apply_device) for them.
+  void setOutputFormat(const std::string& name) { check(rip_set_output_format(h_, name.c_str())); }
+  std::string getOutputFormat() const { return str(&rip_get_output_format); }
+  void setOutputNormalization(double divisor, const std::vector<double>& mean, const std::vector<double>& std_dev) {
+    if (mean.size() != 3 || std_dev.size() != 3) throw std::invalid_argument("setOutputNormalization: mean and std take 3 values");
+    check(rip_set_output_normalization(h_, divisor, mean.data(), std_dev.data()));
+  }
 
   void setFlip(bool enabled) { check(rip_set_flip(h_, enabled)); }
   void setFlipAngle(int angle) { check(rip_set_flip_angle(h_, angle)); }
@@ -347,7 +360,15 @@ class RawImagePipeline {
     if (!bits) return in.cols;
     return packed_width_ ? packed_width_ : (int)(8 * (long long)in.cols / bits);
   }
+  // the frame calls return uint8 Mats: the planar float output formats go through the C interface
+  void need_u8_output() const {
+    const std::string f = getOutputFormat();
+    if (f.find("_chw_") != std::string::npos)
+      throw std::invalid_argument("output format [" + f + "] is a planar float tensor, which the uint8 Mats of this class cannot carry: "
+                                  "use the C interface (rip_apply / rip_apply_device on handle())");
+  }
   Mat run(const Mat& in, std::string& encoding) {
+    need_u8_output();
     int rows = 0, cols = 0, cn = 0;
     char enc[32] = {0};
     const int in_cols = pixel_cols(in, encoding);

@@ -105,6 +105,12 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
 /* Geometry/encoding rip_apply would produce for such an input (no device work). */
 rip_status rip_query_output(rip_pipeline* p, int rows, int cols, int channels, const char* encoding,
                             int* out_rows, int* out_cols, int* out_channels, char encoding_out[32]);
+/* Size of that result: *bytes = the tightly packed frame rip_apply / rip_submit_to / rip_collect check their capacities against
+ * (out_rows * out_cols * out_channels * *elem_bytes), *elem_bytes = bytes per delivered element (1; 2 for bgr16 and the f16 / bf16
+ * formats, 4 for f32), *planar = 1 for the planar output formats (rip_set_output_format), else 0.  Any pointer may be null.  Fails
+ * where rip_query_output fails.  Works on RIP_DEVICE_NONE handles. */
+rip_status rip_query_output_bytes(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, size_t* bytes,
+                                  int* elem_bytes, int* planar);
 /* Geometry of the two tap images for such an input: the post-flip debayered image (flip.cpp:60-62, what
  * getDistDebayeredImage returns) and the pre-undistortion colour image (undistortion.cpp:247-249) share it;
  * rows * cols * channels tightly packed bytes per frame is what rip_apply_device writes to each tap buffer. */
@@ -275,6 +281,46 @@ rip_status rip_get_debayer_16bit_range(const rip_pipeline* p, int* black, int* w
  * RIP_ERR_INVALID_ARGUMENT on an unknown value and leaves the parameters as they were. */
 rip_status rip_set_debayer_method(rip_pipeline* p, const char* method);
 rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
+/* Extension beyond the reference: the output stage.  The pipeline's final image F is 8-bit with channels 0, 1, 2 = B, G, R;
+ * one exact per-pixel conversion behind the last module turns it into what rip_apply / rip_apply_device / rip_submit /
+ * rip_collect deliver:
+ *   native (default)   F itself: exactly the result without this extension, no extra launch, no extra memory
+ *   rgb8               F with the channels of every pixel reversed; uint8, interleaved, 3 channels
+ *   mono8              (3735 B + 19235 G + 9798 R + 16384) >> 15 -- OpenCV 4's 15-bit BGR2GRAY restated (PARITY.md; grey in gives
+ *                      grey out, the primaries give R 76, G 150, B 29); uint8, 1 channel
+ *   rgb_chw_f32 / rgb_chw_f16 / rgb_chw_bf16   planes R, G, B of T_c[v] (rip_set_output_normalization); 4 / 2 / 2 bytes per
+ *   bgr_chw_f32 / bgr_chw_f16 / bgr_chw_bf16   planes B, G, R                       element; planar, 3 planes of out_rows x out_cols
+ * A format other than native needs a three-channel 8-bit pipeline result (Bayer 8-bit, 16-bit with a range, packed, bgr8 and rgb8
+ * frames).  mono8 on a one-channel 8-bit result is the identity (no kernel); every other format on a one-channel result, and every
+ * format other than native on a bgr16 result, fails the frame call and rip_query_output with RIP_ERR_INVALID_ARGUMENT: nothing is
+ * enqueued and the ccc / Kalman state does not advance.
+ * Geometry: the frame calls and rip_query_output report out_rows, out_cols, out_channels (3, or 1 for mono8) and the format's name
+ * as encoding_out; rip_query_output_bytes gives the bytes.  rip_apply_device: for the interleaved formats out_step (0 = tight) and
+ * out_frame_stride mean what they mean without a format; for the planar formats out_step is the row pitch in BYTES inside a plane
+ * (0 = out_cols * element size), plane c of a frame starts at c * out_step * out_rows, and out_frame_stride is 0 for
+ * 3 * out_step * out_rows or at least that -- a contiguous [n, 3, R, C] tensor is (0, 0).  d_out, out_step and out_frame_stride
+ * must be multiples of the element size; the limits of 16 MiB per row and 4 GiB per frame apply to the converted frame.  Nothing
+ * is written beyond out_cols elements of a row: row padding, gaps between planes and between frames stay untouched.
+ * Unchanged by the format: the DEBAYERED and COLOR taps and their getters, rip_get_white_balance_info, rip_get_ccc_track and the
+ * debug dumps (written from F).  RIP_IMAGE_PROCESSED reports an empty image under a format other than native, as it does for
+ * bgr16 results: the delivered buffer is the result.
+ * Cost: one more launch per batch (a memory-rate pass: 3 bytes read, up to 12 written per pixel), and n_frames x out_rows x
+ * out_cols x 3 bytes of device memory (rows padded to 16 bytes) kept by the handle for F, as for "mht".
+ * Unknown names: RIP_ERR_INVALID_ARGUMENT listing the names, nothing changed.  Works on RIP_DEVICE_NONE handles.  Params YAML:
+ * `output: format:` (default "native"), `output: divisor:`, `output: mean: [3]`, `output: std: [3]`; rip_load_params re-creates
+ * the modules, so absent keys mean the defaults, and fails with RIP_ERR_INVALID_ARGUMENT on an invalid value, leaving the
+ * parameters as they were. */
+rip_status rip_set_output_format(rip_pipeline* p, const char* name);
+rip_status rip_get_output_format(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
+/* Normalisation of the planar output formats; mean and std hold 3 values in the order of the format's planes.  Defaults:
+ * divisor 255, mean (0, 0, 0), std (1, 1, 1); divisor 1 gives the raw values.  For plane c and channel value v in 0..255 the
+ * delivered element is the table entry T_c[v]: y = (v / divisor - mean_c) / std_c evaluated in double with every operation
+ * rounded, T_c[v] = (float)y; the f16 and bf16 formats deliver that float rounded to nearest even (overflow to +-inf and
+ * subnormals as IEEE 754 says).  The tables are built on the host and uploaded when the format or the normalisation changes.
+ * A non-finite divisor / mean / std, divisor == 0 or a std_c == 0: RIP_ERR_INVALID_ARGUMENT, nothing changed.  Works on
+ * RIP_DEVICE_NONE handles. */
+rip_status rip_set_output_normalization(rip_pipeline* p, double divisor, const double mean[3], const double std[3]);
+rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, double mean[3], double std[3]); /* any pointer may be null */
 rip_status rip_set_flip(rip_pipeline* p, int enabled);                            /* hpp:69 */
 rip_status rip_set_flip_angle(rip_pipeline* p, int angle);                        /* hpp:70 */
 rip_status rip_set_white_balance(rip_pipeline* p, int enabled);                   /* hpp:72 */
@@ -390,7 +436,7 @@ rip_status rip_debug_plan_info(rip_pipeline* p, int src_rows, int src_cols, int 
  * batches, the lazily built maps / plan / tables; not the re-runs of the debug stage dumps, not the probes) appends one line
  *   <kernel> fc=<0|1> grid=<x>,<y> block=<threads> frames=<n>
  * <kernel>: the kernel's name with its template arguments as a demangler prints them, without namespaces, e.g.
- * "chain_fast_kernel<7, 1, 512, false>"; fc: the floating-point model it was compiled under (rip_set_fp_contraction; the
+ * "chain_fast_kernel<7, 1, 512, false>" (the output stage: "output_convert_kernel<RgbChwF16>", one launch per batch slice); fc: the floating-point model it was compiled under (rip_set_fp_contraction; the
  * twins share a name); frames: the batch the launch serves (0 for the map, plan and table builders).  enable != 0 clears the
  * log and switches it on, 0 switches it off and keeps the text.  Off, a launch pays one null test. */
 rip_status rip_debug_launch_log(rip_pipeline* p, int enable);
@@ -412,6 +458,10 @@ rip_status rip_debug_raw16_narrow(int black, int white, const uint16_t* in, uint
  * bytes, 0 = tight) into rows x cols uint16 samples, tightly packed, on the host with the extract functions the kernel's byte
  * path uses.  Width rule and pitch check as for rip_apply.  No device, no handle. */
 rip_status rip_debug_unpack(const char* encoding, const uint8_t* in, size_t step, int rows, int cols, uint16_t* out);
+/* Test hook: the table of a planar output format (rip_set_output_normalization) for the given normalisation: 3 x 256 elements
+ * of the format's element type (float, or the uint16 bit patterns of f16 / bf16), plane-major, written to out.  rgb8, mono8 and
+ * native have no table: RIP_ERR_INVALID_ARGUMENT, as for an unknown name or an invalid normalisation.  No device, no handle. */
+rip_status rip_debug_output_table(const char* name, double divisor, const double mean[3], const double std[3], void* out);
 /* Test hook for the debug dumps: writes image (rows x cols x channels bytes, channels 1 or 3 = BGR) to path as the PNG
  * writer of rip_set_debug does, after the reference's min-max normalisation when normalize != 0.  No device needed;
  * p may be NULL. */

@@ -1,4 +1,5 @@
-"""Builds librip_hip.so (the C-ABI library, include/rip.h) for gfx950 with hipcc.
+"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion librip_out_hip.so (the kernels of the output
+stage, csrc/rip_output.hip) for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
@@ -10,7 +11,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", os.path.join("..", "..", "include", "rip.h")]
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_output.hpp", os.path.join("..", "..", "include", "rip.h")]
+# The companion library: the output stage's kernels (rip_set_output_format) and their one launch function (rip_output.hpp).  A
+# library of its own so that librip_hip.so's kernel table stays what tests/variant_cases.py closes over; the companion's table
+# is closed by tests/output_variant_cases.py.  librip_hip.so -- every build of it: the default one, the sanitizer build and the
+# A/B variants under variants/ -- links against this one file and finds it through its $ORIGIN rpath.
+OUT_COMPANION = os.path.join(HERE, "librip_out_hip.so")
+COMPANION_SOURCES = ["rip_output.hip"]
+COMPANION_HEADERS = ["rip_output.hpp"]
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -29,12 +37,46 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
+def companion_up_to_date():
+    if not os.path.exists(OUT_COMPANION):
+        return False
+    t = os.path.getmtime(OUT_COMPANION)
+    deps = [os.path.join(CSRC, s) for s in COMPANION_SOURCES + COMPANION_HEADERS] + [os.path.abspath(__file__)]
+    return all(os.path.getmtime(d) <= t for d in deps)
+
+
 def up_to_date():
-    if not os.path.exists(OUT):
+    if not os.path.exists(OUT) or not companion_up_to_date():
         return False
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return all(os.path.getmtime(d) <= t for d in deps)
+
+
+def build_companion(force=False, verbose=False):
+    """librip_out_hip.so, next to librip_hip.so.  Its interface is rip_output.hpp alone, so a rebuild of it does not ask for a
+    relink of the libraries that use it."""
+    if not force and companion_up_to_date():
+        return OUT_COMPANION
+    bdir = os.path.join(HERE, "build_out")
+    os.makedirs(bdir, exist_ok=True)
+    objs = []
+    for s in COMPANION_SOURCES:
+        obj = os.path.join(bdir, os.path.splitext(s)[0] + ".o")
+        cmd = [hipcc()] + FLAGS + os.environ.get("RIP_EXTRA_FLAGS", "").split() + ["-x", "hip", "-c", os.path.join(CSRC, s), "-o", obj]
+        if verbose:
+            print(" ".join(cmd))
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc failed on %s:\n%s" % (s, r.stdout))
+        if verbose and r.stdout.strip():
+            print(r.stdout)
+        objs.append(obj)
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname," + os.path.basename(OUT_COMPANION), "-o", OUT_COMPANION] + objs
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("link failed:\n" + r.stdout)
+    return OUT_COMPANION
 
 
 # --asan: the HOST layer (rip_host.cpp, rip_api.cpp: YAML reader, loaders, table builders, frame ring, copy threads) under
@@ -64,10 +106,11 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
     out=".../variants/x.so"; the default build takes no extra flags beyond $RIP_EXTRA_FLAGS."""
     if asan:
         out, tag = out or ASAN_OUT, tag or "_asan"
-        if not force and os.path.exists(out) and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
+        if not force and os.path.exists(out) and companion_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
             return out
     if out is None and not force and up_to_date():
         return OUT
+    build_companion(verbose=verbose)  # every build of librip_hip.so links against it; `force` is about the library asked for
     out = out or OUT
     objs = []
     procs = []
@@ -89,7 +132,9 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
             raise RuntimeError("hipcc failed on %s:\n%s" % (s, log))
         if verbose and log.strip():
             print(log)
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
+    # the companion is found next to the library ($ORIGIN) or one directory up (variants/*.so)
+    companion = ["-L" + HERE, "-l:" + os.path.basename(OUT_COMPANION), "-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("link failed:\n" + r.stdout)

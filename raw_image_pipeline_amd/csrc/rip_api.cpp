@@ -25,6 +25,7 @@
 
 #include "rip_host.hpp"
 #include "rip_kernels.hpp"
+#include "rip_output.hpp"
 #include "rip_unpack.hpp"
 
 namespace {
@@ -152,7 +153,15 @@ struct Plan {
   int wb_mode = rip::WB_NONE;
   int stage_bits = 0;
   std::string encoding_out;
+  // the output stage (rip_set_output_format; filled in by apply_output_format, everything above describes the pipeline's own image)
+  bool fmt_active = false;        // a format other than "native" is set
+  int out_fmt = rip::OUT_NATIVE;  // the conversion that runs behind the last kernel; OUT_NATIVE: none (mono8 of a one-channel image included)
+  int dl_channels = 3;            // what the frame calls deliver: channels (planes), bytes per element, planar or interleaved
+  int dl_elem_bytes = 1;
+  bool dl_planar = false;
 };
+// tightly packed bytes of one delivered frame
+size_t delivered_bytes(const Plan& pl) { return (size_t)pl.out_rows * pl.out_cols * pl.dl_channels * (size_t)pl.dl_elem_bytes; }
 
 // payload bytes of one input row: ceil(cols * B / 8) for a packed format, cols * channels samples otherwise
 size_t row_bytes(const Plan& pl, int cols, int channels) {
@@ -401,6 +410,11 @@ struct rip_pipeline {
   // per-batch scratch
   DevBuf d_stats, d_wb, d_hist, d_work, d_rowbest, d_argmax, d_mid;
   DevBuf d_mht;  // the Malvar-He-Cutler image of a batch when no DEBAYERED tap holds it (run_batch)
+  // output stage (rip_set_output_format): the pipeline's final image of a batch slice in front of the converter (rows padded to
+  // 16 bytes), and the planar formats' 3 x 256 table, rebuilt and uploaded when the format or the normalisation changes
+  DevBuf d_fmt, d_out_tab;
+  std::vector<uint8_t> h_out_tab;
+  bool out_tab_dirty = true;
   // compiled remap plan (tiled LDS gather), rebuilt when the maps or the source geometry change
   rip::RemapPlan plan;
   DevBuf d_plan_words, d_plan_tiles, d_plan_border, d_plan_counters;
@@ -462,7 +476,7 @@ struct rip_pipeline {
     if (dl_stream) (void)hipStreamDestroy(dl_stream);
     for (DevBuf* b : {&d_tabs, &d_vig_image, &d_map, &d_map_ckpt, &d_filter_fft, &d_bias_fft, &d_accum, &d_ccc_state, &d_geom, &d_stats, &d_wb,
                       &d_hist, &d_work, &d_rowbest, &d_argmax, &d_mid, &d_in, &d_out, &d_tap_deb, &d_tap_col, &d_vig, &d_plan_words,
-                      &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg, &d_mht})
+                      &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg, &d_mht, &d_fmt, &d_out_tab})
       b->release();
   }
 };
@@ -961,6 +975,29 @@ Plan make_plan(const rip_pipeline* p, int rows, int cols, int channels, const st
   return pl;
 }
 
+// The output stage on top of a plan (rip_set_output_format): what the frame calls and rip_query_output deliver.  The taps, the
+// debug dumps and rip_query_taps stay with make_plan's image.  Throws before anything is enqueued where the format does not apply.
+void apply_output_format(const rip_pipeline* p, Plan& pl) {
+  pl.dl_channels = pl.channels;
+  pl.dl_elem_bytes = pl.out_elem_bytes;
+  const int fmt = rip::output_format_id(p->m.out_format);
+  if (fmt == rip::OUT_NATIVE) return;
+  pl.fmt_active = true;
+  if (pl.out_elem_bytes != 1)
+    throw InvalidArgument("output format [" + p->m.out_format + "] needs an 8-bit pipeline result; this frame gives bgr16 (set a 16-bit range, or the format 'native')");
+  if (pl.channels == 1) {
+    if (fmt != rip::OUT_MONO8)
+      throw InvalidArgument("output format [" + p->m.out_format + "] needs a three-channel pipeline result; this frame gives one channel ('mono8' and 'native' apply)");
+    pl.encoding_out = "mono8";  // the identity: no kernel
+    return;
+  }
+  pl.out_fmt = fmt;
+  pl.dl_channels = rip::output_format_channels(fmt);
+  pl.dl_elem_bytes = rip::output_format_elem_bytes(fmt);
+  pl.dl_planar = rip::output_format_planar(fmt);
+  pl.encoding_out = p->m.out_format;
+}
+
 // Enqueues the whole chain for n frames.  d_out rows of out_step bytes.  Taps may be null.
 // reuse_wb: the white-balance gains of the previous launch (same frames) are applied again and no estimator runs -- the
 // debug stage dumps re-run prefixes of the chain without advancing the ccc Kalman state.
@@ -1443,6 +1480,71 @@ void run_batch(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_s
   (void)stats_cleared_here;
 }
 
+// pitch of the staging image in front of the converter: every source row starts 16-byte aligned
+size_t fmt_pitch(const Plan& pl) { return ((size_t)pl.out_cols * 3 + 15) & ~(size_t)15; }
+
+// The planar formats' table on the device, rebuilt on the host (rip::build_output_table) when the format or the normalisation
+// has changed since the last frame
+void ensure_output_table(rip_pipeline* p, int fmt) {
+  if (!p->out_tab_dirty) return;
+  const size_t bytes = 768 * (size_t)rip::output_format_elem_bytes(fmt);
+  p->h_out_tab.resize(bytes);
+  rip::build_output_table(fmt, p->m.out_divisor, p->m.out_mean, p->m.out_std, p->h_out_tab.data());
+  p->d_out_tab.reserve(768 * 4);
+  HIP_CHECK(hipMemcpyAsync(p->d_out_tab.ptr, p->h_out_tab.data(), bytes, hipMemcpyHostToDevice, p->stream));
+  HIP_CHECK(hipStreamSynchronize(p->stream));
+  p->out_tab_dirty = false;
+}
+
+// run_batch with the output stage behind it: under a format the chain's last kernel writes the pipeline's image into the
+// handle's staging buffer and one launch of the converter (librip_out_hip.so) writes the caller's buffer; "native" is run_batch.
+// out_step / out_frame_stride: the DELIVERED layout, resolved (non-zero) under a format.
+void run_batch_formatted(rip_pipeline* p, const Plan& pl, const uint8_t* d_in, size_t in_step, size_t in_frame_stride, int n, int rows,
+                         int cols, uint8_t* d_out, size_t out_step, size_t out_frame_stride, uint8_t* d_tap_deb, uint8_t* d_tap_col) {
+  if (pl.out_fmt == rip::OUT_NATIVE) {
+    run_batch(p, pl, d_in, in_step, in_frame_stride, n, rows, cols, d_out, out_step, out_frame_stride, d_tap_deb, d_tap_col);
+    return;
+  }
+  DeviceGuard device_guard(p->device);
+  const size_t pitch = fmt_pitch(pl), frame = pitch * (size_t)pl.out_rows;
+  p->d_fmt.reserve(frame * (size_t)n);
+  if (pl.dl_planar) ensure_output_table(p, pl.out_fmt);
+  run_batch(p, pl, d_in, in_step, in_frame_stride, n, rows, cols, p->d_fmt.as<uint8_t>(), pitch, frame, d_tap_deb, d_tap_col);
+  rip::OutputConvertParams c = {};
+  c.src = p->d_fmt.as<uint8_t>();
+  c.src_step = pitch;
+  c.src_frame_stride = frame;
+  c.dst = d_out;
+  c.dst_step = out_step;
+  c.dst_frame_stride = out_frame_stride;
+  c.rows = pl.out_rows;
+  c.cols = pl.out_cols;
+  c.n_frames = n;
+  c.format = pl.out_fmt;
+  c.table = pl.dl_planar ? p->d_out_tab.ptr : nullptr;
+  rip::OutputLaunchInfo info = {};
+  if (!rip::launch_output_convert(c, p->stream, &info)) throw DeviceError("internal: the output converter refused a layout the frame call had accepted");
+  hipError_t le = hipGetLastError();
+  if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+  LaunchLogScope log_scope(p);
+  RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+}
+
+// the DELIVERED row pitch and frame stride of rip_apply_device under a format (0 = tight), with the checks rip.h promises:
+// interleaved formats as today, planar ones with out_step the row pitch inside a plane and three planes of out_step * rows
+void resolve_output_layout(const Plan& pl, const void* d_out, size_t& o_step, size_t& o_stride) {
+  const size_t e = (size_t)pl.dl_elem_bytes;
+  const size_t row = (size_t)pl.out_cols * e * (pl.dl_planar ? 1 : (size_t)pl.dl_channels);
+  if (o_step == 0) o_step = row;
+  if (o_step < row) throw InvalidArgument("output row pitch smaller than a row");
+  const unsigned long long frame = (unsigned long long)o_step * pl.out_rows * (pl.dl_planar ? 3ull : 1ull);
+  if (o_step >= (1u << 24) || frame >= (1ull << 32)) throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
+  if (o_stride == 0) o_stride = (size_t)frame;
+  if (o_stride < frame) throw InvalidArgument("output frame stride smaller than a frame");
+  if ((reinterpret_cast<uintptr_t>(d_out) | o_step | o_stride) % e != 0)
+    throw InvalidArgument("output buffer, row pitch and frame stride must be multiples of the element size (" + std::to_string(e) + " bytes)");
+}
+
 // setDebug(true): raw_image_pipeline.hpp:143-172 writes the image after EVERY module -- enabled or not -- to
 // /tmp/0N_<module>.png through saveDebugImage (:179-186: copy, cv::normalize(0, 255, NORM_MINMAX), cv::imwrite).  The modules
 // are one fused kernel here, so the image after module k is produced by running the chain once more with the modules after k
@@ -1689,10 +1791,24 @@ rip_status rip_query_output(rip_pipeline* p, int rows, int cols, int channels, c
     need(p);
     if (!encoding) throw InvalidArgument("encoding is null");
     Plan pl = make_plan(p, rows, cols, channels, encoding);
+    apply_output_format(p, pl);
     if (out_rows) *out_rows = pl.out_rows;
     if (out_cols) *out_cols = pl.out_cols;
-    if (out_channels) *out_channels = pl.channels;
+    if (out_channels) *out_channels = pl.dl_channels;
     if (encoding_out) copy_string(pl.encoding_out, encoding_out, 32);
+  });
+}
+
+rip_status rip_query_output_bytes(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, size_t* bytes, int* elem_bytes,
+                                  int* planar) {
+  return guarded(p, [&] {
+    need(p);
+    if (!encoding) throw InvalidArgument("encoding is null");
+    Plan pl = make_plan(p, rows, cols, channels, encoding);
+    apply_output_format(p, pl);
+    if (bytes) *bytes = delivered_bytes(pl);
+    if (elem_bytes) *elem_bytes = pl.dl_elem_bytes;
+    if (planar) *planar = pl.dl_planar ? 1 : 0;
   });
 }
 
@@ -1717,6 +1833,7 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     if (n_frames < 0) throw InvalidArgument("negative frame count");
     if (n_frames == 0) return;
     Plan pl = make_plan(p, rows, cols, channels, encoding);
+    apply_output_format(p, pl);
     const size_t eb = (size_t)pl.out_elem_bytes, in_row = row_bytes(pl, cols, channels);
     if (in_step == 0) in_step = in_row;
     if (in_frame_stride == 0) in_frame_stride = in_step * rows;
@@ -1726,23 +1843,28 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     // several kernels put the frame index on gridDim.y (<= 65535): longer batches go through in slices.  The
     // frames of a stream are processed in order either way (the ccc Kalman state lives on the device).
     constexpr int kMaxFramesPerLaunch = 16384;
-    const size_t o_step = out_step ? out_step : (size_t)pl.out_cols * pl.channels * eb;
-    const size_t o_stride = out_frame_stride ? out_frame_stride : o_step * pl.out_rows;
+    size_t o_step = out_step ? out_step : (size_t)pl.out_cols * pl.channels * eb;
+    size_t o_stride = out_frame_stride ? out_frame_stride : o_step * pl.out_rows;
+    if (pl.out_fmt != rip::OUT_NATIVE) {  // the converted geometry, same checks
+      o_step = out_step;
+      o_stride = out_frame_stride;
+      resolve_output_layout(pl, d_out, o_step, o_stride);
+    }
     // the kernels address one frame with 32-bit byte offsets and 24-bit row multiplies: refuse pitches they cannot
     // express (and pitches that would make rows or frames overlap) instead of writing somewhere else
-    if (o_step < (size_t)pl.out_cols * pl.channels * eb) throw InvalidArgument("output row pitch smaller than a row");
-    if (o_stride < o_step * (size_t)pl.out_rows) throw InvalidArgument("output frame stride smaller than a frame");
+    if (pl.out_fmt == rip::OUT_NATIVE && o_step < (size_t)pl.out_cols * pl.channels * eb) throw InvalidArgument("output row pitch smaller than a row");
+    if (pl.out_fmt == rip::OUT_NATIVE && o_stride < o_step * (size_t)pl.out_rows) throw InvalidArgument("output frame stride smaller than a frame");
     if (in_frame_stride < in_step * (size_t)(rows - 1) + in_row) throw InvalidArgument("input frame stride smaller than a frame");
     if (in_step >= (1u << 24) || o_step >= (1u << 24) || (unsigned long long)in_step * rows >= (1ull << 32) ||
-        (unsigned long long)o_step * pl.out_rows >= (1ull << 32))
+        (pl.out_fmt == rip::OUT_NATIVE && (unsigned long long)o_step * pl.out_rows >= (1ull << 32)))
       throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
     const size_t tap_frame = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
       const int n = std::min(kMaxFramesPerLaunch, n_frames - f0);
       uint8_t* tap_deb = d_tap_debayered ? static_cast<uint8_t*>(d_tap_debayered) + (size_t)f0 * tap_frame : nullptr;
       uint8_t* tap_col = d_tap_color ? static_cast<uint8_t*>(d_tap_color) + (size_t)f0 * tap_frame : nullptr;
-      run_batch(p, pl, static_cast<const uint8_t*>(d_in) + (size_t)f0 * in_frame_stride, in_step, in_frame_stride, n, rows, cols,
-                static_cast<uint8_t*>(d_out) + (size_t)f0 * o_stride, o_step, o_stride, tap_deb, tap_col);
+      run_batch_formatted(p, pl, static_cast<const uint8_t*>(d_in) + (size_t)f0 * in_frame_stride, in_step, in_frame_stride, n, rows, cols,
+                          static_cast<uint8_t*>(d_out) + (size_t)f0 * o_stride, o_step, o_stride, tap_deb, tap_col);
     }
   });
 }
@@ -1754,13 +1876,14 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     need_device(p);
     if (!image || !out || !encoding) throw InvalidArgument("null buffer or encoding");
     Plan pl = make_plan(p, rows, cols, channels, encoding);
+    apply_output_format(p, pl);
     DeviceGuard device_guard(p->device);
     const size_t eb = (size_t)pl.out_elem_bytes, in_row = row_bytes(pl, cols, channels);
     if (step == 0) step = in_row;
     if (pl.packed_layout && step < in_row) throw InvalidArgument("input row pitch smaller than a row");
     const size_t in_pitch = (in_row + 3) & ~(size_t)3;  // dword-aligned rows on the device
     const size_t in_bytes = in_pitch * rows;
-    const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb;
+    const size_t out_bytes = delivered_bytes(pl);
     const size_t mid_bytes = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
     if (out_capacity < out_bytes) throw CapacityError("output buffer too small: need " + std::to_string(out_bytes) + " bytes");
     p->d_in.reserve(in_bytes);
@@ -1776,10 +1899,22 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
       tap_col = p->d_tap_col.as<uint8_t>();
     }
     HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, in_pitch, image, step, in_row, (size_t)rows, hipMemcpyHostToDevice, p->stream));
-    run_batch(p, pl, p->d_in.as<uint8_t>(), in_pitch, in_bytes, 1, rows, cols, p->d_out.as<uint8_t>(), 0, 0, tap_deb, tap_col);
+    size_t tight_step = 0, tight_stride = 0;
+    if (pl.out_fmt != rip::OUT_NATIVE) resolve_output_layout(pl, p->d_out.ptr, tight_step, tight_stride);
+    run_batch_formatted(p, pl, p->d_in.as<uint8_t>(), in_pitch, in_bytes, 1, rows, cols, p->d_out.as<uint8_t>(), tight_step, tight_stride, tap_deb, tap_col);
     HIP_CHECK(hipMemcpyAsync(out, p->d_out.ptr, out_bytes, hipMemcpyDeviceToHost, p->stream));
     HIP_CHECK(hipStreamSynchronize(p->stream));
-    if (p->m.debug && eb == 1) write_debug_dumps(p, pl, in_pitch, in_bytes, rows, cols, out);
+    if (p->m.debug && eb == 1) {
+      if (pl.out_fmt == rip::OUT_NATIVE) {
+        write_debug_dumps(p, pl, in_pitch, in_bytes, rows, cols, out);
+      } else {  // the dumps show the pipeline's image, not the delivered buffer: fetch it from the staging buffer
+        std::vector<uint8_t> native((size_t)pl.out_rows * pl.out_cols * 3);
+        HIP_CHECK(hipMemcpy2DAsync(native.data(), (size_t)pl.out_cols * 3, p->d_fmt.ptr, fmt_pitch(pl), (size_t)pl.out_cols * 3, (size_t)pl.out_rows,
+                                   hipMemcpyDeviceToHost, p->stream));
+        HIP_CHECK(hipStreamSynchronize(p->stream));
+        write_debug_dumps(p, pl, in_pitch, in_bytes, rows, cols, native.data());
+      }
+    }
     for (int i = 0; i < 3; i++) p->last_valid[i] = false;
     auto remember = [&](int which, DevBuf* buf, int r, int c, bool on) {
       p->last_valid[which] = on;
@@ -1791,10 +1926,11 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     };
     remember(RIP_IMAGE_DEBAYERED, &p->d_tap_deb, pl.mid_rows, pl.mid_cols, tap_deb != nullptr);
     remember(RIP_IMAGE_COLOR, &p->d_tap_col, pl.mid_rows, pl.mid_cols, tap_col != nullptr);
-    remember(RIP_IMAGE_PROCESSED, &p->d_out, pl.out_rows, pl.out_cols, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb == 1);
+    // under a format the delivered buffer is the result (as for bgr16): no PROCESSED image
+    remember(RIP_IMAGE_PROCESSED, &p->d_out, pl.out_rows, pl.out_cols, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb == 1 && !pl.fmt_active);
     if (out_rows) *out_rows = pl.out_rows;
     if (out_cols) *out_cols = pl.out_cols;
-    if (out_channels) *out_channels = pl.channels;
+    if (out_channels) *out_channels = pl.dl_channels;
     if (encoding_out) copy_string(pl.encoding_out, encoding_out, 32);
   });
 }
@@ -1820,9 +1956,10 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     need_device(p);
     if (!image || !encoding || !ticket) throw InvalidArgument("null buffer, encoding or ticket");
     Plan pl = make_plan(p, rows, cols, channels, encoding);
+    apply_output_format(p, pl);
     {  // destinations given by the caller (rip_submit_to): checked before anything is enqueued or any slot is touched
       const size_t eb0 = (size_t)pl.out_elem_bytes;
-      const size_t out_need = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb0, mid_need = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
+      const size_t out_need = delivered_bytes(pl), mid_need = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
       if (ext_out && ext_out_capacity < out_need) throw CapacityError("rip_submit_to: result buffer too small: need " + std::to_string(out_need) + " bytes");
       if ((ext_deb || ext_col) && ext_tap_capacity < mid_need) throw CapacityError("rip_submit_to: tap buffer too small: need " + std::to_string(mid_need) + " bytes");
       if (ext_deb && !((p->tap_mask & RIP_TAP_DEBAYERED) && eb0 == 1)) throw InvalidArgument("rip_submit_to: the debayered tap is not kept (rip_set_taps)");
@@ -1866,7 +2003,7 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     if (pl.packed_layout && step < in_row) throw InvalidArgument("input row pitch smaller than a row");
     const size_t in_pitch = (in_row + 3) & ~(size_t)3;  // dword-aligned rows on the device
     const size_t in_bytes = in_pitch * rows;
-    const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * eb;
+    const size_t out_bytes = delivered_bytes(pl);
     const size_t mid_bytes = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
     sl.d_in.reserve(in_bytes);
     sl.d_out.reserve(out_bytes);
@@ -1906,8 +2043,10 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     }
     HIP_CHECK(hipEventRecord(sl.ev_up, p->ul_stream));
     HIP_CHECK(hipStreamWaitEvent(p->stream, sl.ev_up, 0));
-    run_batch(p, pl, sl.d_in.as<uint8_t>(), in_pitch, in_bytes, 1, rows, cols, sl.d_out.as<uint8_t>(), 0, 0,
-              sl.has_deb ? sl.d_tap_deb.as<uint8_t>() : nullptr, sl.has_col ? sl.d_tap_col.as<uint8_t>() : nullptr);
+    size_t tight_step = 0, tight_stride = 0;
+    if (pl.out_fmt != rip::OUT_NATIVE) resolve_output_layout(pl, sl.d_out.ptr, tight_step, tight_stride);
+    run_batch_formatted(p, pl, sl.d_in.as<uint8_t>(), in_pitch, in_bytes, 1, rows, cols, sl.d_out.as<uint8_t>(), tight_step, tight_stride,
+                        sl.has_deb ? sl.d_tap_deb.as<uint8_t>() : nullptr, sl.has_col ? sl.d_tap_col.as<uint8_t>() : nullptr);
     HIP_CHECK(hipEventRecord(sl.ev_kernels, p->stream));
     HIP_CHECK(hipStreamWaitEvent(p->dl_stream, sl.ev_kernels, 0));
     if (sl.ev_dl_start) HIP_CHECK(hipEventRecord(sl.ev_dl_start, p->dl_stream));
@@ -1947,7 +2086,7 @@ rip_status rip_collect(rip_pipeline* p, uint64_t ticket, uint8_t* out, size_t ou
       if (s->busy && s->ticket == ticket) sl = s.get();
     if (!sl) throw InvalidArgument("rip_collect: ticket " + std::to_string(ticket) + " is not in flight");
     const Plan& pl = sl->pl;
-    const size_t out_bytes = (size_t)pl.out_rows * pl.out_cols * pl.channels * (size_t)pl.out_elem_bytes;
+    const size_t out_bytes = delivered_bytes(pl);
     if (out && out_capacity < out_bytes) throw CapacityError("output buffer too small: need " + std::to_string(out_bytes) + " bytes");
     DeviceGuard device_guard(p->device);
     HIP_CHECK(hipEventSynchronize(sl->ev_done));
@@ -1984,10 +2123,10 @@ rip_status rip_collect(rip_pipeline* p, uint64_t ticket, uint8_t* out, size_t ou
     // they may be freed or edited, so the getters go back to the device image in the slot this frame keeps held.
     remember(RIP_IMAGE_DEBAYERED, &sl->d_tap_deb, sl->dl_deb && sl->dst_tap[0] == sl->h_tap[0] ? sl->dst_tap[0] : nullptr, pl.mid_rows, pl.mid_cols, sl->has_deb);
     remember(RIP_IMAGE_COLOR, &sl->d_tap_col, sl->dl_col && sl->dst_tap[1] == sl->h_tap[1] ? sl->dst_tap[1] : nullptr, pl.mid_rows, pl.mid_cols, sl->has_col);
-    remember(RIP_IMAGE_PROCESSED, &sl->d_out, sl->dst_out == sl->h_out ? sl->dst_out : nullptr, pl.out_rows, pl.out_cols, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1);
+    remember(RIP_IMAGE_PROCESSED, &sl->d_out, sl->dst_out == sl->h_out ? sl->dst_out : nullptr, pl.out_rows, pl.out_cols, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1 && !pl.fmt_active);
     if (out_rows) *out_rows = pl.out_rows;
     if (out_cols) *out_cols = pl.out_cols;
-    if (out_channels) *out_channels = pl.channels;
+    if (out_channels) *out_channels = pl.dl_channels;
     if (encoding_out) copy_string(pl.encoding_out, encoding_out, 32);
   });
 }
@@ -2103,7 +2242,7 @@ rip_status rip_load_params(rip_pipeline* p, const char* path) {
       p->m.und_available = false;
       p->ccc_state_init = false;
     }
-    p->tabs_dirty = p->vig_dirty = p->ccc_cfg_dirty = true;
+    p->tabs_dirty = p->vig_dirty = p->ccc_cfg_dirty = p->out_tab_dirty = true;
     und_init(p);  // setBalance / setFovScale re-run init()
   });
 }
@@ -2195,6 +2334,12 @@ RIP_SETTER(rip_set_debayer_16bit_range, (rip_pipeline * p, int black, int white)
 RIP_SETTER(rip_set_debayer_encoding, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.debayer_encoding = s)
 RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            rip::check_debayer_method(s); p->m.debayer_method = s)
+RIP_SETTER(rip_set_output_format, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+           (void)rip::output_format_id(s); if (p->m.out_format != s) p->out_tab_dirty = true; p->m.out_format = s)
+RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, const double* mean, const double* sd),
+           if (!mean || !sd) throw InvalidArgument("null mean or std");
+           rip::check_output_normalization(divisor, mean, sd); p->m.out_divisor = divisor;
+           for (int i = 0; i < 3; i++) { p->m.out_mean[i] = mean[i]; p->m.out_std[i] = sd[i]; } p->out_tab_dirty = true)
 RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
 RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)
 RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v != 0)
@@ -2262,6 +2407,32 @@ rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t cap) 
   return guarded(p, [&] {
     need(p);
     copy_string(p->m.debayer_method, out, cap);
+  });
+}
+
+rip_status rip_get_output_format(const rip_pipeline* p, char* out, size_t cap) {
+  return guarded(p, [&] {
+    need(p);
+    copy_string(p->m.out_format, out, cap);
+  });
+}
+
+rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, double* mean, double* sd) {
+  return guarded(p, [&] {
+    need(p);
+    if (divisor) *divisor = p->m.out_divisor;
+    for (int i = 0; i < 3; i++) {
+      if (mean) mean[i] = p->m.out_mean[i];
+      if (sd) sd[i] = p->m.out_std[i];
+    }
+  });
+}
+
+rip_status rip_debug_output_table(const char* name, double divisor, const double* mean, const double* sd, void* out) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    if (!name || !mean || !sd || !out) throw InvalidArgument("rip_debug_output_table: null argument");
+    const int fmt = rip::output_format_id(name);
+    rip::build_output_table(fmt, divisor, mean, sd, out);
   });
 }
 

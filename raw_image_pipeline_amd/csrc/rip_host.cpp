@@ -296,6 +296,24 @@ void params_from_node(Modules& m, const YamlNode& node) {
   // loadParams re-creates the modules, so absent keys mean off.  An invalid range fails the load like an unknown method.
   const int black_level = node["debayer"].get("black_level", 0), white_level = node["debayer"].get("white_level", 0);
   check_debayer_16bit_range(black_level, white_level);
+  // extension keys output: format: / divisor: / mean: [3] / std: [3] (rip_set_output_format, rip_set_output_normalization);
+  // absent keys mean the defaults, an invalid value fails the load like an unknown debayer method
+  const YamlNode& o = node["output"];
+  const std::string out_format = o.get("format", std::string("native"));
+  (void)output_format_id(out_format);
+  const double out_divisor = o.get("divisor", 255.0);
+  double out_mean[3] = {0, 0, 0}, out_std[3] = {1, 1, 1};
+  for (int which = 0; which < 2; which++) {
+    const char* key = which ? "std" : "mean";
+    if (!o[key].defined()) continue;
+    const std::vector<double> v = o.get_vector(key);
+    if (v.size() != 3) throw std::invalid_argument(std::string("output: ") + key + ": a sequence of 3 numbers is expected");
+    for (int i = 0; i < 3; i++) (which ? out_std : out_mean)[i] = v[i];
+  }
+  check_output_normalization(out_divisor, out_mean, out_std);
+  m.out_format = out_format;
+  m.out_divisor = out_divisor;
+  for (int i = 0; i < 3; i++) m.out_mean[i] = out_mean[i], m.out_std[i] = out_std[i];
   m.debayer_method = debayer_method;
   m.debayer_16bit = node["debayer"].get("accept_16bit", false);
   m.raw16_black = black_level;
@@ -383,6 +401,76 @@ void apply_example_params(Modules& m) {
 void check_debayer_method(const std::string& method) {
   if (method != "bilinear" && method != "mht")
     throw std::invalid_argument("Debayer method [" + method + "] not supported. Supported methods: 'bilinear', 'mht'");
+}
+
+namespace {
+const char* const kOutputFormatNames[9] = {"native", "rgb8", "mono8", "rgb_chw_f32", "rgb_chw_f16", "rgb_chw_bf16",
+                                           "bgr_chw_f32", "bgr_chw_f16", "bgr_chw_bf16"};  // index = rip_output.hpp OutputFormat
+
+uint32_t float_bits(float f) {
+  uint32_t x;
+  std::memcpy(&x, &f, sizeof(x));
+  return x;
+}
+// IEEE 754 binary32 -> binary16, round to nearest even
+uint16_t f32_to_f16(float f) {
+  uint32_t x = float_bits(f);
+  const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
+  x &= 0x7FFFFFFFu;
+  if (x > 0x7F800000u) return (uint16_t)(sign | 0x7E00u);  // NaN
+  const int e = (int)(x >> 23);
+  uint32_t m = x & 0x7FFFFFu;
+  if (e >= 143) return (uint16_t)(sign | 0x7C00u);  // 2^16 and above, inf
+  if (e >= 113) {                                    // normal halves; a carry out of the mantissa goes into the exponent, up to inf
+    uint32_t h = ((uint32_t)(e - 112) << 10) | (m >> 13);
+    const uint32_t rem = m & 0x1FFFu;
+    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) h++;
+    return (uint16_t)(sign | h);
+  }
+  if (e < 102) return sign;  // below 2^-25: zero
+  m |= 0x800000u;            // subnormal halves, in units of 2^-24
+  const int shift = 126 - e;
+  uint32_t h = m >> shift;
+  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  if (rem > half || (rem == half && (h & 1u))) h++;
+  return (uint16_t)(sign | h);
+}
+// binary32 -> bfloat16, round to nearest even
+uint16_t f32_to_bf16(float f) {
+  const uint32_t x = float_bits(f);
+  if ((x & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((x >> 16) | 0x0040u);  // NaN stays NaN
+  return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1u)) >> 16);
+}
+}  // namespace
+
+int output_format_id(const std::string& name) {
+  std::string names;
+  for (int i = 0; i < 9; i++) {
+    if (name == kOutputFormatNames[i]) return i;
+    names += std::string(i ? ", '" : "'") + kOutputFormatNames[i] + "'";
+  }
+  throw std::invalid_argument("Output format [" + name + "] not supported. Supported formats: " + names);
+}
+
+void check_output_normalization(double divisor, const double mean[3], const double sd[3]) {
+  bool ok = std::isfinite(divisor) && divisor != 0.0;
+  for (int i = 0; i < 3 && ok; i++) ok = std::isfinite(mean[i]) && std::isfinite(sd[i]) && sd[i] != 0.0;
+  if (!ok) throw std::invalid_argument("output normalisation: divisor, mean and std must be finite, divisor and every std non-zero");
+}
+
+void build_output_table(int format, double divisor, const double mean[3], const double sd[3], void* out) {
+  if (format < 3 || format > 8) throw std::invalid_argument("this output format has no table (the planar float formats have one)");
+  check_output_normalization(divisor, mean, sd);
+  const int kind = (format - 3) % 3;  // f32, f16, bf16
+  for (int c = 0; c < 3; c++)
+    for (int v = 0; v < 256; v++) {
+      volatile double q = (double)v / divisor;  // every operation rounded to double on its own
+      volatile double d = q - mean[c];
+      const float t = (float)(d / sd[c]);
+      const int i = c * 256 + v;
+      if (kind == 0) static_cast<float*>(out)[i] = t;
+      else static_cast<uint16_t*>(out)[i] = kind == 1 ? f32_to_f16(t) : f32_to_bf16(t);
+    }
 }
 
 void check_debayer_16bit_range(int black, int white) {

@@ -57,6 +57,11 @@ struct Modules {
   // extension (rip_set_debayer_method): "bilinear" (the CPU path, debayer.cpp:49-70) or "mht" (Malvar-He-Cutler, what the
   // CUDA path's cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT) computes, debayer.cpp:93-108)
   std::string debayer_method = "bilinear";
+  // extension (rip_set_output_format, rip_set_output_normalization): the output stage behind the last module -- the format the
+  // frame calls deliver ("native": the pipeline's own image) and the normalisation of the planar float formats, mean / std in
+  // the order of the format's planes
+  std::string out_format = "native";
+  double out_divisor = 255.0, out_mean[3] = {0, 0, 0}, out_std[3] = {1, 1, 1};
   // FlipModule (flip.hpp:63-66)
   bool flip_enabled = false;
   int flip_angle = 0;
@@ -99,6 +104,15 @@ bool load_params_file(Modules& m, const std::string& path);             // raw_i
 void check_debayer_method(const std::string& method);
 // the 16-bit ranges rip_set_debayer_16bit_range accepts: (0, 0) or 0 <= black < white <= 65535; throws std::invalid_argument
 void check_debayer_16bit_range(int black, int white);
+// the output formats rip_set_output_format accepts: the id (rip_output.hpp OutputFormat; 0 = "native"); throws
+// std::invalid_argument listing the names for any other name
+int output_format_id(const std::string& name);
+// the normalisations rip_set_output_normalization accepts: everything finite, divisor != 0, std_c != 0; throws std::invalid_argument
+void check_output_normalization(double divisor, const double mean[3], const double sd[3]);
+// The 3 x 256 table of a planar format (ids 3 .. 8), plane-major, in the format's element type: for plane c and value v,
+// y = (v / divisor - mean_c) / std_c in double, every operation rounded, T_c[v] = (float)y; f16 / bf16 entries are that float
+// rounded to nearest even (overflow to +-inf and subnormals as IEEE 754 says).  out: 768 elements of 4 / 2 / 2 bytes.
+void build_output_table(int format, double divisor, const double mean[3], const double sd[3], void* out);
 bool load_camera_calibration_file(Modules& m, const std::string& path); // undistortion.cpp:157-195
 bool load_color_calibration_file(Modules& m, const std::string& path);  // color_calibration.cpp:52-76
 void apply_example_camera_calibration(Modules& m);  // values of config/alphasense_calib_example.yaml

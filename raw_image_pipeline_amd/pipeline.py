@@ -37,6 +37,23 @@ def packed_width(row_bytes, bits):
     return 8 * int(row_bytes) // bits
 
 
+# The output formats of set_output_format (include/rip.h rip_set_output_format) besides "native": numpy dtype of a delivered
+# element, planar ([3, R, C]) or interleaved, channels.  numpy has no bfloat16: the host calls return bf16 as uint16 bit patterns.
+OUTPUT_FORMATS = {
+    "rgb8": (np.uint8, False, 3), "mono8": (np.uint8, False, 1),
+    "rgb_chw_f32": (np.float32, True, 3), "rgb_chw_f16": (np.float16, True, 3), "rgb_chw_bf16": (np.uint16, True, 3),
+    "bgr_chw_f32": (np.float32, True, 3), "bgr_chw_f16": (np.float16, True, 3), "bgr_chw_bf16": (np.uint16, True, 3),
+}
+
+
+def _delivered(rows, cols, channels, encoding):
+    """(shape, numpy dtype) of one delivered frame as rip_query_output / rip_apply / rip_collect describe it."""
+    dtype, planar, _ = OUTPUT_FORMATS.get(encoding, (np.uint16 if encoding.endswith("16") else np.uint8, False, channels))
+    if planar:
+        return (channels, rows, cols), np.dtype(dtype)
+    return ((rows, cols) if channels == 1 else (rows, cols, channels)), np.dtype(dtype)
+
+
 class RipError(RuntimeError):
     """HIP/device failure (RIP_ERR_DEVICE, RIP_ERR_CAPACITY)."""
 
@@ -218,6 +235,7 @@ class RawImagePipeline:
         self.out_pool = None  # an OutputPool: collect() / the image getters then recycle the arrays of their deep copies
         self._given = {}       # ticket -> (out, tap_debayered, tap_color) arrays handed to submit()
         self._given_last = (None, None, None)  # ... of the frame collected last (what the image getters return)
+        self._output_format = self.get_output_format()  # kept beside the handle's: apply_device asks on every batch
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -259,6 +277,13 @@ class RawImagePipeline:
                    C.byref(cn), enc)
         return r.value, c.value, cn.value, enc.value.decode()
 
+    def query_output_bytes(self, rows, cols, channels, encoding):
+        """(bytes, element bytes, planar) of one tightly packed delivered frame (rip_query_output_bytes): what the capacities
+        of ``process`` / ``submit(out=)`` / ``collect`` are checked against."""
+        b, e, pl = C.c_size_t(), C.c_int(), C.c_int()
+        self._call("rip_query_output_bytes", int(rows), int(cols), int(channels), encoding.encode(), C.byref(b), C.byref(e), C.byref(pl))
+        return b.value, e.value, bool(pl.value)
+
     def query_taps(self, rows, cols, channels, encoding):
         """Geometry of the debayered / colour taps (post-flip, pre-undistortion): rows, cols, channels."""
         tr, tc, tcn = C.c_int(), C.c_int(), C.c_int()
@@ -297,8 +322,7 @@ class RawImagePipeline:
         orows, ocols, ocn, oenc = self.query_output(rows, cols, cn, encoding)
         if wide != encoding.endswith("16"):
             raise ValueError("dtype %s does not match encoding %s" % (img.dtype, encoding))
-        oshape = (orows, ocols) if ocn == 1 else (orows, ocols, ocn)
-        odtype = np.uint16 if oenc.endswith("16") else np.uint8
+        oshape, odtype = _delivered(orows, ocols, ocn, oenc)
         out = self.out_pool.take(oshape, odtype) if self.out_pool is not None else np.empty(oshape, odtype)
         r, c, k = C.c_int(), C.c_int(), C.c_int()
         enc = C.create_string_buffer(32)
@@ -307,7 +331,7 @@ class RawImagePipeline:
                    encoding.encode(), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes), C.byref(r), C.byref(c),
                    C.byref(k), enc)
         self.last_encoding = enc.value.decode()
-        shape = (r.value, c.value) if k.value == 1 else (r.value, c.value, k.value)
+        shape, _ = _delivered(r.value, c.value, k.value, self.last_encoding)
         return out if out.shape == shape else out.reshape(shape)
 
     def apply(self, image, encoding, width=None):
@@ -360,20 +384,18 @@ class RawImagePipeline:
         view = C.c_void_p()
         self._call("rip_collect", C.c_uint64(int(ticket)), None, C.c_size_t(0), C.byref(view), C.byref(r), C.byref(c), C.byref(k), enc)
         self.last_encoding = enc.value.decode()
-        wide = self.last_encoding.endswith("16")
+        shape, dtype = _delivered(r.value, c.value, k.value, self.last_encoding)
         n = r.value * c.value * k.value
-        shape = (r.value, c.value) if k.value == 1 else (r.value, c.value, k.value)
         self._given_last = self._given.pop(int(ticket), (None, None, None))
         if self._given_last[0] is not None:  # the download went straight into the caller's array: it IS the deep copy
             g = self._given_last[0]
             return g if g.shape == tuple(shape) else g.reshape(shape)
         if copy:  # the library's copy (split over a few threads for whole frames), not numpy's
-            dtype = np.uint16 if wide else np.uint8
             out = self.out_pool.take(shape, dtype) if self.out_pool is not None else np.empty(shape, dtype)
             self._lib.rip_copy_host(out.ctypes.data_as(C.c_void_p), view, C.c_size_t(out.nbytes))
             return out
-        buf = (C.c_uint16 if wide else C.c_uint8) * n
-        arr = np.frombuffer(buf.from_address(view.value), np.uint16 if wide else np.uint8).reshape(shape)
+        buf = C.c_uint8 * (n * dtype.itemsize)
+        arr = np.frombuffer(buf.from_address(view.value), dtype).reshape(shape)
         arr.flags.writeable = False
         return arr
 
@@ -390,7 +412,12 @@ class RawImagePipeline:
         given; without one it is bgr16 as bytes, [n, R, C, 6].
 
         Packed Bayer encodings: [n, rows, row bytes] uint8 tensors, ``width`` pixels per row (default
-        ``8 * row_bytes // bits``); the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be given."""
+        ``8 * row_bytes // bits``); the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be given.
+
+        Under an output format (``set_output_format``) the result is uint8 [n, R, C, 3] (rgb8) / [n, R, C] (mono8) or float32 /
+        float16 / bfloat16 [n, 3, R, C]; ``out`` may then be a strided view whose innermost elements are contiguous: its row
+        pitch and frame stride are handed on as rip_apply_device's out_step / out_frame_stride (a planar view's planes must lie
+        ``rows`` row pitches apart)."""
         import torch
         if frames.dtype != torch.uint8 or not frames.is_cuda:
             raise ValueError("frames must be a uint8 CUDA tensor")
@@ -423,11 +450,28 @@ class RawImagePipeline:
         in_step = frames.stride(1)
         in_frame = frames.stride(0) if n > 1 else in_step * rows
         orows, ocols, ocn, enc = self.query_output(rows, cols, cn, encoding)
-        shape = (n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn * (2 if enc.endswith("16") else 1))
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
-        elif tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError("out must be a contiguous tensor of shape %s" % (shape,))
+        out_step = out_frame = 0
+        if self._output_format != "native" and enc in OUTPUT_FORMATS:
+            dtype, planar, _ = OUTPUT_FORMATS[enc]
+            tdtype = torch.bfloat16 if enc.endswith("bf16") else {np.uint8: torch.uint8, np.float32: torch.float32, np.float16: torch.float16}[dtype]
+            shape = (n, 3, orows, ocols) if planar else ((n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn))
+            if out is None:
+                out = torch.empty(shape, dtype=tdtype, device=frames.device)
+            elif tuple(out.shape) != shape or out.dtype != tdtype:
+                raise ValueError("out must be a %s tensor of shape %s" % (tdtype, shape))
+            elif not out.is_contiguous():
+                elem = out.element_size()
+                ok = out.stride(-1) == 1 and (planar or ocn == 1 or out.stride(2) == ocn) and (not planar or out.stride(1) == out.stride(2) * orows)
+                if not ok:
+                    raise ValueError("out: the elements of a row must be contiguous and the planes of a frame `rows` row pitches apart")
+                out_step = out.stride(2 if planar else 1) * elem
+                out_frame = out.stride(0) * elem if n > 1 else 0
+        else:
+            shape = (n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn * (2 if enc.endswith("16") else 1))
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+            elif tuple(out.shape) != shape or not out.is_contiguous():
+                raise ValueError("out must be a contiguous tensor of shape %s" % (shape,))
         if out.device != frames.device:
             raise ValueError("out must live on the device of frames")
         # taps hold the post-flip, pre-undistortion geometry (tightly packed): query it with undistortion off
@@ -451,8 +495,8 @@ class RawImagePipeline:
         with torch.cuda.device(frames.device):  # the C-ABI selects the handle's device; keep the caller's current device
             self._given_last = (None, None, None)
             self._call("rip_apply_device", C.c_void_p(frames.data_ptr()), C.c_size_t(in_step), C.c_size_t(in_frame), int(n),
-                       int(rows), int(cols), int(cn), encoding.encode(), C.c_void_p(out.data_ptr()), C.c_size_t(0),
-                       C.c_size_t(0), C.c_void_p(tap_debayered.data_ptr() if tap_debayered is not None else 0),
+                       int(rows), int(cols), int(cn), encoding.encode(), C.c_void_p(out.data_ptr()), C.c_size_t(out_step),
+                       C.c_size_t(out_frame), C.c_void_p(tap_debayered.data_ptr() if tap_debayered is not None else 0),
                        C.c_void_p(tap_color.data_ptr() if tap_color is not None else 0))
         self.last_encoding = enc
         return out
@@ -505,7 +549,10 @@ class RawImagePipeline:
 
     # ---- loaders ---------------------------------------------------------------------------------
     def load_params(self, path):
-        self._call("rip_load_params", path.encode())
+        try:
+            self._call("rip_load_params", path.encode())
+        finally:
+            self._output_format = self.get_output_format()  # the params file's `output: format:`
 
     def load_camera_calibration(self, path):
         self._call("rip_load_camera_calibration", path.encode())
@@ -590,6 +637,32 @@ class RawImagePipeline:
 
     def get_debayer_method(self):
         return self._string("rip_get_debayer_method")
+
+    def set_output_format(self, name):
+        """Extension: what the frame calls deliver -- "native" (default: the pipeline's own image, nothing added), "rgb8",
+        "mono8", or the planar tensors "rgb_chw_f32" / "rgb_chw_f16" / "rgb_chw_bf16" / "bgr_chw_f32" / "bgr_chw_f16" /
+        "bgr_chw_bf16" normalised by ``set_output_normalization``.  ``process`` / ``apply`` / ``collect`` then return uint8
+        [R, C, 3] / [R, C] or float32 / float16 [3, R, C]; bf16 comes back as uint16 bit patterns [3, R, C] (numpy has no
+        bfloat16; ``apply_device`` returns a torch.bfloat16 tensor).  include/rip.h rip_set_output_format."""
+        self._call("rip_set_output_format", name.encode())
+        self._output_format = name
+
+    def get_output_format(self):
+        return self._string("rip_get_output_format")
+
+    def set_output_normalization(self, divisor=255.0, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
+        """Extension: the planar formats deliver ``(v / divisor - mean[c]) / std[c]`` for plane c (mean / std in the order of
+        the format's planes), evaluated in double and rounded to the element type.  include/rip.h rip_set_output_normalization."""
+        m, _ = _as_doubles(list(mean))
+        s, _ = _as_doubles(list(std))
+        if len(m) != 3 or len(s) != 3:
+            raise ValueError("mean and std take 3 values")
+        self._call("rip_set_output_normalization", C.c_double(divisor), m, s)
+
+    def get_output_normalization(self):
+        d, m, s = C.c_double(), (C.c_double * 3)(), (C.c_double * 3)()
+        self._call("rip_get_output_normalization", C.byref(d), m, s)
+        return d.value, tuple(m), tuple(s)
 
     def set_flip(self, enabled):
         self._call("rip_set_flip", int(bool(enabled)))
