@@ -581,9 +581,9 @@ void launch_stats(const StatsParams& p, const Tunables& tn, hipStream_t stream) 
   if (bayer_fast_geometry(p.src, p.src_step, p.src_frame_stride, p.rows, p.cols, p.src_kind)) {
     ItemMap im{p.cols / 4, 1.0f / (float)(p.cols / 4)};
     const int items = (p.rows / 2) * (p.cols / 4);
-    // keep >= 1 block per 2^20 items so the 32-bit per-thread partial sums cannot overflow
     // wave tasks: 64 groups wide x pairs_per_task row pairs.  The wave total of the largest statistic
     // (pca: sum of squares) is 64 lanes * 8 px * 255^2 * pairs_per_task: 128 pairs keep it below 2^32
+    // (wave_sum adds the 64 per-lane sums in 32 bits; a wave may own at most 66 051 saturated pixels, 128 pairs are 65 536)
     const int groups = p.cols / 4, n_pairs = p.rows / 2;
     const int col_waves = (groups + 63) / 64;
     // per frame: 512 wave tasks when the batch fills the chip anyway, 2048 for a single frame (shorter row walks; with the
@@ -610,13 +610,19 @@ void launch_stats(const StatsParams& p, const Tunables& tn, hipStream_t stream) 
     ItemMap im{p.cols / 4, 1.0f / (float)(p.cols / 4)};
     const int items = p.rows * (p.cols / 4);
     int per_frame = grid_blocks_for(items, std::max(8, 2048 / std::max(1, std::min(p.n_frames, 16))));
-    per_frame = std::max(per_frame, (int)((items + (1 << 20) - 1) >> 20));
+    // The bound on the work of a block is set by wave_sum, which adds the 64 per-lane sums of a wave in 32 bits: pca's sum of
+    // squares wraps once a wave owns more than 66 051 saturated pixels (66 052 * 255^2 > 2^32; a lane alone could take 64
+    // times as many).  A thread walks ceil(items / (blocks * 256)) items of 4 pixels, a wave 256 times as many pixels: one block
+    // per 2^16 items keeps that at 256 items per thread, 65 536 pixels per wave.  (Until now one block per 2^20 items, which only
+    // guarded the per-lane sums: a colour frame above 33.5 Mpx in a batch of 16 or more, where the cap is 128 blocks, wrapped.)
+    per_frame = std::max(per_frame, (int)(((long long)items + (1 << 16) - 1) >> 16));
     RIP_LOG_LAUNCH(dim3(per_frame, p.n_frames), kBlock, p.n_frames, "stats_color_kernel");
     hipLaunchKernelGGL(stats_color_kernel, dim3(per_frame, p.n_frames), dim3(kBlock), stats_hist_lds_bytes(p.mode), stream, p, im, items);
     return;
   }
   long long npix = (long long)p.rows * p.cols;
-  int blocks = std::max(grid_blocks_for(npix, 1024), (int)((npix + (1 << 22) - 1) >> 22));
+  // one pixel per thread and step: one block per 2^18 pixels keeps a thread at 1024 pixels and a wave at 65 536 (see above)
+  int blocks = std::max(grid_blocks_for(npix, 1024), (int)((npix + (1 << 18) - 1) >> 18));
   RIP_LOG_LAUNCH(dim3(blocks, p.n_frames), kBlock, p.n_frames, "stats_generic_kernel");
   hipLaunchKernelGGL(stats_generic_kernel, dim3(blocks, p.n_frames), dim3(kBlock), stats_hist_lds_bytes(p.mode), stream, p);
 }
