@@ -10,8 +10,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
-SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_output.hpp", os.path.join("..", "..", "include", "rip.h")]
+SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion library: the output stage's kernels (rip_set_output_format) and their one launch function (rip_output.hpp).  A
 # library of its own so that librip_hip.so's kernel table stays what tests/variant_cases.py closes over; the companion's table
 # is closed by tests/output_variant_cases.py.  librip_hip.so -- every build of it: the default one, the sanitizer build and the
@@ -79,7 +79,7 @@ def build_companion(force=False, verbose=False):
     return OUT_COMPANION
 
 
-# --asan: the HOST layer (rip_host.cpp, rip_api.cpp: YAML reader, loaders, table builders, frame ring, copy threads) under
+# --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under
 # AddressSanitizer + UndefinedBehaviorSanitizer, compiled with g++ against GCC's runtimes; the device code is compiled by hipcc
 # as always.  (Not clang's runtime: the ROCm build of compiler-rt intercepts hsa_amd_memory_pool_allocate for device-side ASan and
 # aborts the first HIP allocation of a process on a GPU box -- "allocator is trying to allocate 0x400000 bytes" -- without

@@ -1,0 +1,940 @@
+// rip_batch.cpp -- everything between a Plan and the kernels: the device-resident constants a batch needs (maps, remap plan,
+// tables, ccc model), the route a batch takes through the kernels of rip_chain/stats/ccc/remap/fused/demosaic.hip, the output
+// stage behind it and the debug dumps.  Everything is enqueued on the handle's stream.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "rip_handle.hpp"
+
+namespace rip::api {
+
+// ------------------------------------------------------------------------------------------------
+// undistortion bookkeeping: UndistortionModule::init() (undistortion.cpp:197-238) minus the map
+// generation, which is deferred until a frame (or rip_init_undistortion) needs it.
+// ------------------------------------------------------------------------------------------------
+void und_init(rip_pipeline* p) {
+  rip::Modules& m = p->m;
+  double newK[9];
+  if (rip::is_pinhole_model(m.dist_model)) {
+    // plumb_bob / radtan / rational_polynomial: cv::getOptimalNewCameraMatrix with alpha = balance (not in the reference)
+    double k[8];
+    rip::pinhole_coefficients(m.dist_model, m.dist_D, k);
+    rip::pinhole_estimate_new_camera_matrix(m.dist_K, k, m.dist_w, m.dist_h, m.balance, m.rect_w, m.rect_h, m.fov_scale, newK);
+  } else {
+    rip::fisheye_estimate_new_camera_matrix(m.dist_K, m.dist_D, m.dist_w, m.dist_h, m.dist_R, m.balance, m.rect_w, m.rect_h,
+                                            m.fov_scale, newK);
+  }
+  std::memcpy(m.rect_K, newK, sizeof(newK));
+  for (int i = 0; i < 8; i++) m.rect_D[i] = 0;
+  const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  std::memcpy(m.rect_R, eye, sizeof(eye));
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) m.rect_P[i * 4 + j] = m.rect_K[i * 3 + j];
+  p->map_dirty = true;
+}
+
+// Where the maps are built: on the device for device handles (rip_maps.hip: one thread per map row, FP64, double-double
+// atan -- milliseconds instead of 0.25-0.5 s of host threads per calibration change), on the host for RIP_DEVICE_NONE handles
+// and when RIP_MAPS_ON_HOST is set (A/B and debugging).  Both produce the same floats (tests/test_parity_gpu.py).
+static bool maps_on_device(const rip_pipeline* p) { return p->device != RIP_DEVICE_NONE && !p->maps_on_host; }
+
+void ensure_host_maps(rip_pipeline* p) {
+  if (!p->map_dirty) return;
+  const rip::Modules& m = p->m;
+  if (m.dist_w <= 0 || m.dist_h <= 0) throw AssertError("undistortion: image size is not set");
+  const size_t n = (size_t)m.dist_w * m.dist_h * 2;
+  p->h_map.resize(n);
+  // maps have the *dist* image size even after setNewImageSize (undistortion.cpp:216)
+  const bool pinhole = rip::is_pinhole_model(m.dist_model);  // every other name builds fisheye maps, as the reference does
+  if (maps_on_device(p)) {
+    DeviceGuard device_guard(p->device);
+    LaunchLogScope log_scope(p);
+    rip::UndistortMapParams fp = {};
+    std::memcpy(fp.K, m.dist_K, sizeof(fp.K));
+    fp.pinhole = pinhole ? 1 : 0;
+    if (pinhole)
+      rip::pinhole_coefficients(m.dist_model, m.dist_D, fp.D);
+    else
+      std::memcpy(fp.D, m.dist_D, 4 * sizeof(double));
+    rip::fisheye_inverse_PR(m.rect_K, m.dist_R, fp.iR);
+    fp.w = m.dist_w;
+    fp.h = m.dist_h;
+    p->d_map.reserve(n * sizeof(float));
+    fp.map_xy = p->d_map.as<float>();
+    p->d_map_ckpt.reserve(rip::undistort_ckpt_bytes(fp.w, fp.h));
+    fp.ckpt = p->d_map_ckpt.as<double>();
+    rip::launch_undistort_maps(fp, p->stream);
+    // no host copy yet: the remap-plan compiler runs on the device too; need_host_map() fetches the floats for
+    // rip_get_undistortion_maps or for a plan compiled on the host
+    p->map_dirty = false;
+    p->map_uploaded = true;
+    p->h_map_valid = false;
+    p->plan.valid = false;
+    return;
+  }
+  if (pinhole) {
+    double k[8];
+    rip::pinhole_coefficients(m.dist_model, m.dist_D, k);
+    rip::pinhole_init_undistort_rectify_map(m.dist_K, k, m.dist_R, m.rect_K, m.dist_w, m.dist_h, p->h_map.data());
+  } else {
+    rip::fisheye_init_undistort_rectify_map(m.dist_K, m.dist_D, m.dist_R, m.rect_K, m.dist_w, m.dist_h, p->h_map.data());
+  }
+  p->map_dirty = false;
+  p->map_uploaded = false;
+  p->h_map_valid = true;
+  p->plan.valid = false;
+}
+
+// the maps as floats on the host
+void need_host_map(rip_pipeline* p) {
+  ensure_host_maps(p);
+  if (p->h_map_valid) return;
+  DeviceGuard device_guard(p->device);
+  HIP_CHECK(hipMemcpyAsync(p->h_map.data(), p->d_map.ptr, p->h_map.size() * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+  HIP_CHECK(hipStreamSynchronize(p->stream));
+  p->h_map_valid = true;
+}
+
+static_assert(rip::kRemapOutside == rip::kPlanOutside && rip::kRemapBorder == rip::kPlanBorder, "plan sentinels");
+static_assert(sizeof(rip::RemapTile) == sizeof(rip::RemapTileDesc), "tile descriptor layout");
+
+void ensure_plan(rip_pipeline* p, int src_rows, int src_cols) {
+  ensure_maps(p);
+  LaunchLogScope log_scope(p);
+  const rip::Modules& m = p->m;
+  if (!p->plan.valid || p->plan.src_rows != src_rows || p->plan.src_cols != src_cols || p->plan.drows != m.dist_h ||
+      p->plan.dcols != m.dist_w) {
+    p->plan_on_device = false;
+    p->chain_items_flip = -1;
+    if (maps_on_device(p) && !p->plan_on_host) {
+      // Compile the plan where the maps are (rip_maps.hip remap_plan_kernel: one workgroup per tile; the same words, tile
+      // rectangles and border pixels as rip::compile_remap_plan, the border list in another order): no 8 B/px map read-back,
+      // no 4 B/px plan upload, no host threads -- a calibration change costs the map kernel plus ~0.1 ms.
+      rip::RemapPlan& pl = p->plan;
+      pl = rip::RemapPlan();
+      pl.drows = m.dist_h;
+      pl.dcols = m.dist_w;
+      pl.src_rows = src_rows;
+      pl.src_cols = src_cols;
+      pl.tiles_x = (pl.dcols + rip::kRemapTileW - 1) / rip::kRemapTileW;
+      pl.tiles_y = (pl.drows + rip::kRemapTileH - 1) / rip::kRemapTileH;
+      const size_t ntiles = (size_t)pl.tiles_x * pl.tiles_y;
+      const unsigned border_cap = 1u << 20;  // pixels; more than that (a map that mostly straddles the border) goes to the host
+      p->d_plan_words.reserve(ntiles * rip::kRemapTilePx * sizeof(uint32_t));
+      p->d_plan_tiles.reserve(ntiles * sizeof(rip::RemapTileDesc));
+      p->d_plan_border.reserve((size_t)border_cap * sizeof(uint32_t));
+      p->d_plan_counters.reserve(4 * sizeof(unsigned));
+      HIP_CHECK(hipMemsetAsync(p->d_plan_counters.ptr, 0, 4 * sizeof(unsigned), p->stream));
+      rip::RemapPlanBuildParams bp = {};
+      bp.map_xy = p->d_map.as<float>();
+      bp.drows = pl.drows;
+      bp.dcols = pl.dcols;
+      bp.src_rows = src_rows;
+      bp.src_cols = src_cols;
+      bp.tiles_x = pl.tiles_x;
+      bp.tiles_y = pl.tiles_y;
+      bp.words = p->d_plan_words.as<uint32_t>();
+      bp.tiles = p->d_plan_tiles.as<rip::RemapTileDesc>();
+      bp.border = p->d_plan_border.as<uint32_t>();
+      bp.border_cap = border_cap;
+      bp.counters = p->d_plan_counters.as<unsigned>();
+      rip::launch_remap_plan_build(bp, p->stream);
+      // the footprint of the same quantised taps (rip::compile_remap_footprint's hull): lo starts at 0x7F7F7F7F, hi at 0
+      const int pairs = (src_rows + 1) / 2;
+      p->d_plan_fp.reserve(2 * (size_t)pairs * sizeof(int));
+      HIP_CHECK(hipMemsetAsync(p->d_plan_fp.ptr, 0x7F, (size_t)pairs * sizeof(int), p->stream));
+      HIP_CHECK(hipMemsetAsync(p->d_plan_fp.as<int>() + pairs, 0, (size_t)pairs * sizeof(int), p->stream));
+      rip::RemapFootprintParams fq = {};
+      fq.map_xy = bp.map_xy;
+      fq.drows = pl.drows;
+      fq.dcols = pl.dcols;
+      fq.src_rows = src_rows;
+      fq.src_cols = src_cols;
+      fq.tiles_x = pl.tiles_x;
+      fq.tiles_y = pl.tiles_y;
+      fq.lo = p->d_plan_fp.as<int>();
+      fq.hi = p->d_plan_fp.as<int>() + pairs;
+      rip::launch_remap_footprint(fq, p->stream);
+      pl.fp_lo.resize(pairs);
+      pl.fp_hi.resize(pairs);
+      unsigned counters[4] = {0, 0, 0, 0};
+      HIP_CHECK(hipMemcpyAsync(counters, p->d_plan_counters.ptr, sizeof(counters), hipMemcpyDeviceToHost, p->stream));
+      HIP_CHECK(hipMemcpyAsync(pl.fp_lo.data(), fq.lo, (size_t)pairs * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+      HIP_CHECK(hipMemcpyAsync(pl.fp_hi.data(), fq.hi, (size_t)pairs * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+      HIP_CHECK(hipStreamSynchronize(p->stream));
+      for (int i = 0; i < pairs; i++)
+        if (pl.fp_lo[i] >= pl.fp_hi[i]) pl.fp_lo[i] = INT32_MAX, pl.fp_hi[i] = 0;  // the host compiler's "no tap" form
+      if (counters[0] <= border_cap) {
+        p->plan_n_border = (int)counters[0];
+        pl.max_lds_bytes = counters[1];
+        pl.max_rect_w = (int)counters[2];
+        pl.max_rect_h = (int)counters[3];
+        pl.valid = true;
+        p->plan_on_device = true;
+        p->plan_uploaded = true;
+      }
+    }
+    if (!p->plan_on_device) {
+      need_host_map(p);
+      rip::compile_remap_plan(p->plan, p->h_map.data(), m.dist_h, m.dist_w, src_rows, src_cols);
+      p->plan_n_border = (int)p->plan.border.size();
+      p->plan_uploaded = false;
+    }
+  }
+  if (!p->plan_uploaded) {
+    p->d_plan_words.reserve(p->plan.words.size() * sizeof(uint32_t));
+    p->d_plan_tiles.reserve(p->plan.tiles.size() * sizeof(rip::RemapTile));
+    HIP_CHECK(hipMemcpyAsync(p->d_plan_words.ptr, p->plan.words.data(), p->plan.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             p->stream));
+    HIP_CHECK(hipMemcpyAsync(p->d_plan_tiles.ptr, p->plan.tiles.data(), p->plan.tiles.size() * sizeof(rip::RemapTile),
+                             hipMemcpyHostToDevice, p->stream));
+    p->d_plan_border.reserve(std::max<size_t>(4, p->plan.border.size() * sizeof(uint32_t)));
+    if (!p->plan.border.empty())
+      HIP_CHECK(hipMemcpyAsync(p->d_plan_border.ptr, p->plan.border.data(), p->plan.border.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    p->plan_uploaded = true;
+  }
+}
+
+// The fast chain kernel's items whose output the remap reads (rip::chain_footprint_items on the current plan's footprint), on
+// the device; uploaded once per (plan, flip).  Returns how many there are, or -1 when the footprint covers more than 95 % of
+// the frame (balance 1, wide fields of view): the dense walk is as good there and needs no table.
+static int ensure_chain_items(rip_pipeline* p, int rows, int cols, int flip_angle) {
+  if (p->chain_items_flip != flip_angle) {
+    std::vector<uint32_t> items;
+    rip::chain_footprint_items(p->plan.fp_lo, p->plan.fp_hi, rows, cols, flip_angle, items);
+    const long long dense = (long long)(rows / 2) * (cols / 4);
+    p->chain_items_n = (long long)items.size() * 20 > dense * 19 ? -1 : (int)items.size();
+    if (p->chain_items_n >= 0) {
+      p->d_chain_items.reserve(std::max<size_t>(4, items.size() * sizeof(uint32_t)));
+      if (!items.empty())
+        HIP_CHECK(hipMemcpyAsync(p->d_chain_items.ptr, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+      HIP_CHECK(hipStreamSynchronize(p->stream));
+    }
+    p->chain_items_flip = flip_angle;
+  }
+  return p->chain_items_n;
+}
+
+void ensure_maps(rip_pipeline* p) {
+  ensure_host_maps(p);
+  if (p->map_uploaded) return;
+  p->d_map.reserve(p->h_map.size() * sizeof(float));
+  HIP_CHECK(hipMemcpyAsync(p->d_map.ptr, p->h_map.data(), p->h_map.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
+  HIP_CHECK(hipStreamSynchronize(p->stream));
+  p->map_uploaded = true;
+}
+
+static void ensure_tables(rip_pipeline* p) {
+  if (!p->tabs_dirty) return;
+  LaunchLogScope log_scope(p);
+  rip::DevTables& t = p->h_tabs;
+  const rip::ColorTables& c = rip::color_tables();
+  rip::build_gamma_lut(p->m.gamma_k, t.gamma_lut);
+  for (int i = 0; i < 256; i++) t.lin_tab[i] = c.srgb_gamma[p->m.gamma_enabled ? t.gamma_lut[i] : i];
+  std::memcpy(t.cbrt_tab, c.cbrt, sizeof(t.cbrt_tab));
+  for (int i = 0; i < 256; i++) t.yf_tab[i] = (uint32_t)c.lab_to_yf[2 * i] | ((uint32_t)c.lab_to_yf[2 * i + 1] << 16);
+  for (int i = 0; i < 4096; i++) t.inv_gamma[i] = (uint8_t)std::min<int>(255, c.inv_gamma[i]);
+  std::memcpy(t.sdiv, c.sdiv, sizeof(t.sdiv));
+  std::memcpy(t.hdiv, c.hdiv180, sizeof(t.hdiv));
+  std::memcpy(t.lab_fwd, c.fwd, sizeof(t.lab_fwd));
+  std::memcpy(t.lab_inv, c.inv, sizeof(t.lab_inv));
+  for (int ch = 0; ch < 3; ch++) {
+    if (c.inv[ch * 3] < -32768 || c.inv[ch * 3] > 32767 || c.inv[ch * 3 + 1] < -32768 || c.inv[ch * 3 + 1] > 32767)
+      throw std::runtime_error("Lab inverse coefficients do not fit 16 bits");
+    t.lab_inv_pk[ch * 2] = (int32_t)(((uint32_t)c.inv[ch * 3] & 0xffffu) | ((uint32_t)c.inv[ch * 3 + 1] << 16));
+    t.lab_inv_pk[ch * 2 + 1] = c.inv[ch * 3 + 2];
+  }
+  std::vector<float> accum;
+  rip::ccc_build_scalar_tables(t.log_tab, accum, t.exp_neg_tab);
+  rip::fft256_twiddles(t.tw_re, t.tw_im);
+  p->d_tabs.reserve(sizeof(rip::DevTables));
+  HIP_CHECK(hipMemcpyAsync(p->d_tabs.ptr, &t, sizeof(t), hipMemcpyHostToDevice, p->stream));
+  p->d_vig_image.reserve(rip::vig_image_bytes());
+  rip::launch_vig_image(p->d_tabs.as<rip::DevTables>(), p->d_vig_image.as<uint32_t>(), p->stream);
+  if (!p->d_accum.ptr) {
+    p->d_accum.reserve(accum.size() * sizeof(float));
+    HIP_CHECK(hipMemcpyAsync(p->d_accum.ptr, accum.data(), accum.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(p->stream));  // host staging buffers go out of scope
+  p->tabs_dirty = false;
+}
+
+static void ensure_vignette(rip_pipeline* p, int rows, int cols) {
+  if (!p->vig_dirty && p->vig_rows == rows && p->vig_cols == cols) return;
+  rip::build_vignette_mask(rows, cols, p->m.vig_scale, p->m.vig_a2, p->m.vig_a4, p->h_vig, p->fp_contract);
+  p->d_vig.reserve(p->h_vig.size() * sizeof(float));
+  HIP_CHECK(hipMemcpyAsync(p->d_vig.ptr, p->h_vig.data(), p->h_vig.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
+  HIP_CHECK(hipStreamSynchronize(p->stream));
+  p->vig_rows = rows;
+  p->vig_cols = cols;
+  p->vig_dirty = false;
+}
+
+static void ensure_ccc(rip_pipeline* p, int rows, int cols) {
+  if (!p->ccc.loaded) {
+    if (!p->ccc_model_env.empty()) {
+      if (!rip::ccc_load_model_file(p->ccc, p->ccc_model_env)) throw InvalidArgument("RIP_CCC_MODEL: cannot read " + p->ccc_model_env);
+      p->ccc_uploaded = false;
+    } else {
+      throw InvalidArgument(
+          "white balance method [ccc] needs a model: call rip_load_ccc_model()/rip_set_ccc_model() or set RIP_CCC_MODEL "
+          "(the reference loads raw_image_pipeline_white_balance/model/default.bin)");
+    }
+  }
+  if (!p->ccc_uploaded) {
+    size_t bytes = 65536 * 2 * sizeof(float);
+    p->d_filter_fft.reserve(bytes);
+    p->d_bias_fft.reserve(bytes);
+    HIP_CHECK(hipMemcpyAsync(p->d_filter_fft.ptr, p->ccc.filter_fft.data(), bytes, hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipMemcpyAsync(p->d_bias_fft.ptr, p->ccc.bias_fft.data(), bytes, hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    p->ccc_uploaded = true;
+  }
+  if (!p->ccc_state_init) {
+    rip::CccState s = {};
+    s.first_frame = 1;
+    s.uv_x = s.uv_y = 128;  // uv_pos_ = (height/2, width/2), :178
+    s.st_x = s.st_y = 128.f;
+    s.kf_h = (float)p->kf_h;
+    s.kf_r = (float)p->kf_r;
+    s.temporal = p->m.wb_temporal ? 1 : 0;
+    p->d_ccc_state.reserve(sizeof(s));
+    HIP_CHECK(hipMemcpyAsync(p->d_ccc_state.ptr, &s, sizeof(s), hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    p->ccc_state_init = true;
+    p->ccc_reset_pending = false;
+    p->ccc_cfg_dirty = false;
+  }
+  if (p->ccc_reset_pending || p->ccc_cfg_dirty) {
+    // patch individual fields, stream-ordered, keeping the filter state
+    rip::CccState* d = p->d_ccc_state.as<rip::CccState>();
+    if (p->ccc_reset_pending) {
+      static const int one = 1;
+      HIP_CHECK(hipMemcpyAsync(&d->first_frame, &one, sizeof(int), hipMemcpyHostToDevice, p->stream));
+    }
+    float hr[2] = {(float)p->kf_h, (float)p->kf_r};
+    int temporal = p->m.wb_temporal ? 1 : 0;
+    HIP_CHECK(hipMemcpyAsync(&d->kf_h, hr, sizeof(hr), hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipMemcpyAsync(&d->temporal, &temporal, sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    p->ccc_reset_pending = false;
+    p->ccc_cfg_dirty = false;
+  }
+  if (p->geom_rows != rows || p->geom_cols != cols) {
+    // cv::resize(src, small, Size(360,270)) coefficient tables (imgproc/resize.cpp)
+    struct Geom {
+      int xofs[360];
+      short ialpha[720];
+      int yofs[540];
+      short ibeta[540];
+      int area_fast;
+    };
+    static_assert(sizeof(Geom) % 4 == 0, "geom");
+    std::vector<uint8_t> raw(sizeof(Geom));
+    Geom& g = *reinterpret_cast<Geom*>(raw.data());
+    double scale_x = (double)cols / 360, scale_y = (double)rows / 270;
+    int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
+    g.area_fast = (std::fabs(scale_x - isx) < 2.220446049250313e-16 && std::fabs(scale_y - isy) < 2.220446049250313e-16 && isx == 2 && isy == 2) ? 1 : 0;
+    auto sat16 = [](int v) { return (short)std::min(32767, std::max(-32768, v)); };
+    for (int dx = 0; dx < 360; dx++) {
+      float fx = (float)((dx + 0.5) * scale_x - 0.5);
+      int sx = (int)std::floor(fx);
+      fx -= sx;
+      if (sx < 0) { fx = 0; sx = 0; }
+      if (sx >= cols - 1) { fx = 0; sx = cols - 1; }
+      g.xofs[dx] = sx;
+      g.ialpha[2 * dx] = sat16((int)std::lrintf((1.f - fx) * 2048));
+      g.ialpha[2 * dx + 1] = sat16((int)std::lrintf(fx * 2048));
+    }
+    for (int dy = 0; dy < 270; dy++) {
+      float fy = (float)((dy + 0.5) * scale_y - 0.5);
+      int sy = (int)std::floor(fy);
+      fy -= sy;
+      g.ibeta[2 * dy] = sat16((int)std::lrintf((1.f - fy) * 2048));
+      g.ibeta[2 * dy + 1] = sat16((int)std::lrintf(fy * 2048));
+      g.yofs[2 * dy] = std::min(std::max(sy, 0), rows - 1);
+      g.yofs[2 * dy + 1] = std::min(std::max(sy + 1, 0), rows - 1);
+    }
+    p->d_geom.reserve(sizeof(Geom));
+    HIP_CHECK(hipMemcpyAsync(p->d_geom.ptr, raw.data(), sizeof(Geom), hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    p->geom_rows = rows;
+    p->geom_cols = cols;
+  }
+}
+
+namespace {
+
+// where a kernel reads its frames: the five source fields every parameter block of rip_kernels.hpp starts with
+template <typename Params>
+void set_source(Params& d, ConstFrameView src) {
+  d.src = src.ptr;
+  d.src_step = src.step;
+  d.src_frame_stride = src.frame_stride;
+  d.rows = src.rows;
+  d.cols = src.cols;
+}
+
+// The stand-alone demosaic kernels' common parameters (Raw16Params, MhtParams, Debayer16Params)
+template <typename Params>
+Params demosaic_params(const Plan& pl, ConstFrameView src, FrameView out, int n) {
+  Params d = {};
+  set_source(d, src);
+  d.bayer_ry = pl.ry;
+  d.bayer_rx = pl.rx;
+  d.dst = out.ptr;
+  d.dst_step = out.step;
+  d.dst_frame_stride = out.frame_stride;
+  d.flip_angle = pl.flip_angle;
+  d.n_frames = n;
+  return d;
+}
+
+// Malvar-He-Cutler demosaic (rip_set_debayer_method "mht", rip_demosaic.hip): one pass of its own writes the post-flip BGR
+// image -- the DEBAYERED tap (flip.cpp:60-62), into the caller's tap buffer when one was requested, else into d_mht -- and the
+// rest of the chain runs on that image exactly as on a bgr8 frame holding it, with no flip left to do.
+// 16-bit frames with a range (rip_set_debayer_16bit_range, rip_raw16.hip) and packed frames (rip_packed.hip) take the same
+// route with either method: demosaic at 16 bits + narrowing + flip in one pass, into the same destination.
+// 16-bit frames without a range (one kernel, no taps, either method): the pass writes the bgr16 result into the caller's
+// output and that is all.  Returns false then -- the batch is complete -- and otherwise true with the image it wrote in `bgr`.
+bool enqueue_demosaic_pass(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, ConstFrameView& bgr) {
+  const bool bgr16 = pl.out_elem_bytes == 2;
+  FrameView out = dst;
+  if (!bgr16) {
+    // tight when it is the tap; else 16-byte aligned rows and frames: what launch_remap_tiled asks of the image it gathers from
+    const size_t step = taps.debayered ? (size_t)pl.mid_cols * 3 : ((size_t)pl.mid_cols * 3 + 15) & ~(size_t)15;
+    out = {taps.debayered, step, step * pl.mid_rows, pl.mid_rows, pl.mid_cols};
+    if (!out.ptr) {
+      p->d_mht.reserve(out.frame_stride * (size_t)n);
+      out.ptr = p->d_mht.as<uint8_t>();
+    }
+  }
+  {
+    ProfScope ps(p, RIP_KERNEL_CHAIN, p->stream);
+    if (pl.raw16) {
+      rip::Raw16Params d = demosaic_params<rip::Raw16Params>(pl, src, out, n);
+      d.mht = pl.mht ? 1 : 0;
+      d.black = pl.black;
+      d.white = pl.white;
+      if (pl.packed_layout) rip::launch_packed(d, pl.packed_layout, p->stream);
+      else rip::launch_raw16(d, p->stream);
+    } else if (pl.mht) {
+      rip::MhtParams d = demosaic_params<rip::MhtParams>(pl, src, out, n);
+      d.elem_bytes = pl.in_elem_bytes;
+      d.drows = pl.mid_rows;
+      d.dcols = pl.mid_cols;
+      rip::launch_demosaic_mht(d, p->stream);
+    } else {  // 16-bit Bayer extension with the range off, bilinear
+      rip::Debayer16Params d = demosaic_params<rip::Debayer16Params>(pl, src, out, n);
+      d.drows = pl.out_rows;
+      d.dcols = pl.out_cols;
+      rip::launch_debayer16(d, p->stream);
+    }
+  }
+  hipError_t le = hipGetLastError();
+  if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+  if (bgr16) p->last_batch_frames = 0;  // no white balance ran: rip_get_white_balance_info must not hand out an earlier batch's gains
+  bgr = out;
+  return !bgr16;
+}
+
+// the plan of the frames enqueue_demosaic_pass wrote: plain bgr8, already flipped (their DEBAYERED tap is written too)
+Plan as_bgr8_after_demosaic(const Plan& pl) {
+  Plan s = pl;
+  s.raw16 = s.mht = false;
+  s.in_elem_bytes = 1;
+  s.packed_layout = 0;
+  s.src_kind = rip::SRC_BGR;
+  s.ry = s.rx = 0;
+  s.flip_angle = 0;
+  return s;
+}
+
+// Which kernels a batch goes through: decided once by plan_route, before the first launch, and executed by run_chain
+struct BatchRoute {
+  enum Remap {
+    NONE,         // no undistortion: the chain writes the caller's output
+    FUSED_BAYER,  // chain + remap in one kernel that reads the Bayer frames (rip_fused.hip)
+    DIRECT,       // no chain: the remap gathers from the caller's frames as they lie
+    DIRECT_MONO,  // ... and the ring kernel flips by 180 degrees and applies the gamma table as it gathers
+    AFTER_CHAIN   // the chain writes chain_dst, the remap gathers from it
+  } remap = NONE;
+  bool tiled = false;     // the plan is compiled and the tiled / ring kernel is tried first
+  bool no_tap = true;     // neither tap requested
+  FrameView chain_dst{};  // the caller's output, the COLOR tap, or d_mid (16-byte pitch)
+  int chain_items = -1;   // -1 dense, else the footprint list's length
+  int groups = 1, per_group = 0;  // overlap_groups split (1 = off)
+  hipStream_t back = nullptr;     // the remap's stream: the handle's internal one with groups > 1, else the caller's
+};
+
+// white-balance methods estimated from per-frame sums (FrameStats)
+bool wb_from_sums(const Plan& pl) { return pl.wb_mode == rip::WB_Q8 || pl.wb_mode == rip::WB_PCA || pl.wb_mode == rip::WB_SIMPLE; }
+
+// the remap's view of ng frames: plan, destination (frames f0.. of dst), and -- `src` -- either the intermediate image or, on
+// the fused and direct routes, the caller's frames themselves
+rip::RemapTiledParams remap_params(const rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, int f0, int ng) {
+  rip::RemapTiledParams tp = {};
+  rip::RemapParams& r = tp.base;
+  set_source(r, src);
+  r.channels = pl.channels;
+  r.map_xy = p->d_map.as<float>();
+  r.dst = dst.ptr + (size_t)f0 * dst.frame_stride;
+  r.dst_step = dst.step;
+  r.dst_frame_stride = dst.frame_stride;
+  r.drows = pl.out_rows;
+  r.dcols = pl.out_cols;
+  r.n_frames = ng;
+  tp.words = p->d_plan_words.as<uint32_t>();
+  tp.tiles = p->d_plan_tiles.as<rip::RemapTileDesc>();
+  tp.tiles_x = p->plan.tiles_x;
+  tp.tiles_y = p->plan.tiles_y;
+  tp.border_list = p->d_plan_border.as<uint32_t>();
+  tp.n_border = p->plan_n_border;
+  tp.lds_bytes = (unsigned)p->plan.max_lds_bytes;
+  return tp;
+}
+// DIRECT_MONO: the chain's two operations, done by the ring kernel
+rip::RemapTiledParams mono_ops(const rip_pipeline* p, const Plan& pl, rip::RemapTiledParams tp) {
+  tp.mono_lut = (pl.stage_bits & rip::ST_GAMMA) ? p->d_tabs.as<uint8_t>() + offsetof(rip::DevTables, gamma_lut) : nullptr;
+  tp.mono_flip180 = pl.flip_angle == 180 ? 1 : 0;
+  return tp;
+}
+// the chain's parameters for ng frames (dst / taps filled in by the caller)
+rip::ChainParams chain_params(const rip_pipeline* p, const Plan& pl, ConstFrameView src, rip::FrameWb* wb, int ng) {
+  rip::ChainParams c = {};
+  set_source(c, src);
+  c.src_kind = pl.src_kind;
+  c.bayer_ry = pl.ry;
+  c.bayer_rx = pl.rx;
+  c.drows = pl.mid_rows;
+  c.dcols = pl.mid_cols;
+  c.channels = pl.channels;
+  c.flip_angle = pl.flip_angle;
+  c.n_frames = ng;
+  c.wb_mode = pl.wb_mode;
+  c.wb = wb;
+  c.stage_bits = pl.stage_bits;
+  for (int i = 0; i < 9; i++) c.cc_m[i] = p->m.cc_matrix[i];
+  for (int i = 0; i < 3; i++) c.cc_bias[i] = (float)p->m.cc_bias[i];
+  if (pl.stage_bits & rip::ST_VIG) c.vig_mask = p->d_vig.as<float>();
+  // cv::Scalar(hue_gain_, saturation_gain_, value_gain_) on (H,S,V), color_enhancer.cpp:42
+  c.hsv_gain[0] = (float)p->m.ce_hue_gain;
+  c.hsv_gain[1] = (float)p->m.ce_saturation_gain;
+  c.hsv_gain[2] = (float)p->m.ce_value_gain;
+  c.tabs = p->d_tabs.as<rip::DevTables>();
+  c.vig_image = p->d_vig_image.as<uint32_t>();
+  c.fp_contract = p->fp_contract;
+  return c;
+}
+
+// Everything that allocates, uploads or synchronises happens here, before the first launch of the chain; the two dry runs ask
+// the fused and the ring kernel whether they take the geometry.
+BatchRoute plan_route(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb) {
+  BatchRoute rt;
+  rt.no_tap = !taps.color && !taps.debayered;
+  rt.chain_dst = dst;
+  p->d_wb.reserve(sizeof(rip::FrameWb) * (size_t)n);
+  if (reuse_wb) {
+    if (p->last_batch_frames != n) throw DeviceError("internal: white-balance gains of another batch");
+  } else if (wb_from_sums(pl)) {
+    p->d_stats.reserve(sizeof(rip::FrameStats) * (size_t)n);
+    if (pl.wb_mode == rip::WB_SIMPLE) p->d_hist.reserve((size_t)n * 768 * sizeof(unsigned));
+  } else if (pl.wb_mode == rip::WB_FLOAT) {
+    ensure_ccc(p, pl.mid_rows, pl.mid_cols);
+    p->d_hist.reserve((size_t)n * rip::ccc_hist_split(n) * 65536 * sizeof(unsigned));
+    p->d_work.reserve((size_t)n * 65536 * 2 * sizeof(float));
+    p->d_rowbest.reserve((size_t)n * 256 * 2 * sizeof(float));
+    p->d_argmax.reserve((size_t)n * 2 * sizeof(int));
+  }
+  if (pl.remap) {
+    ensure_maps(p);
+    if (p->use_tiled_remap && (pl.channels == 3 || pl.channels == 1)) {
+      ensure_plan(p, pl.mid_rows, pl.mid_cols);
+      rt.tiled = true;
+    }
+    rt.remap = BatchRoute::AFTER_CHAIN;
+    // Memory-rate stage sets with neither tap requested: the remap's tiles demosaic and colour their own source rectangles
+    // out of the Bayer frames (rip_fused.hip) -- no intermediate image is written, read or even allocated.
+    if (rt.tiled && rt.no_tap && pl.src_kind == rip::SRC_BAYER &&
+        rip::launch_remap_fused(remap_params(p, pl, src, dst, 0, n), chain_params(p, pl, src, p->d_wb.as<rip::FrameWb>(), n), p->plan.max_rect_w,
+                                p->plan.max_rect_h, p->tn, p->stream, /*dry_run=*/true))
+      rt.remap = BatchRoute::FUSED_BAYER;
+    // bgr8 / mono8 frames with nothing to do before the undistortion (no flip, no white balance, no stage, no tap): the
+    // chain would be a copy -- the remap gathers from the caller's frames as they lie
+    else if (rt.no_tap && (pl.src_kind == rip::SRC_BGR || pl.src_kind == rip::SRC_MONO) && pl.flip_angle == 0 && pl.wb_mode == rip::WB_NONE &&
+             pl.stage_bits == 0)
+      rt.remap = BatchRoute::DIRECT;
+    // mono8: the whole chain is a 180-degree flip and the gamma table -- the ring kernel addresses the mirrored rectangle
+    // and maps the taps through the table as it gathers them
+    else if (rt.tiled && rt.no_tap && pl.src_kind == rip::SRC_MONO && (pl.flip_angle == 0 || pl.flip_angle == 180) && p->tn.remap_fused &&
+             rip::launch_remap_tiled(mono_ops(p, pl, remap_params(p, pl, src, dst, 0, n)), p->tn, p->stream, /*dry_run=*/true))
+      rt.remap = BatchRoute::DIRECT_MONO;
+    // The pre-undistortion image: tightly packed when it is an API output (the COLOR tap: written once, gathered from), else
+    // internal with 16-byte aligned rows (the tiled remap stages it with aligned 16-byte loads)
+    const size_t tap_pitch = (size_t)pl.mid_cols * pl.channels;
+    const size_t mid_pitch = taps.color ? tap_pitch : ((tap_pitch + 15) & ~(size_t)15);
+    rt.chain_dst = {taps.color, mid_pitch, mid_pitch * pl.mid_rows, pl.mid_rows, pl.mid_cols};
+    if (rt.remap == BatchRoute::AFTER_CHAIN && !taps.color) {
+      p->d_mid.reserve(rt.chain_dst.frame_stride * (size_t)n);
+      rt.chain_dst.ptr = p->d_mid.as<uint8_t>();
+    }
+  }
+  // In front of the remap, with no tap asking for the whole intermediate image, the fast Bayer kernel computes only the items
+  // whose pixels the remap reads (its plan's footprint: the corners a fisheye map never samples are ~21 % of config 2's frame).
+  // The statistics pass above it still reads every pixel: the white-balance estimates are defined over the whole frame.
+  const int rows = src.rows, cols = src.cols;
+  if (rt.tiled && rt.remap == BatchRoute::AFTER_CHAIN && rt.no_tap && p->tn.chain_footprint && pl.src_kind == rip::SRC_BAYER && pl.channels == 3 &&
+      (pl.flip_angle == 0 || pl.flip_angle == 180) && rows % 2 == 0 && cols % 4 == 0 && rows / 2 <= 65535 && cols / 4 <= 65535 &&
+      rows == pl.mid_rows && cols == pl.mid_cols && p->plan.fp_lo.size() == (size_t)(rows + 1) / 2)
+    rt.chain_items = ensure_chain_items(p, rows, cols, pl.flip_angle);
+  if (pl.stage_bits & rip::ST_VIG) ensure_vignette(p, pl.mid_rows, pl.mid_cols);
+  // Frame groups (tunable overlap_groups > 1; OFF by default): with the batch cut into G groups of frames, remap(g) runs on the
+  // handle's internal stream beside stats(g + 1) and chain(g + 1) on the caller's stream (overlap_mode 1), or beside stats(g + 1)
+  // only (mode 2: the chain waits for the remap).  raw_image_pipeline.hpp:143-172 only orders the stages of ONE frame, and
+  // everything that carries state from frame to frame -- the ccc Kalman filter -- stays on the caller's stream in frame order;
+  // the caller's stream waits for the internal one before run_chain returns, so the batch is complete in stream order
+  // exactly as without the split.  Measured on config2 (256 frames, one box, round 3): 4.87 ms per step unsplit; mode 1 with
+  // 2 / 4 / 8 / 16 groups 4.98 / 5.00 / 5.09 / 5.70; mode 2 with 2 / 4 groups 4.94 / 5.05 -- the three kernels lean on the
+  // same VALU issue slots and LDS, and the shorter launches pay their tails (docs/experiments_r1-3.md), so the default stays 1.
+  if (pl.remap && !reuse_wb && p->tn.overlap_groups > 1) rt.groups = std::min(p->tn.overlap_groups, n);
+  rt.back = p->stream;
+  if (rt.groups > 1) {
+    if (!p->aux_stream) HIP_CHECK(hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking));
+    while (p->ovl_events.size() < 2 * (size_t)rt.groups + 1) {
+      hipEvent_t e;
+      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      p->ovl_events.push_back(e);
+    }
+    rt.back = p->aux_stream;
+  }
+  rt.per_group = (n + rt.groups - 1) / rt.groups;
+  return rt;
+}
+
+// The white-balance estimate of frames f0 .. f0 + ng of a batch of n: statistics and finalisation, gains into d_wb[f0..].
+// stats_clean_before: the prefix of d_stats known to be zero when the batch began.
+void enqueue_wb_estimate(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, ConstFrameView src, int f0, int ng, int n, size_t stats_clean_before) {
+  const hipStream_t front = p->stream;
+  rip::FrameWb* wb_g = p->d_wb.as<rip::FrameWb>() + f0;
+  if (wb_from_sums(pl)) {
+    rip::FrameStats* stats_g = p->d_stats.as<rip::FrameStats>() + f0;
+    unsigned* hist_g = pl.wb_mode == rip::WB_SIMPLE ? p->d_hist.as<unsigned>() + (size_t)f0 * 768 : nullptr;
+    if (hist_g) p->hist_clean_bytes = 0;  // the same buffer serves SimpleWB's histograms
+    // grey-world / pca: the statistics kernel itself finishes a frame (gains written by the workgroup that ends last) and
+    // hands its FrameStats back zeroed, so neither a memset nor a finalisation launch separates the batches -- two
+    // dependent launches less on the single-frame path.  The records are cleared here only when they are not known to be
+    // clean: fresh memory, or a batch that did not run to its end.
+    const bool fused_finalize = pl.wb_mode != rip::WB_SIMPLE;
+    const size_t stats_bytes = sizeof(rip::FrameStats) * (size_t)n;
+    if (!fused_finalize || stats_clean_before < stats_bytes) HIP_CHECK(hipMemsetAsync(stats_g, 0, sizeof(rip::FrameStats) * (size_t)ng, front));
+    p->stats_clean_bytes = 0;  // until this batch has been enqueued completely
+    if (hist_g) HIP_CHECK(hipMemsetAsync(hist_g, 0, (size_t)ng * 768 * sizeof(unsigned), front));
+    rip::StatsParams sp = {};
+    set_source(sp, src);
+    sp.src_kind = pl.src_kind;
+    sp.bayer_ry = pl.ry;
+    sp.bayer_rx = pl.rx;
+    sp.n_frames = ng;
+    sp.mode = pl.wb_mode;
+    sp.thresh255 = (unsigned)(uint16_t)std::lrintf((float)p->m.wb_bright_thr * 255);
+    sp.stats = stats_g;
+    sp.hist3 = hist_g;
+    sp.wb_out = fused_finalize ? wb_g : nullptr;
+    {
+      ProfScope ps(p, RIP_KERNEL_STATS, front);
+      rip::launch_stats(sp, p->tn, front);
+    }
+    // SimpleWB::setP(clipping_percentile_) (white_balance.cpp:55); total = pixels per channel plane
+    if (!fused_finalize)
+      rip::launch_wb_finalize(pl.wb_mode, sp.stats, nullptr, nullptr, p->d_tabs.as<rip::DevTables>(), wb_g, ng, front, sp.hist3,
+                              (float)p->m.wb_percentile, src.rows * src.cols);
+  } else if (pl.wb_mode == rip::WB_FLOAT) {
+    rip::CccParams cp = {};  // the launcher zeroes the histogram when its kernel accumulates in HBM
+    set_source(cp, src);
+    cp.src_kind = pl.src_kind;
+    cp.bayer_ry = pl.ry;
+    cp.bayer_rx = pl.rx;
+    cp.flip_angle = pl.flip_angle;
+    cp.drows = pl.mid_rows;
+    cp.dcols = pl.mid_cols;
+    cp.n_frames = ng;
+    const uint8_t* gm = p->d_geom.as<uint8_t>();
+    cp.geom.xofs = reinterpret_cast<const int*>(gm);
+    cp.geom.ialpha = reinterpret_cast<const short*>(gm + 360 * 4);
+    cp.geom.yofs = reinterpret_cast<const int*>(gm + 360 * 4 + 720 * 2);
+    cp.geom.ibeta = reinterpret_cast<const short*>(gm + 360 * 4 + 720 * 2 + 540 * 4);
+    cp.geom.area_fast = ((double)pl.mid_cols / 360 == 2.0 && (double)pl.mid_rows / 270 == 2.0) ? 1 : 0;
+    // setSaturationThreshold(float, float): thresholds are held as float (:437-440); 255 * thr in float
+    cp.upper = 255 * (float)p->m.wb_bright_thr;
+    cp.lower = 255 * (float)p->m.wb_dark_thr;
+    cp.hist_split = rip::ccc_hist_split(n);  // of the whole batch: what d_hist was sized for
+    cp.hist_counts = p->d_hist.as<unsigned>() + (size_t)f0 * cp.hist_split * 65536;
+    cp.accum_tab = p->d_accum.as<float>();
+    cp.work = p->d_work.as<float>() + (size_t)f0 * 65536 * 2;
+    cp.filter_fft = p->d_filter_fft.as<float>();
+    cp.bias_fft = p->d_bias_fft.as<float>();
+    cp.row_best = p->d_rowbest.as<float>() + (size_t)f0 * 256 * 2;
+    cp.argmax = p->d_argmax.as<int>() + (size_t)f0 * 2;
+    cp.tabs = p->d_tabs.as<rip::DevTables>();
+    const size_t hist_bytes = (size_t)ng * 65536 * sizeof(unsigned);  // what the global-atomic kernel accumulates into
+    cp.hist_is_clean = (rt.groups == 1 && p->hist_clean_ptr == p->d_hist.ptr && p->hist_clean_cap == p->d_hist.cap && p->hist_clean_bytes >= hist_bytes) ? 1 : 0;
+    p->hist_clean_bytes = 0;  // until the estimator has been enqueued completely
+    bool estimated;
+    int left_clean = 0;
+    {
+      ProfScope ps(p, RIP_KERNEL_CCC, front);
+      estimated = rip::launch_ccc_estimate(cp, p->tn, front, &left_clean);
+    }
+    // no histogram, no estimate: fail before the finalisation advances the persistent Kalman state on stale data
+    if (!estimated) throw DeviceError("ccc white balance: a kernel of the estimator could not be launched");
+    if (left_clean && rt.groups == 1) {
+      p->hist_clean_ptr = p->d_hist.ptr;
+      p->hist_clean_cap = p->d_hist.cap;
+      p->hist_clean_bytes = hist_bytes;
+    }
+    const bool inline_argmax = rip::ccc_argmax_in_finalize(ng);
+    rip::launch_wb_finalize(rip::WB_FLOAT, nullptr, cp.argmax, p->d_ccc_state.as<rip::CccState>(), cp.tabs, wb_g, ng, front, nullptr, 0.f, 0,
+                            inline_argmax ? cp.row_best : nullptr, inline_argmax ? cp.argmax : nullptr);
+  }
+}
+
+// FUSED_BAYER: chain + remap of group g in one kernel (memory-rate stage sets, no taps)
+void enqueue_fused_remap(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, int f0, int ng, int n) {
+  ProfScope ps(p, RIP_KERNEL_REMAP, p->stream);
+  rip::ChainParams fc = chain_params(p, pl, src, p->d_wb.as<rip::FrameWb>() + f0, ng);
+  fc.dst_streaming = (n >= 8 && p->tn.chain_nt != 0) ? 1 : 0;  // the kernel's output is the batch's final image: non-temporal stores for batches
+  if (!rip::launch_remap_fused(remap_params(p, pl, src, dst, f0, ng), fc, p->plan.max_rect_w, p->plan.max_rect_h, p->tn, p->stream, /*dry_run=*/false))
+    throw DeviceError("internal: the fused remap refused a geometry it had accepted");
+}
+
+// The fused chain of group g (frames f0 .. f0 + ng of n) into the route's chain_dst, the DEBAYERED tap beside it
+void enqueue_chain(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, ConstFrameView src, FrameView dst, Taps taps, int g, int f0, int ng, int n) {
+  const hipStream_t front = p->stream;
+  const size_t tap_pitch = (size_t)pl.mid_cols * pl.channels, tap_frame = tap_pitch * pl.mid_rows;  // taps are tightly packed API outputs
+  rip::ChainParams c = chain_params(p, pl, src, p->d_wb.as<rip::FrameWb>() + f0, ng);
+  c.dst = rt.chain_dst.ptr + (size_t)f0 * rt.chain_dst.frame_stride;
+  c.dst_step = rt.chain_dst.step;
+  c.dst_frame_stride = rt.chain_dst.frame_stride;
+  // Non-temporal stores for batches: the image is far larger than the L2s, so lines the chain leaves there only get in the
+  // way.  Rounds 3-4 kept them for images no kernel of the batch reads again (debayer-only, 256 frames: 1.08 against 1.16
+  // ms; the remap of that time lost 19 % behind them); with the LDS-DMA ring remap it is the other way round (round 5, config 2:
+  // remap 1.94-1.97 -> 1.83-1.85 ms behind a chain that stores non-temporally) -- tunable chain_nt
+  c.dst_streaming = (n >= 8 && p->tn.chain_nt != 0 && (!pl.remap || p->tn.chain_nt < 0)) ? 1 : 0;
+  c.tap = taps.debayered ? taps.debayered + (size_t)f0 * tap_frame : nullptr;
+  c.tap_frame_stride = tap_frame;
+  c.deal = pl.remap ? -1 : 0;  // hint for launch_chain: the remap gathers from this image next (Tunables::chain_deal)
+  if (rt.chain_items >= 0 && rip::chain_uses_fast_path(c)) {
+    c.item_list = p->d_chain_items.as<uint32_t>();
+    c.n_list_items = rt.chain_items;
+  }
+  p->last_chain_walked = c.item_list ? rt.chain_items : (src.rows / 2) * (src.cols / 4);
+  // overlap_mode 2: only the statistics of this group share the chip with the remap of the previous one; the chain waits
+  if (rt.back != front && p->tn.overlap_mode == 2 && g > 0) HIP_CHECK(hipStreamWaitEvent(front, p->ovl_events[rt.groups + g - 1], 0));
+  {
+    ProfScope ps(p, RIP_KERNEL_CHAIN, front);
+    rip::launch_chain(c, p->tn, front);
+  }
+  if (!pl.remap && taps.color) {
+    // pre-undistortion copy == final image when no remap follows
+    for (int f = f0; f < f0 + ng; f++)
+      HIP_CHECK(hipMemcpy2DAsync(taps.color + (size_t)f * tap_frame, tap_pitch, dst.ptr + (size_t)f * dst.frame_stride, dst.step, tap_pitch,
+                                 (size_t)pl.mid_rows, hipMemcpyDeviceToDevice, front));
+  }
+}
+
+// The undistortion of one group on `stream`: the tiled / ring kernel where the route has a compiled plan and the kernel takes
+// the geometry, else the plain gather.  DIRECT_MONO has no second choice: the plain gather neither flips nor applies the table.
+void enqueue_remap(rip_pipeline* p, const BatchRoute& rt, const rip::RemapTiledParams& tp, hipStream_t stream) {
+  bool done = false;
+  if (rt.tiled) {
+    ProfScope ps(p, RIP_KERNEL_REMAP, stream);
+    done = rip::launch_remap_tiled(tp, p->tn, stream);
+  }
+  if (!done && rt.remap == BatchRoute::DIRECT_MONO) throw DeviceError("internal: the ring remap refused a geometry it had accepted");
+  if (!done) {
+    ProfScope ps(p, RIP_KERNEL_REMAP, stream);
+    if (!rip::launch_remap(tp.base, stream)) throw InvalidArgument("undistortion: frame geometry exceeds the kernels' 32-bit addressing");
+  }
+}
+
+// The chain on 8-bit frames, from the white-balance estimate to the undistorted image
+void run_chain(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb) {
+  ensure_tables(p);
+  const BatchRoute rt = plan_route(p, pl, src, dst, taps, n, reuse_wb);
+  const size_t stats_clean_before = (p->stats_clean_ptr == p->d_stats.ptr && p->stats_clean_cap == p->d_stats.cap) ? p->stats_clean_bytes : 0;
+  const hipStream_t front = p->stream, back = rt.back;
+  const int groups = rt.groups;
+  // Whatever was enqueued on the internal stream is joined into the caller's stream when this function is left -- also by
+  // an exception: the batch is complete, in the caller's stream order, once the last remap is.
+  struct Join {
+    rip_pipeline* p;
+    int slot;
+    bool used = false;
+    ~Join() {
+      if (!used) return;
+      (void)hipEventRecord(p->ovl_events[slot], p->aux_stream);
+      (void)hipStreamWaitEvent(p->stream, p->ovl_events[slot], 0);
+    }
+  } join{p, 2 * groups};
+  for (int g = 0; g < groups; g++) {
+    const int f0 = g * rt.per_group, ng = std::min(rt.per_group, n - f0);
+    if (ng <= 0) break;
+    const ConstFrameView src_g = frames_from(src, f0);
+    if (!reuse_wb) enqueue_wb_estimate(p, pl, rt, src_g, f0, ng, n, stats_clean_before);
+    if (rt.remap == BatchRoute::FUSED_BAYER) {
+      enqueue_fused_remap(p, pl, src_g, dst, f0, ng, n);
+    } else if (rt.remap == BatchRoute::DIRECT) {  // no chain at all: the remap reads the input frames
+      enqueue_remap(p, rt, remap_params(p, pl, src_g, dst, f0, ng), front);
+    } else if (rt.remap == BatchRoute::DIRECT_MONO) {
+      enqueue_remap(p, rt, mono_ops(p, pl, remap_params(p, pl, src_g, dst, f0, ng)), front);
+    } else {
+      enqueue_chain(p, pl, rt, src_g, dst, taps, g, f0, ng, n);
+      if (rt.remap == BatchRoute::NONE) continue;
+      if (back != front) {  // remap(g) starts when chain(g) is done; the caller's stream goes on with group g + 1
+        HIP_CHECK(hipEventRecord(p->ovl_events[g], front));
+        HIP_CHECK(hipStreamWaitEvent(back, p->ovl_events[g], 0));
+        join.used = true;
+      }
+      enqueue_remap(p, rt, remap_params(p, pl, frames_from(ConstFrameView(rt.chain_dst), f0), dst, f0, ng), back);
+      if (back != front && p->tn.overlap_mode == 2) HIP_CHECK(hipEventRecord(p->ovl_events[groups + g], back));
+    }
+  }
+  p->last_batch_frames = n;
+  hipError_t le = hipGetLastError();
+  if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+  if (wb_from_sums(pl) && !reuse_wb && pl.wb_mode != rip::WB_SIMPLE) {  // every statistics launch went out: its records come back zeroed
+    p->stats_clean_ptr = p->d_stats.ptr;
+    p->stats_clean_cap = p->d_stats.cap;
+    p->stats_clean_bytes = std::max(stats_clean_before, sizeof(rip::FrameStats) * (size_t)n);
+  }
+}
+
+}  // namespace
+
+// Enqueues the whole chain for n frames of `src` into `dst`; either tap may be null.
+// reuse_wb: the white-balance gains of the previous launch (same frames) are applied again and no estimator runs -- the
+// debug stage dumps re-run prefixes of the chain without advancing the ccc Kalman state.
+void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb) {
+  p->work_enqueued = true;  // from here on something may sit on p->stream
+  DeviceGuard device_guard(p->device);
+  LaunchLogScope log_scope(p);
+  if (!pl.raw16 && !pl.mht && pl.out_elem_bytes == 1) {  // the chain demosaics by itself (bilinear, 8 bits)
+    run_chain(p, pl, src, dst, taps, n, reuse_wb);
+    return;
+  }
+  ConstFrameView bgr;
+  if (enqueue_demosaic_pass(p, pl, src, dst, taps, n, bgr)) run_chain(p, as_bgr8_after_demosaic(pl), bgr, dst, {nullptr, taps.color}, n, reuse_wb);
+}
+
+// pitch of the staging image in front of the converter: every source row starts 16-byte aligned
+size_t fmt_pitch(const Plan& pl) { return ((size_t)pl.out_cols * 3 + 15) & ~(size_t)15; }
+
+// The planar formats' table on the device, rebuilt on the host (rip::build_output_table) when the format or the normalisation
+// has changed since the last frame
+static void ensure_output_table(rip_pipeline* p, int fmt) {
+  if (!p->out_tab_dirty) return;
+  const size_t bytes = 768 * (size_t)rip::output_format_elem_bytes(fmt);
+  p->h_out_tab.resize(bytes);
+  rip::build_output_table(fmt, p->m.out_divisor, p->m.out_mean, p->m.out_std, p->h_out_tab.data());
+  p->d_out_tab.reserve(768 * 4);
+  HIP_CHECK(hipMemcpyAsync(p->d_out_tab.ptr, p->h_out_tab.data(), bytes, hipMemcpyHostToDevice, p->stream));
+  HIP_CHECK(hipStreamSynchronize(p->stream));
+  p->out_tab_dirty = false;
+}
+
+// run_batch with the output stage behind it: under a format the chain's last kernel writes the pipeline's image into the
+// handle's staging buffer and one launch of the converter (librip_out_hip.so) writes the caller's buffer; "native" is run_batch.
+// dst: the DELIVERED frames.
+void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n) {
+  if (pl.out_fmt == rip::OUT_NATIVE) {
+    run_batch(p, pl, src, dst, taps, n);
+    return;
+  }
+  DeviceGuard device_guard(p->device);
+  FrameView staged = {nullptr, fmt_pitch(pl), fmt_pitch(pl) * (size_t)pl.out_rows, pl.out_rows, pl.out_cols};
+  p->d_fmt.reserve(staged.frame_stride * (size_t)n);
+  staged.ptr = p->d_fmt.as<uint8_t>();
+  if (pl.dl_planar) ensure_output_table(p, pl.out_fmt);
+  run_batch(p, pl, src, staged, taps, n);
+  rip::OutputConvertParams c = {};
+  c.src = staged.ptr;
+  c.src_step = staged.step;
+  c.src_frame_stride = staged.frame_stride;
+  c.dst = dst.ptr;
+  c.dst_step = dst.step;
+  c.dst_frame_stride = dst.frame_stride;
+  c.rows = pl.out_rows;
+  c.cols = pl.out_cols;
+  c.n_frames = n;
+  c.format = pl.out_fmt;
+  c.table = pl.dl_planar ? p->d_out_tab.ptr : nullptr;
+  rip::OutputLaunchInfo info = {};
+  if (!rip::launch_output_convert(c, p->stream, &info)) throw DeviceError("internal: the output converter refused a layout the frame call had accepted");
+  hipError_t le = hipGetLastError();
+  if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+  LaunchLogScope log_scope(p);
+  RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+}
+
+// setDebug(true): raw_image_pipeline.hpp:143-172 writes the image after EVERY module -- enabled or not -- to
+// /tmp/0N_<module>.png through saveDebugImage (:179-186: copy, cv::normalize(0, 255, NORM_MINMAX), cv::imwrite).  The modules
+// are one fused kernel here, so the image after module k is produced by running the chain once more with the modules after k
+// switched off (same input frame still on the device: src; same white-balance gains: reuse_wb).  RIP_DEBUG_DIR replaces /tmp.
+void write_debug_dumps(rip_pipeline* p, const Plan& pl, ConstFrameView src, const uint8_t* final_image) {
+  static const char* const kNames[8] = {"00_debayer", "01_flip", "02_white_balancing", "03_color_calibration", "04_gamma_correction",
+                                        "05_vignetting_correction", "06_color_enhancer", "07_undistortion"};
+  static const int kStages[8] = {0, 0, 0, rip::ST_CC, rip::ST_CC | rip::ST_GAMMA, rip::ST_CC | rip::ST_GAMMA | rip::ST_VIG,
+                                 rip::ST_CC | rip::ST_GAMMA | rip::ST_VIG | rip::ST_HSV, rip::ST_CC | rip::ST_GAMMA | rip::ST_VIG | rip::ST_HSV};
+  const std::string& dir = p->debug_dir;
+  std::vector<uint8_t> host;
+  // the re-runs below are not launches of the caller's frame: keep them out of an active rip_profile_begin/end session
+  // (they would skew its per-class averages and use up its event slots), and out of the launch record (rip_debug_launch_log)
+  struct ProfPause {
+    rip_pipeline* p;
+    bool was, log_was;
+    explicit ProfPause(rip_pipeline* pp) : p(pp), was(pp->prof_on), log_was(pp->launch_log_on) { p->prof_on = p->launch_log_on = false; }
+    ~ProfPause() {
+      p->prof_on = was;
+      p->launch_log_on = log_was;
+    }
+  } prof_pause(p);
+  std::string failed;
+  for (int k = 0; k < 8; k++) {
+    int r, c;
+    if (k == 7) {  // after the undistortion module: the output of this call
+      r = pl.out_rows;
+      c = pl.out_cols;
+      host.assign(final_image, final_image + (size_t)r * c * pl.channels);
+    } else {
+      Plan s = pl;
+      s.remap = false;
+      if (k < 1) s.flip_angle = 0;
+      const bool swap = s.flip_angle == 90 || s.flip_angle == 270;
+      s.mid_rows = swap ? src.cols : src.rows;
+      s.mid_cols = swap ? src.rows : src.cols;
+      if (k < 2) s.wb_mode = rip::WB_NONE;
+      s.stage_bits &= kStages[k];
+      s.out_rows = r = s.mid_rows;
+      s.out_cols = c = s.mid_cols;
+      const size_t bytes = (size_t)r * c * s.channels;
+      p->d_dbg.reserve(bytes);
+      run_batch(p, s, src, {p->d_dbg.as<uint8_t>(), (size_t)c * s.channels, bytes, r, c}, {nullptr, nullptr}, 1, /*reuse_wb=*/true);
+      host.resize(bytes);
+      HIP_CHECK(hipMemcpyAsync(host.data(), p->d_dbg.ptr, bytes, hipMemcpyDeviceToHost, p->stream));
+      HIP_CHECK(hipStreamSynchronize(p->stream));
+    }
+    rip::normalize_minmax_u8(host.data(), host.size());
+    const std::string path = dir + "/" + kNames[k] + ".png";
+    if (!rip::write_png(path, host.data(), r, c, pl.channels)) {
+      std::fprintf(stderr, "raw_image_pipeline: could not write %s\n", path.c_str());
+      failed += (failed.empty() ? "" : ", ") + path;
+    }
+  }
+  // cv::imwrite's failure does not fail apply() in the reference either; the message stays readable through rip_last_error()
+  if (!failed.empty()) p->last_error = "debug dumps not written: " + failed;
+}
+
+}  // namespace rip::api

@@ -1,0 +1,349 @@
+// rip_handle.hpp -- internal to librip_hip.so (not installed): the handle behind include/rip.h and what the host units
+// share.  rip_plan.cpp turns a frame's geometry and encoding into a Plan, rip_batch.cpp enqueues the kernels of a batch,
+// rip_ring.cpp holds the host-frame calls and their ring, rip_api.cpp the rest of the C ABI.
+#pragma once
+#include "../../include/rip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "rip_host.hpp"
+#include "rip_kernels.hpp"
+#include "rip_output.hpp"
+
+namespace rip {
+// Launch record (rip_kernels.hpp): the text of a handle's log, one launch per line
+struct LaunchLog {
+  std::string text;
+};
+}  // namespace rip
+
+namespace rip::api {
+
+struct InvalidArgument : std::invalid_argument {
+  using std::invalid_argument::invalid_argument;
+};
+struct AssertError : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+struct DeviceError : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+struct CapacityError : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+
+#define HIP_CHECK(expr)                                                                                  \
+  do {                                                                                                   \
+    hipError_t err_ = (expr);                                                                            \
+    if (err_ != hipSuccess)                                                                              \
+      throw ::rip::api::DeviceError(std::string(#expr) + " failed: " + hipGetErrorString(err_) + " (" + __FILE__ + \
+                        ":" + std::to_string(__LINE__) + ")");                                           \
+  } while (0)
+
+// Grow-only device buffer; frees its memory when it goes out of scope (on the device that is current then: handles
+// release theirs explicitly under their own device in ~rip_pipeline)
+struct DevBuf {
+  void* ptr = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void reserve(size_t bytes) {
+    if (bytes <= cap) return;
+    if (ptr) HIP_CHECK(hipFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+    size_t want = bytes + bytes / 8;
+    HIP_CHECK(hipMalloc(&ptr, want));
+    cap = want;
+    // RIP_TRACE_ALLOC=1: one line per device allocation on stderr (tools/probes/remap_modes_probe.py relates the per-process
+    // modes of the remap's duration to where its buffers landed)
+    static const bool trace = std::getenv("RIP_TRACE_ALLOC") != nullptr;
+    if (trace) std::fprintf(stderr, "rip alloc %zu bytes at %p\n", want, ptr);
+  }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+  }
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(ptr);
+  }
+};
+
+// Selects the handle's device for the duration of one C-ABI call and puts the caller's current device back afterwards
+// (a CameraRig thread, or torch, keeps its own current device across calls into handles that live elsewhere).
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int device) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    HIP_CHECK(hipSetDevice(device));
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// What one frame geometry/encoding turns into
+struct Plan {
+  int src_kind = rip::SRC_BGR, ry = 0, rx = 0;
+  int in_elem_bytes = 1;   // bytes per input sample: 2 for bayer_*16 frames (rip_set_debayer_16bit)
+  int out_elem_bytes = 1;  // bytes per output sample: 2 = the 16-bit extension with the range off (debayer + flip only, bgr16 out)
+  // bayer_*16 frames with a 16-bit range (rip_set_debayer_16bit_range): demosaiced at 16 bits, narrowed to 8 bits with
+  // (black, white) and flipped by one pass of its own (rip_raw16.hip), then the whole chain as for a bgr8 frame
+  bool raw16 = false;
+  int black = 0, white = 0;
+  // packed 10- / 12-bit frames (rip::PackedLayout; 0: none): a raw16 plan whose rows are unpacked by the kernel's tile staging
+  // (rip_packed.hip), with the handle's range or the format's natural one
+  int packed_layout = 0;
+  bool mht = false;       // Bayer input demosaiced by Malvar-He-Cutler (rip_set_debayer_method "mht") instead of bilinear
+  int channels = 3;       // channels after the debayer stage
+  int flip_angle = 0;     // effective
+  int mid_rows = 0, mid_cols = 0;  // post-flip geometry (pointwise chain output)
+  int out_rows = 0, out_cols = 0;
+  bool remap = false;
+  int wb_mode = rip::WB_NONE;
+  int stage_bits = 0;
+  std::string encoding_out;
+  // the output stage (rip_set_output_format; filled in by apply_output_format, everything above describes the pipeline's own image)
+  bool fmt_active = false;        // a format other than "native" is set
+  int out_fmt = rip::OUT_NATIVE;  // the conversion that runs behind the last kernel; OUT_NATIVE: none (mono8 of a one-channel image included)
+  int dl_channels = 3;            // what the frame calls deliver: channels (planes), bytes per element, planar or interleaved
+  int dl_elem_bytes = 1;
+  bool dl_planar = false;
+};
+
+// n frames of rows x cols pixels in device memory: rows `step` bytes apart, frames `frame_stride` bytes apart (both resolved,
+// never 0).  FrameView is written, ConstFrameView is read.
+struct ConstFrameView {
+  const uint8_t* ptr;
+  size_t step, frame_stride;
+  int rows, cols;
+};
+struct FrameView {
+  uint8_t* ptr;
+  size_t step, frame_stride;
+  int rows, cols;
+  operator ConstFrameView() const { return {ptr, step, frame_stride, rows, cols}; }
+};
+// the view from frame f0 on
+template <typename View>
+View frames_from(View v, int f0) {
+  v.ptr += (size_t)f0 * v.frame_stride;
+  return v;
+}
+// the caller's tap buffers (null: not requested): tightly packed mid_rows x mid_cols x channels frames
+struct Taps {
+  uint8_t* debayered;
+  uint8_t* color;
+};
+
+// One frame in flight on the asynchronous host path (rip_submit / rip_collect): its own device input / output / tap
+// buffers, a pinned result buffer, and the three events that chain upload -> kernels -> download.
+struct RingSlot {
+  DevBuf d_in, d_out, d_tap_deb, d_tap_col;
+  void* h_out = nullptr;  // hipHostMalloc
+  size_t h_out_cap = 0;
+  void* h_in = nullptr;   // hipHostMalloc: staging copy of a pageable caller frame (the caller's buffer is free again when rip_submit returns)
+  size_t h_in_cap = 0;
+  void* h_tap[2] = {nullptr, nullptr};  // hipHostMalloc: the debayered / colour taps of the frame, downloaded with the result
+  // where this frame's downloads go: the slot's own pinned buffers above, or the page-locked buffers the caller gave rip_submit_to
+  void* dst_out = nullptr;
+  void* dst_tap[2] = {nullptr, nullptr};
+  int gate_device = -1;  // device whose InflightGate queue holds ev_done (set when the frame is enqueued)
+  size_t h_tap_cap[2] = {0, 0};
+  hipEvent_t ev_up = nullptr, ev_kernels = nullptr, ev_done = nullptr;
+  hipEvent_t ev_start = nullptr, ev_dl_start = nullptr;  // RIP_DEBUG_RING only: before the upload / the download (the other three then carry timestamps too)
+  uint64_t ticket = 0;
+  bool busy = false;  // submitted, not collected yet
+  bool held = false;  // collected: the pinned result and the taps stay put until the next collect (or until a submit needs the slot)
+  Plan pl;
+  bool has_deb = false, has_col = false;  // the taps this frame keeps on the device
+  bool dl_deb = false, dl_col = false;    // ... and downloads into h_tap with the result
+  static void reserve_pinned(void*& ptr, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return;
+    if (ptr) HIP_CHECK(hipHostFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+    HIP_CHECK(hipHostMalloc(&ptr, bytes + bytes / 8, hipHostMallocDefault));
+    cap = bytes + bytes / 8;
+  }
+  void reserve_host(size_t bytes) { reserve_pinned(h_out, h_out_cap, bytes); }
+  void reserve_host_in(size_t bytes) { reserve_pinned(h_in, h_in_cap, bytes); }
+  void release();  // rip_ring.cpp
+};
+
+}  // namespace rip::api
+
+struct rip_pipeline {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  rip::Modules m;
+  // environment overrides, read once when the handle is created (never on a frame path)
+  rip::Tunables tn;
+  bool maps_on_host = false;      // RIP_MAPS_ON_HOST
+  bool plan_on_host = false;      // RIP_PLAN_ON_HOST: compile the remap plan on the host even when the maps are on the device
+  std::string debug_dir = "/tmp"; // RIP_DEBUG_DIR
+  std::string ccc_model_env;      // RIP_CCC_MODEL
+  mutable std::string last_error;
+  int tap_mask = RIP_TAP_DEBAYERED | RIP_TAP_COLOR | RIP_TAP_PROCESSED;
+  int tap_download_mask = 0;  // rip_set_tap_download: which of the kept taps rip_submit also downloads with the result
+  int fp_contract = 0;        // rip_set_fp_contraction / RIP_FP_CONTRACT: contraction model of the float stages (0 none, 1 fused)
+
+  // constants on the device
+  rip::DevTables h_tabs;
+  rip::api::DevBuf d_tabs, d_vig_image;  // d_vig_image: the fused chain's LDS tables as one image (rip::launch_vig_image)
+  bool tabs_dirty = true;
+  // undistortion maps (interleaved float2), built lazily
+  std::vector<float> h_map;
+  rip::api::DevBuf d_map, d_map_ckpt;  // d_map_ckpt: scratch of the map kernels (row accumulators at every 32nd column)
+  bool map_dirty = true, map_uploaded = false;
+  bool h_map_valid = false;  // device-built maps are copied to the host only when something on the host asks for them
+  // vignetting mask plane per geometry (float, rows x cols)
+  std::vector<float> h_vig;
+  rip::api::DevBuf d_vig;
+  int vig_rows = -1, vig_cols = -1;
+  bool vig_dirty = true;
+  // ccc
+  rip::CccModel ccc;
+  rip::api::DevBuf d_filter_fft, d_bias_fft, d_accum, d_ccc_state, d_geom;
+  bool ccc_uploaded = false, ccc_state_init = false, ccc_reset_pending = false, ccc_cfg_dirty = true;
+  double kf_h = 0.0, kf_r = 1.0;
+  int geom_rows = -1, geom_cols = -1;
+  // per-batch scratch
+  rip::api::DevBuf d_stats, d_wb, d_hist, d_work, d_rowbest, d_argmax, d_mid;
+  rip::api::DevBuf d_mht;  // the Malvar-He-Cutler image of a batch when no DEBAYERED tap holds it (run_batch)
+  // output stage (rip_set_output_format): the pipeline's final image of a batch slice in front of the converter (rows padded to
+  // 16 bytes), and the planar formats' 3 x 256 table, rebuilt and uploaded when the format or the normalisation changes
+  rip::api::DevBuf d_fmt, d_out_tab;
+  std::vector<uint8_t> h_out_tab;
+  bool out_tab_dirty = true;
+  // compiled remap plan (tiled LDS gather), rebuilt when the maps or the source geometry change
+  rip::RemapPlan plan;
+  rip::api::DevBuf d_plan_words, d_plan_tiles, d_plan_border, d_plan_counters;
+  bool plan_uploaded = false;
+  bool plan_on_device = false;  // compiled by remap_plan_kernel: plan.words / tiles / border stay empty on the host
+  int plan_n_border = 0;
+  rip::api::DevBuf d_plan_fp;  // the device compiler's footprint (lo, hi per source row pair), read back into plan.fp_lo / fp_hi
+  // the fast chain kernel's items inside the plan's footprint (rip::chain_footprint_items), uploaded once per (plan, flip)
+  rip::api::DevBuf d_chain_items;
+  int chain_items_flip = -1;  // -1: not built for the current plan
+  int chain_items_n = 0;
+  int last_chain_walked = 0;  // items per frame the last chain launch of run_batch walked (rip_debug_chain_footprint)
+  bool use_tiled_remap = true;
+  int last_batch_frames = 0;
+  bool work_enqueued = false;  // some frame call has put work on `stream` (rip_set_stream orders a new stream behind it)
+  // prefix of d_stats known to hold zeroed FrameStats records (the grey-world / pca statistics kernels clean up after themselves)
+  const void* stats_clean_ptr = nullptr;
+  size_t stats_clean_cap = 0, stats_clean_bytes = 0;  // (pointer, capacity) identify the allocation: rip::api::DevBuf only ever grows
+  // the leading bytes of d_hist known to be zero: the ccc estimator's global-atomic histogram (small batches) hands its
+  // counters back zeroed, so a stream of single frames pays for one memset, not one per frame
+  const void* hist_clean_ptr = nullptr;
+  size_t hist_clean_cap = 0, hist_clean_bytes = 0;
+  // cross-kernel overlap inside one batch (run_batch): the remap of frame group g runs on this internal stream while the
+  // statistics and the fused chain of group g + 1 run on the caller's stream
+  hipStream_t aux_stream = nullptr;
+  std::vector<hipEvent_t> ovl_events;
+  hipEvent_t switch_event = nullptr;  // rip_set_stream: orders the new stream behind the work left on the old one
+  // asynchronous host path: frames in flight (rip_submit / rip_collect), upload and download streams
+  std::vector<std::unique_ptr<rip::api::RingSlot>> ring;
+  int ring_depth = 3;
+  uint64_t next_ticket = 1;
+  hipStream_t ul_stream = nullptr, dl_stream = nullptr;
+  // optional per-kernel timing with HIP events on the handle's stream (bench.py roofline leg)
+  bool prof_on = false;
+  std::vector<hipEvent_t> prof_events;  // pairs
+  std::vector<int> prof_ids;
+  size_t prof_used = 0;
+  // rip_debug_launch_log: which kernels the handle's calls launched
+  bool launch_log_on = false;
+  rip::LaunchLog launch_log;
+  // host-apply staging and last-frame taps
+  rip::api::DevBuf d_in, d_out, d_tap_deb, d_tap_col, d_dbg;
+  int last_rows[3] = {0, 0, 0}, last_cols[3] = {0, 0, 0}, last_cn[3] = {0, 0, 0};
+  bool last_valid[3] = {false, false, false};
+  rip::api::DevBuf* last_buf[3] = {nullptr, nullptr, nullptr};
+  const void* last_host[3] = {nullptr, nullptr, nullptr};  // pinned host copy of the image (frames that came through rip_collect), else null
+
+
+  ~rip_pipeline();  // rip_api.cpp
+};
+
+namespace rip::api {
+
+// RAII marker: records an event pair around the launches of one kernel class when profiling is on
+struct ProfScope {
+  rip_pipeline* p;
+  hipStream_t stream;  // the stream the class's kernels are launched on (the handle's, or the internal overlap stream)
+  size_t slot = (size_t)-1;
+  ProfScope(rip_pipeline* pp, int id, hipStream_t s) : p(pp), stream(s) {
+    if (!p->prof_on || p->prof_used + 2 > p->prof_events.size()) return;
+    slot = p->prof_used;
+    p->prof_used += 2;
+    p->prof_ids.push_back(id);
+    (void)hipEventRecord(p->prof_events[slot], stream);
+  }
+  ~ProfScope() {
+    if (slot != (size_t)-1) (void)hipEventRecord(p->prof_events[slot + 1], stream);
+  }
+};
+
+// RAII: points this thread's launch-record sink at the handle's log (when that is on) around the code that launches kernels
+struct LaunchLogScope {
+  rip::LaunchLog* before;
+  explicit LaunchLogScope(rip_pipeline* p) : before(rip::t_launch_log) { rip::t_launch_log = p->launch_log_on ? &p->launch_log : nullptr; }
+  ~LaunchLogScope() { rip::t_launch_log = before; }
+  LaunchLogScope(const LaunchLogScope&) = delete;
+  LaunchLogScope& operator=(const LaunchLogScope&) = delete;
+};
+
+rip_status status_of(const std::exception& e);  // rip_api.cpp: the status an exception of a C-ABI call stands for
+// runs the body of a C-ABI call: an exception becomes the handle's last error and a status
+template <typename F>
+rip_status guarded(const rip_pipeline* p, F&& fn) {
+  try {
+    fn();
+    return RIP_OK;
+  } catch (const std::exception& e) {
+    if (p) p->last_error = e.what();
+    return status_of(e);
+  }
+}
+
+// rip_api.cpp
+void need(const rip_pipeline* p);         // a handle
+void need_device(const rip_pipeline* p);  // ... that has a device
+void copy_string(const std::string& s, char* out, size_t cap);
+
+// rip_plan.cpp: no HIP call
+int parse_packed(const std::string& e, int& ry, int& rx);
+size_t row_bytes(const Plan& pl, int cols, int channels);
+size_t delivered_bytes(const Plan& pl);
+Plan make_plan(const rip::Modules& m, int rows, int cols, int channels, const std::string& encoding);
+void apply_output_format(const rip::Modules& m, Plan& pl);
+FrameView tight_output_view(const Plan& pl, void* d_out);
+FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, size_t out_frame_stride);
+
+// rip_batch.cpp
+void und_init(rip_pipeline* p);
+void ensure_host_maps(rip_pipeline* p);
+void need_host_map(rip_pipeline* p);
+void ensure_maps(rip_pipeline* p);
+void ensure_plan(rip_pipeline* p, int src_rows, int src_cols);
+size_t fmt_pitch(const Plan& pl);
+void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb = false);
+void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n);
+void write_debug_dumps(rip_pipeline* p, const Plan& pl, ConstFrameView src, const uint8_t* final_image);
+
+}  // namespace rip::api

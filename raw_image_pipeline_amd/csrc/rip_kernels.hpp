@@ -1,5 +1,5 @@
 // rip_kernels.hpp -- POD parameter blocks and launch entry points of the gfx950 kernels.
-// Everything here is plain data: the API layer (rip_api.cpp) fills the structs, the launchers
+// Everything here is plain data: the API layer (rip_batch.cpp) fills the structs, the launchers
 // (rip_chain.hip, rip_stats.hip, rip_ccc.hip, rip_remap.hip; shared device code in rip_device.hpp) enqueue on the caller's stream.  No allocation, no synchronisation.
 #pragma once
 
@@ -290,7 +290,7 @@ struct Tunables {
   int chain_footprint = 1;    // RIP_CHAIN_FOOTPRINT=0: the fast chain kernel in front of the remap computes every pixel, not only the ones the remap reads (ChainParams::item_list)
   int chain_nt = -1;          // RIP_CHAIN_NT: non-temporal stores of the fused chain for batches of >= 8 frames; -1 = always (round 5: also when the remap reads the image back), 0 = never, 1 = only when no kernel of the batch reads the image again (rounds 3-4)
   int ccc_lds_hist_min = 12;  // RIP_CCC_LDS_HIST_MIN: smallest batch that takes the LDS histogram (round 4, with 4 workgroups per frame: ms per batch of 8 / 16 / 32 / 47 frames, atomic kernel vs LDS: 0.069 / 0.093 / 0.142 / 0.191 vs 0.077 / 0.081 / 0.093 / 0.108)
-  int overlap_groups = 0;     // RIP_OVERLAP_GROUPS: frame groups a batch is split into on the handle's internal streams (rip_api.cpp run_batch); 0 / 1 = off (the measured optimum)
+  int overlap_groups = 0;     // RIP_OVERLAP_GROUPS: frame groups a batch is split into on the handle's internal streams (rip_batch.cpp run_batch); 0 / 1 = off (the measured optimum)
   int overlap_mode = 1;       // RIP_OVERLAP_MODE: 1 = remap(g) beside stats(g+1) + chain(g+1); 2 = beside stats(g+1) only (the chain waits)
   int debug_occupancy = 0;    // RIP_DEBUG_OCC: print the residency of every chain variant launched (development aid)
 };
@@ -301,7 +301,7 @@ Tunables tunables_from_env();  // rip_api.cpp; called by rip_create
 //   <kernel with its template arguments as the demangler prints them> fc=<0|1> grid=<x>,<y> block=<n> frames=<n>
 // fc: the floating-point model the translation unit was compiled under (the _fc1 twins share a kernel's name).  Off -- the sink
 // is null -- a launch site pays one null test: no formatting, no allocation, no lock.
-struct LaunchLog;                       // rip_api.cpp
+struct LaunchLog;                       // rip_handle.hpp
 extern __thread LaunchLog* t_launch_log;  // null: off
 void launch_log_add(LaunchLog* log, int fc, unsigned grid_x, unsigned grid_y, unsigned block, int frames, const char* fmt, ...)
     __attribute__((format(printf, 7, 8)));

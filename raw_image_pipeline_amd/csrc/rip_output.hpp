@@ -1,6 +1,6 @@
 // rip_output.hpp -- the output stage (rip_set_output_format): one exact per-pixel conversion of the pipeline's final 8-bit BGR
 // image into the format the caller asked for.  The kernels live in a library of their own, librip_out_hip.so (rip_output.hip):
-// this header is its whole interface -- plain data and one launch function, which rip_api.cpp calls.
+// this header is its whole interface -- plain data and one launch function, which rip_batch.cpp calls.
 #pragma once
 
 #include <hip/hip_runtime.h>

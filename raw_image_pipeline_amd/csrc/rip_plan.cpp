@@ -1,0 +1,194 @@
+// rip_plan.cpp -- what one frame geometry / encoding turns into (Plan), the output stage on top of it and the layout of the
+// delivered buffer.  Arithmetic and checks on the handle's parameters only: this unit makes no HIP call.
+#include "rip_handle.hpp"
+#include "rip_unpack.hpp"
+
+namespace rip::api {
+
+int parse_bayer(const std::string& e, int& ry, int& rx) {
+  // position of the R sample in the 2x2 cell for the ROS pattern names (debayer.cpp:48-70)
+  if (e == "bayer_rggb8") { ry = 0; rx = 0; return 1; }
+  if (e == "bayer_grbg8") { ry = 0; rx = 1; return 1; }
+  if (e == "bayer_gbrg8") { ry = 1; rx = 0; return 1; }
+  if (e == "bayer_bggr8") { ry = 1; rx = 1; return 1; }
+  return 0;
+}
+bool is_bayer16(const std::string& e) {
+  return e == "bayer_bggr16" || e == "bayer_gbrg16" || e == "bayer_grbg16" || e == "bayer_rggb16";
+}
+// bayer_<pattern><suffix> of the packed 10- / 12-bit formats (rip.h "Packed Bayer frames"): the R sample's phase and the layout
+// (rip::PackedLayout), or 0
+int parse_packed(const std::string& e, int& ry, int& rx) {
+  static const struct { const char* suffix; int layout; } kSuffixes[] = {
+      {"10p", rip::PACKED_10P}, {"12p", rip::PACKED_12P}, {"10_csi2", rip::PACKED_10_CSI2}, {"12_csi2", rip::PACKED_12_CSI2}};
+  if (e.size() < 13 || e.compare(0, 6, "bayer_") != 0) return 0;
+  const std::string suffix = e.substr(10);
+  for (const auto& k : kSuffixes)
+    if (suffix == k.suffix && parse_bayer(e.substr(0, 10) + "8", ry, rx)) return k.layout;
+  return 0;
+}
+
+// tightly packed bytes of one delivered frame
+size_t delivered_bytes(const Plan& pl) { return (size_t)pl.out_rows * pl.out_cols * pl.dl_channels * (size_t)pl.dl_elem_bytes; }
+
+// payload bytes of one input row: ceil(cols * B / 8) for a packed format, cols * channels samples otherwise
+size_t row_bytes(const Plan& pl, int cols, int channels) {
+  if (pl.packed_layout) return rip::packed_row_bytes(pl.packed_layout, cols);
+  return (size_t)cols * (size_t)channels * (size_t)pl.in_elem_bytes;
+}
+
+// ------------------------------------------------------------------------------------------------
+// planning: raw_image_pipeline.hpp:143-172 stage gating
+// ------------------------------------------------------------------------------------------------
+Plan make_plan(const rip::Modules& m, int rows, int cols, int channels, const std::string& encoding) {
+  Plan pl;
+  if (rows < 1 || cols < 1) throw AssertError("empty image");
+  // the kernels address one frame with 32-bit byte offsets and 24-bit row multiplies
+  if (cols > (1 << 22) || rows > (1 << 22) || (unsigned long long)rows * cols * 3ull >= (1ull << 32))
+    throw InvalidArgument("image too large: a frame must stay below 4 GiB and 4 Mpx per side");
+  pl.encoding_out = encoding;
+  if (parse_bayer(encoding, pl.ry, pl.rx)) {
+    if (channels != 1) throw AssertError("cv::demosaicing: Bayer input must have one channel");
+    if (rows < 3 || cols < 3) throw AssertError("cv::demosaicing: image too small");
+    pl.src_kind = rip::SRC_BAYER;
+    pl.channels = 3;
+    pl.encoding_out = "bgr8";
+  } else if (is_bayer16(encoding)) {
+    // debayer.cpp:76-78 throws for these names; rip_set_debayer_16bit(1) opts into the extension instead
+    if (!m.debayer_16bit) throw InvalidArgument("Encoding [" + encoding + "] is a valid pattern but is not supported!");
+    if (channels != 1) throw AssertError("cv::demosaicing: Bayer input must have one channel");
+    if (rows < 3 || cols < 3) throw AssertError("cv::demosaicing: image too small");
+    std::string e8 = encoding.substr(0, encoding.size() - 2) + "8";
+    parse_bayer(e8, pl.ry, pl.rx);
+    pl.src_kind = rip::SRC_BAYER;
+    pl.in_elem_bytes = 2;
+    pl.channels = 3;
+    if (m.raw16_white > 0) {  // narrowed right after the demosaic: an 8-bit frame from there on
+      pl.raw16 = true;
+      pl.black = m.raw16_black;
+      pl.white = m.raw16_white;
+      pl.encoding_out = "bgr8";
+    } else {
+      pl.out_elem_bytes = 2;
+      pl.encoding_out = "bgr16";
+    }
+  } else if (const int layout = parse_packed(encoding, pl.ry, pl.rx)) {
+    // no reference behaviour to override: accepted whatever rip_set_debayer_16bit says
+    if (channels != 1) throw AssertError("cv::demosaicing: Bayer input must have one channel");
+    if (rows < 3 || cols < 3) throw AssertError("cv::demosaicing: image too small");
+    const int mult = rip::packed_cols_multiple(layout);
+    if (cols % mult != 0)
+      throw InvalidArgument("Encoding [" + encoding + "]: the width must be a multiple of " + std::to_string(mult) + " (whole CSI-2 groups of " +
+                            std::to_string(mult) + " pixels in " + std::to_string(mult * rip::packed_bits(layout) / 8) + " bytes), got " + std::to_string(cols));
+    pl.src_kind = rip::SRC_BAYER;
+    pl.channels = 3;
+    pl.packed_layout = layout;
+    pl.raw16 = true;  // narrowed right after the demosaic, never bgr16
+    if (m.raw16_white > 0) {
+      pl.black = m.raw16_black;
+      pl.white = m.raw16_white;
+    } else {  // the format's natural range
+      pl.black = 0;
+      pl.white = (1 << rip::packed_bits(layout)) - 1;
+    }
+    pl.encoding_out = "bgr8";
+  } else if (encoding == "rgb8") {
+    if (channels != 3) throw AssertError("cvtColor(RGB2BGR): rgb8 input must have three channels");
+    pl.src_kind = rip::SRC_RGB;  // swapped to BGR; the encoding string stays "rgb8" (debayer.cpp:72-73)
+    pl.channels = 3;
+  } else if (channels == 3) {
+    pl.src_kind = rip::SRC_BGR;
+    pl.channels = 3;
+  } else if (channels == 1) {
+    pl.src_kind = rip::SRC_MONO;
+    pl.channels = 1;
+  } else {
+    throw InvalidArgument("images with " + std::to_string(channels) + " channels are not supported");
+  }
+  pl.mht = pl.src_kind == rip::SRC_BAYER && m.debayer_method == "mht";
+  pl.flip_angle = (m.flip_enabled && (m.flip_angle == 90 || m.flip_angle == 180 || m.flip_angle == 270)) ? m.flip_angle : 0;
+  const bool swap = pl.flip_angle == 90 || pl.flip_angle == 270;
+  pl.mid_rows = swap ? cols : rows;
+  pl.mid_cols = swap ? rows : cols;
+  if (m.wb_enabled && pl.channels == 3) {
+    const std::string& w = m.wb_method;
+    if (w == "gray_world" || w == "grey_world")
+      pl.wb_mode = rip::WB_Q8;
+    else if (w == "ccc")
+      pl.wb_mode = rip::WB_FLOAT;
+    else if (w == "pca")
+      pl.wb_mode = rip::WB_PCA;
+    else if (w == "simple")
+      pl.wb_mode = rip::WB_SIMPLE;
+    else if (w == "learned")
+      throw InvalidArgument("White Balance method [learned] (cv::xphoto::LearningBasedWB, a model compiled into opencv_contrib) is not implemented by the MI355X pipeline; use 'simple', 'gray_world', 'ccc' or 'pca'");
+    else
+      throw InvalidArgument("White Balance method [" + w + "] not supported. Supported algorithms: 'simple', 'gray_world', 'learned', 'ccc', 'pca'");
+  }
+  if (m.cc_enabled && pl.channels == 3 && m.cc_available) pl.stage_bits |= rip::ST_CC;
+  if (m.gamma_enabled) pl.stage_bits |= rip::ST_GAMMA;
+  if (m.vig_enabled) {
+    if (pl.channels != 3) throw AssertError("cvtColor(BGR2Lab): vignetting correction needs a 3-channel image");
+    pl.stage_bits |= rip::ST_VIG;
+  }
+  if (m.ce_enabled && pl.channels == 3) pl.stage_bits |= rip::ST_HSV;
+  pl.remap = m.und_enabled && m.und_available && m.dist_model != "none";
+  if (pl.out_elem_bytes == 2 && (pl.wb_mode != rip::WB_NONE || pl.stage_bits != 0 || pl.remap))
+    // every later module of the reference works on 8-bit images (cv::LUT, xphoto white balance, 8-bit Lab / HSV tables)
+    // and would assert on CV_16UC3
+    throw AssertError("16-bit Bayer frames go through debayer and flip only: disable white balance, colour calibration, gamma, "
+                      "vignetting, colour enhancer and undistortion (they are 8-bit stages)");
+  pl.out_rows = pl.remap ? m.dist_h : pl.mid_rows;
+  pl.out_cols = pl.remap ? m.dist_w : pl.mid_cols;
+  return pl;
+}
+
+// The output stage on top of a plan (rip_set_output_format): what the frame calls and rip_query_output deliver.  The taps, the
+// debug dumps and rip_query_taps stay with make_plan's image.  Throws before anything is enqueued where the format does not apply.
+void apply_output_format(const rip::Modules& m, Plan& pl) {
+  pl.dl_channels = pl.channels;
+  pl.dl_elem_bytes = pl.out_elem_bytes;
+  const int fmt = rip::output_format_id(m.out_format);
+  if (fmt == rip::OUT_NATIVE) return;
+  pl.fmt_active = true;
+  if (pl.out_elem_bytes != 1)
+    throw InvalidArgument("output format [" + m.out_format + "] needs an 8-bit pipeline result; this frame gives bgr16 (set a 16-bit range, or the format 'native')");
+  if (pl.channels == 1) {
+    if (fmt != rip::OUT_MONO8)
+      throw InvalidArgument("output format [" + m.out_format + "] needs a three-channel pipeline result; this frame gives one channel ('mono8' and 'native' apply)");
+    pl.encoding_out = "mono8";  // the identity: no kernel
+    return;
+  }
+  pl.out_fmt = fmt;
+  pl.dl_channels = rip::output_format_channels(fmt);
+  pl.dl_elem_bytes = rip::output_format_elem_bytes(fmt);
+  pl.dl_planar = rip::output_format_planar(fmt);
+  pl.encoding_out = m.out_format;
+}
+
+// The tightly packed DELIVERED frames at d_out: what a row pitch and a frame stride of 0 stand for.  Planar formats: `step` is
+// the row pitch inside a plane and a frame is three planes of step * rows.
+FrameView tight_output_view(const Plan& pl, void* d_out) {
+  const size_t step = (size_t)pl.out_cols * (size_t)pl.dl_elem_bytes * (pl.dl_planar ? 1 : (size_t)pl.dl_channels);
+  return {static_cast<uint8_t*>(d_out), step, step * (size_t)pl.out_rows * (pl.dl_planar ? 3 : 1), pl.out_rows, pl.out_cols};
+}
+
+// The delivered frames of rip_apply_device (0 = tight), with the checks rip.h promises.  The kernels address one frame with
+// 32-bit byte offsets and 24-bit row multiplies: pitches they cannot express, and pitches that would make rows or frames
+// overlap, are refused instead of writing somewhere else.
+FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, size_t out_frame_stride) {
+  FrameView v = tight_output_view(pl, d_out);
+  const size_t e = (size_t)pl.dl_elem_bytes, row = v.step;
+  if (out_step) v.step = out_step;
+  if (v.step < row) throw InvalidArgument("output row pitch smaller than a row");
+  const unsigned long long frame = (unsigned long long)v.step * pl.out_rows * (pl.dl_planar ? 3ull : 1ull);
+  v.frame_stride = out_frame_stride ? out_frame_stride : (size_t)frame;
+  if (v.frame_stride < frame) throw InvalidArgument("output frame stride smaller than a frame");
+  if (v.step >= (1u << 24) || frame >= (1ull << 32)) throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
+  // native results are bytes, or bgr16 samples whose alignment has never been asked for
+  if (pl.out_fmt != rip::OUT_NATIVE && (reinterpret_cast<uintptr_t>(d_out) | v.step | v.frame_stride) % e != 0)
+    throw InvalidArgument("output buffer, row pitch and frame stride must be multiples of the element size (" + std::to_string(e) + " bytes)");
+  return v;
+}
+
+}  // namespace rip::api

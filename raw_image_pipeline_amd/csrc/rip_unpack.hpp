@@ -1,5 +1,5 @@
 // rip_unpack.hpp -- packed 10- / 12-bit Bayer rows (rip.h "Packed Bayer frames"): the layouts, their geometry rule and the
-// extract functions, shared by the kernels' byte path (rip_raw16_dev.hpp), the host layer (rip_api.cpp: row bytes, the checks)
+// extract functions, shared by the kernels' byte path (rip_raw16_dev.hpp), the host layer (rip_plan.cpp: row bytes, the checks)
 // and rip_debug_unpack, which pins this arithmetic on the CPU.
 //
 // Sample x of a row of bytes b[0..]:

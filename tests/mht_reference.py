@@ -2,7 +2,7 @@
 expected image of the "mht" debayer method, for any Bayer pattern and 8- or 16-bit samples."""
 import numpy as np
 
-# phase (ry, rx) of the R sample in the 2 x 2 cell (parse_bayer, rip_api.cpp)
+# phase (ry, rx) of the R sample in the 2 x 2 cell (parse_bayer, rip_plan.cpp)
 PHASE = {"rggb": (0, 0), "grbg": (0, 1), "gbrg": (1, 0), "bggr": (1, 1)}
 
 # The published filters, integer weights over 16, as {(dy, dx): weight} around the centre (the table in PARITY.md).

@@ -49,4 +49,4 @@ def test_up_to_date_covers_the_companion(rip_lib):
     assert B.up_to_date() and B.companion_up_to_date()
     for f in B.COMPANION_SOURCES + B.COMPANION_HEADERS:
         assert os.path.exists(os.path.join(B.CSRC, f))
-    assert "rip_output.hpp" in B.HEADERS     # rip_api.cpp includes it: librip_hip.so is rebuilt when the interface changes
+    assert "rip_output.hpp" in B.HEADERS     # rip_handle.hpp includes it: librip_hip.so is rebuilt when the interface changes

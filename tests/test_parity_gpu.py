@@ -458,7 +458,7 @@ def test_batch_with_many_frames_per_workgroup(gpu_pipe, oracle, monkeypatch, wb)
 def test_statistics_records_are_handed_back_clean(gpu_pipe, oracle):
     """The grey-world / pca statistics kernels finish their frames themselves: the workgroup that ends a frame last writes
     its gains and zeroes the frame's record, and the library skips the memset and the finalisation launch for as long as
-    it knows the records are clean (rip_api.cpp run_batch).  One handle, batches of changing length, method, input kind and
+    it knows the records are clean (rip_batch.cpp run_batch).  One handle, batches of changing length, method, input kind and
     geometry back to back (SimpleWB in between keeps its own finalisation kernel, colour input takes another statistics
     kernel, a longer batch re-allocates the records): every frame of every batch must equal the oracle, i.e. no sum of an
     earlier batch may survive and no ticket counter may be left half-way."""
