@@ -234,6 +234,17 @@ class RawImagePipeline {
     check(rip_set_output_normalization(h_, divisor, mean.data(), std_dev.data()));
   }
 
+  // not in the reference: the resize stage (rip.h rip_set_output_size).  The frame calls deliver Mats of height x width --
+  // cv::resize(F, Size(width, height), 0, 0, INTER_LINEAR) of the pipeline's final image F, in front of the output format; (0, 0)
+  // is off.  getOutputCameraInfo: size, K (3 x 3) and P (3 x 4) of the delivered image for an input frame of that geometry.
+  void setOutputSize(int width, int height) { check(rip_set_output_size(h_, width, height)); }
+  void getOutputSize(int& width, int& height) const { check(rip_get_output_size(h_, &width, &height)); }
+  void getOutputCameraInfo(int rows, int cols, int channels, const std::string& encoding, int& height, int& width, Mat& K, Mat& P) const {
+    K = detail::make_f64(3, 3);
+    P = detail::make_f64(3, 4);
+    check(rip_get_output_camera_info(h_, rows, cols, channels, encoding.c_str(), &height, &width, detail::doubles(K), detail::doubles(P)));
+  }
+
   void setFlip(bool enabled) { check(rip_set_flip(h_, enabled)); }
   void setFlipAngle(int angle) { check(rip_set_flip_angle(h_, angle)); }
 

@@ -321,6 +321,39 @@ rip_status rip_get_output_format(const rip_pipeline* p, char* out, size_t capaci
  * RIP_DEVICE_NONE handles. */
 rip_status rip_set_output_normalization(rip_pipeline* p, double divisor, const double mean[3], const double std[3]);
 rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, double mean[3], double std[3]); /* any pointer may be null */
+/* Extension beyond the reference: the resize stage.  A target size (width, height) makes rip_apply / rip_apply_device / rip_submit /
+ * rip_collect deliver the output format applied to F' = resize(F, height rows, width cols) instead of F, the pipeline's final image
+ * (rows x cols after flip / undistortion, 8-bit, 3 channels BGR or 1 channel); under "native" they deliver F' itself.  (0, 0), the
+ * default, is off; otherwise both values are in 1..16384.  Anything else (one of them 0, negative, above 16384):
+ * RIP_ERR_INVALID_ARGUMENT naming the rule, nothing changed.  A target equal to F's size delivers exactly what a handle without a
+ * target delivers: no launch, no extra memory.
+ * resize(F, H, W) is cv::resize(F, Size(W, H), 0, 0, INTER_LINEAR) on 8-bit data as oracle/rip_oracle.c restates it (PARITY.md
+ * "Resize"; all integers behind two small per-axis tables built on the host): with R x C the size of F, the 2 x 2 mean
+ * (a + b + c + d + 2) >> 2 when R == 2 H and C == 2 W, else two taps per axis with 11-bit weights and the source position
+ * (x + 0.5) * C / W - 0.5 of output column x (pixel centres; rows alike), clamped at the edges.
+ * Refused by the frame calls and by rip_query_output / rip_query_output_bytes / rip_get_output_camera_info with
+ * RIP_ERR_INVALID_ARGUMENT, before anything is enqueued (the ccc / Kalman state does not advance): a target on a bgr16 result, and an
+ * F larger than 16384 on a side.  The format rules are unchanged; mono8 on a one-channel result stays the identity, on F'.
+ * Geometry: rip_query_output, rip_query_output_bytes, the frame calls' out_rows / out_cols, their capacity checks, rip_apply_device's
+ * out_step / out_frame_stride rules and limits and the planar formats' plane stride all refer to the delivered height x width.
+ * Unchanged and still on F: rip_query_taps, the DEBAYERED / COLOR taps and their getters, rip_get_white_balance_info,
+ * rip_get_ccc_track, the debug dumps and every camera getter.  RIP_IMAGE_PROCESSED reports an empty image while a resize is active,
+ * as it does under a format.
+ * Cost: one more launch per batch slice in front of the converter, n_frames x rows x cols x channels bytes of device memory (rows
+ * padded to 16 bytes) kept by the handle for F, and as much for F' under a format other than native.
+ * Works on RIP_DEVICE_NONE handles.  Params YAML: `output: size: [width, height]`; rip_load_params re-creates the modules, so an
+ * absent key means off; an invalid value fails with RIP_ERR_INVALID_ARGUMENT and leaves the parameters as they were. */
+rip_status rip_set_output_size(rip_pipeline* p, int width, int height);
+rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height); /* either pointer may be null */
+/* Camera matrix K (3 x 3) and projection matrix P (3 x 4) of the image the frame calls deliver for such an input frame (arguments as
+ * for rip_query_output), with its size in *height / *width.  They start from the rect K / P when that frame would be undistorted,
+ * else from the dist K / P; with a target size and a = width / C, b = height / R in double (R x C: the size of F; every operation
+ * rounded): K[0] *= a, K[1] *= a, K[2] = a * (K[2] + 0.5) - 0.5, K[4] *= b, K[5] = b * (K[5] + 0.5) - 0.5, rows 0 and 1 of P
+ * likewise with P[3] *= a and P[7] *= b -- the inverse of the pixel-centre mapping u = (u' + 0.5) / a - 0.5 the resize uses.  Without
+ * an active resize the matrices come back unchanged with F's size.  Any output pointer may be null.  Fails where rip_query_output
+ * fails.  Works on RIP_DEVICE_NONE handles. */
+rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* height, int* width,
+                                      double K[9], double P[12]);
 rip_status rip_set_flip(rip_pipeline* p, int enabled);                            /* hpp:69 */
 rip_status rip_set_flip_angle(rip_pipeline* p, int angle);                        /* hpp:70 */
 rip_status rip_set_white_balance(rip_pipeline* p, int enabled);                   /* hpp:72 */
@@ -462,6 +495,12 @@ rip_status rip_debug_unpack(const char* encoding, const uint8_t* in, size_t step
  * of the format's element type (float, or the uint16 bit patterns of f16 / bf16), plane-major, written to out.  rgb8, mono8 and
  * native have no table: RIP_ERR_INVALID_ARGUMENT, as for an unknown name or an invalid normalisation.  No device, no handle. */
 rip_status rip_debug_output_table(const char* name, double divisor, const double mean[3], const double std[3], void* out);
+/* Test hook: the tables of the resize stage (rip_set_output_size) from a src_rows x src_cols image to dst_rows x dst_cols, every
+ * side in 1..16384 (RIP_ERR_INVALID_ARGUMENT otherwise, or for a null table): xofs[dst_cols] the first tap's column, alpha[2 *
+ * dst_cols] the two weights of a column, yofs[2 * dst_rows] the two clamped rows, beta[2 * dst_rows] the two weights of a row,
+ * *area2 (optional) = 1 when the 2 x 2 mean replaces them.  No device, no handle. */
+rip_status rip_debug_resize_tables(int src_rows, int src_cols, int dst_rows, int dst_cols, int32_t* xofs, int16_t* alpha, int32_t* yofs,
+                                   int16_t* beta, int* area2);
 /* Test hook for the debug dumps: writes image (rows x cols x channels bytes, channels 1 or 3 = BGR) to path as the PNG
  * writer of rip_set_debug does, after the reference's min-max normalisation when normalize != 0.  No device needed;
  * p may be NULL. */

@@ -1,5 +1,5 @@
-"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion librip_out_hip.so (the kernels of the output
-stage, csrc/rip_output.hip) for gfx950 with hipcc.
+"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companions librip_out_hip.so (the kernels of the output
+stage, csrc/rip_output.hip) and librip_rsz_hip.so (the kernels of the resize stage, csrc/rip_resize.hip) for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", os.path.join("..", "..", "include", "rip.h")]
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion library: the output stage's kernels (rip_set_output_format) and their one launch function (rip_output.hpp).  A
 # library of its own so that librip_hip.so's kernel table stays what tests/variant_cases.py closes over; the companion's table
 # is closed by tests/output_variant_cases.py.  librip_hip.so -- every build of it: the default one, the sanitizer build and the
@@ -19,6 +19,11 @@ HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_
 OUT_COMPANION = os.path.join(HERE, "librip_out_hip.so")
 COMPANION_SOURCES = ["rip_output.hip"]
 COMPANION_HEADERS = ["rip_output.hpp"]
+# The second companion, on the same terms: the resize stage's kernels (rip_set_output_size) behind rip_resize.hpp; its table is
+# closed by tests/resize_variant_cases.py.
+OUT_RSZ = os.path.join(HERE, "librip_rsz_hip.so")
+RSZ_SOURCES = ["rip_resize.hip"]
+RSZ_HEADERS = ["rip_resize.hpp"]
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -37,31 +42,35 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def companion_up_to_date():
-    if not os.path.exists(OUT_COMPANION):
+def _companion_up_to_date(out, sources, headers):
+    if not os.path.exists(out):
         return False
-    t = os.path.getmtime(OUT_COMPANION)
-    deps = [os.path.join(CSRC, s) for s in COMPANION_SOURCES + COMPANION_HEADERS] + [os.path.abspath(__file__)]
+    t = os.path.getmtime(out)
+    deps = [os.path.join(CSRC, s) for s in sources + headers] + [os.path.abspath(__file__)]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
+def companion_up_to_date():
+    return _companion_up_to_date(OUT_COMPANION, COMPANION_SOURCES, COMPANION_HEADERS)
+
+
+def rsz_up_to_date():
+    return _companion_up_to_date(OUT_RSZ, RSZ_SOURCES, RSZ_HEADERS)
+
+
 def up_to_date():
-    if not os.path.exists(OUT) or not companion_up_to_date():
+    if not os.path.exists(OUT) or not companion_up_to_date() or not rsz_up_to_date():
         return False
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def build_companion(force=False, verbose=False):
-    """librip_out_hip.so, next to librip_hip.so.  Its interface is rip_output.hpp alone, so a rebuild of it does not ask for a
-    relink of the libraries that use it."""
-    if not force and companion_up_to_date():
-        return OUT_COMPANION
-    bdir = os.path.join(HERE, "build_out")
+def _build_companion(out, sources, bdir_name, verbose):
+    bdir = os.path.join(HERE, bdir_name)
     os.makedirs(bdir, exist_ok=True)
     objs = []
-    for s in COMPANION_SOURCES:
+    for s in sources:
         obj = os.path.join(bdir, os.path.splitext(s)[0] + ".o")
         cmd = [hipcc()] + FLAGS + os.environ.get("RIP_EXTRA_FLAGS", "").split() + ["-x", "hip", "-c", os.path.join(CSRC, s), "-o", obj]
         if verbose:
@@ -72,11 +81,26 @@ def build_companion(force=False, verbose=False):
         if verbose and r.stdout.strip():
             print(r.stdout)
         objs.append(obj)
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname," + os.path.basename(OUT_COMPANION), "-o", OUT_COMPANION] + objs
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname," + os.path.basename(out), "-o", out] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("link failed:\n" + r.stdout)
-    return OUT_COMPANION
+    return out
+
+
+def build_companion(force=False, verbose=False):
+    """librip_out_hip.so, next to librip_hip.so.  Its interface is rip_output.hpp alone, so a rebuild of it does not ask for a
+    relink of the libraries that use it."""
+    if not force and companion_up_to_date():
+        return OUT_COMPANION
+    return _build_companion(OUT_COMPANION, COMPANION_SOURCES, "build_out", verbose)
+
+
+def build_rsz(force=False, verbose=False):
+    """librip_rsz_hip.so, next to librip_hip.so; its interface is rip_resize.hpp alone."""
+    if not force and rsz_up_to_date():
+        return OUT_RSZ
+    return _build_companion(OUT_RSZ, RSZ_SOURCES, "build_rsz", verbose)
 
 
 # --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under
@@ -106,11 +130,12 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
     out=".../variants/x.so"; the default build takes no extra flags beyond $RIP_EXTRA_FLAGS."""
     if asan:
         out, tag = out or ASAN_OUT, tag or "_asan"
-        if not force and os.path.exists(out) and companion_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
+        if not force and os.path.exists(out) and companion_up_to_date() and rsz_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
             return out
     if out is None and not force and up_to_date():
         return OUT
-    build_companion(verbose=verbose)  # every build of librip_hip.so links against it; `force` is about the library asked for
+    build_companion(verbose=verbose)  # every build of librip_hip.so links against both; `force` is about the library asked for
+    build_rsz(verbose=verbose)
     out = out or OUT
     objs = []
     procs = []
@@ -132,8 +157,8 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
             raise RuntimeError("hipcc failed on %s:\n%s" % (s, log))
         if verbose and log.strip():
             print(log)
-    # the companion is found next to the library ($ORIGIN) or one directory up (variants/*.so)
-    companion = ["-L" + HERE, "-l:" + os.path.basename(OUT_COMPANION), "-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    # the companions are found next to the library ($ORIGIN) or one directory up (variants/*.so)
+    companion = ["-L" + HERE, "-l:" + os.path.basename(OUT_COMPANION), "-l:" + os.path.basename(OUT_RSZ), "-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
     cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -65,7 +65,7 @@ rip_pipeline::~rip_pipeline() {
   if (dl_stream) (void)hipStreamDestroy(dl_stream);
   for (DevBuf* b : {&d_tabs, &d_vig_image, &d_map, &d_map_ckpt, &d_filter_fft, &d_bias_fft, &d_accum, &d_ccc_state, &d_geom, &d_stats, &d_wb,
                     &d_hist, &d_work, &d_rowbest, &d_argmax, &d_mid, &d_in, &d_out, &d_tap_deb, &d_tap_col, &d_vig, &d_plan_words,
-                    &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg, &d_mht, &d_fmt, &d_out_tab})
+                    &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg, &d_mht, &d_fmt, &d_out_tab, &d_rsz, &d_rsz_tab})
     b->release();
 }
 
@@ -220,8 +220,8 @@ rip_status rip_query_output(rip_pipeline* p, int rows, int cols, int channels, c
     if (!encoding) throw InvalidArgument("encoding is null");
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
     apply_output_format(p->m, pl);
-    if (out_rows) *out_rows = pl.out_rows;
-    if (out_cols) *out_cols = pl.out_cols;
+    if (out_rows) *out_rows = pl.dl_rows;
+    if (out_cols) *out_cols = pl.dl_cols;
     if (out_channels) *out_channels = pl.dl_channels;
     if (encoding_out) copy_string(pl.encoding_out, encoding_out, 32);
   });
@@ -382,6 +382,7 @@ RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, cons
            if (!mean || !sd) throw InvalidArgument("null mean or std");
            rip::check_output_normalization(divisor, mean, sd); p->m.out_divisor = divisor;
            for (int i = 0; i < 3; i++) { p->m.out_mean[i] = mean[i]; p->m.out_std[i] = sd[i]; } p->out_tab_dirty = true)
+RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), rip::check_output_size(width, height); p->m.out_w = width; p->m.out_h = height)
 RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
 RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)
 RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v != 0)
@@ -463,6 +464,55 @@ rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, 
       if (mean) mean[i] = p->m.out_mean[i];
       if (sd) sd[i] = p->m.out_std[i];
     }
+  });
+}
+
+rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height) {
+  return guarded(p, [&] {
+    need(p);
+    if (width) *width = p->m.out_w;
+    if (height) *height = p->m.out_h;
+  });
+}
+
+rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* height, int* width, double K[9],
+                                      double P[12]) {
+  return guarded(p, [&] {
+    need(p);
+    if (!encoding) throw InvalidArgument("encoding is null");
+    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
+    apply_output_format(p->m, pl);
+    const rip::Modules& m = p->m;
+    double k[9], pr[12];
+    for (int i = 0; i < 9; i++) k[i] = pl.remap ? m.rect_K[i] : m.dist_K[i];
+    for (int i = 0; i < 12; i++) pr[i] = pl.remap ? m.rect_P[i] : m.dist_P[i];
+    if (pl.rsz_active) {
+      // the inverse of the tables' pixel-centre mapping u = (u' + 0.5) / a - 0.5 (PARITY.md "Resize")
+      const double a = (double)pl.dl_cols / pl.out_cols, b = (double)pl.dl_rows / pl.out_rows;
+      k[0] *= a;
+      k[1] *= a;
+      k[2] = a * (k[2] + 0.5) - 0.5;
+      k[4] *= b;
+      k[5] = b * (k[5] + 0.5) - 0.5;
+      pr[0] *= a;
+      pr[1] *= a;
+      pr[2] = a * (pr[2] + 0.5) - 0.5;
+      pr[3] *= a;
+      pr[5] *= b;
+      pr[6] = b * (pr[6] + 0.5) - 0.5;
+      pr[7] *= b;
+    }
+    if (height) *height = pl.dl_rows;
+    if (width) *width = pl.dl_cols;
+    if (K) std::memcpy(K, k, sizeof(k));
+    if (P) std::memcpy(P, pr, sizeof(pr));
+  });
+}
+
+rip_status rip_debug_resize_tables(int src_rows, int src_cols, int dst_rows, int dst_cols, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta,
+                                   int* area2) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    rip::build_resize_tables(src_rows, src_cols, dst_rows, dst_cols, xofs, alpha, yofs, beta, area2);
   });
 }
 

@@ -829,8 +829,8 @@ void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView ds
   if (enqueue_demosaic_pass(p, pl, src, dst, taps, n, bgr)) run_chain(p, as_bgr8_after_demosaic(pl), bgr, dst, {nullptr, taps.color}, n, reuse_wb);
 }
 
-// pitch of the staging image in front of the converter: every source row starts 16-byte aligned
-size_t fmt_pitch(const Plan& pl) { return ((size_t)pl.out_cols * 3 + 15) & ~(size_t)15; }
+// pitch of the staging image in front of the resize and the converter: every source row starts 16-byte aligned
+size_t fmt_pitch(const Plan& pl) { return ((size_t)pl.out_cols * pl.channels + 15) & ~(size_t)15; }
 
 // The planar formats' table on the device, rebuilt on the host (rip::build_output_table) when the format or the normalisation
 // has changed since the last frame
@@ -845,11 +845,43 @@ static void ensure_output_table(rip_pipeline* p, int fmt) {
   p->out_tab_dirty = false;
 }
 
-// run_batch with the output stage behind it: under a format the chain's last kernel writes the pipeline's image into the
-// handle's staging buffer and one launch of the converter (librip_out_hip.so) writes the caller's buffer; "native" is run_batch.
+// The tables of the resize stage on the device, rebuilt on the host (rip::build_resize_tables) when the sizes they were built for
+// change.  One buffer: xofs, alpha (both padded to whole lanes), yofs, beta -- every part starts 16-byte aligned.
+struct ResizeTables {
+  const int32_t* xofs;
+  const int16_t* alpha;
+  const int32_t* yofs;
+  const int16_t* beta;
+  int area2;
+};
+// The upload goes through the handle's pageable copy and waits for the stream, like the other ensure_* functions: a handle that
+// alternates between targets pays that wait on every change (one table set is kept, not one per target).
+static ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, int W) {
+  const size_t wp = rip::resize_table_cols(W), hp = ((size_t)H + 3) & ~(size_t)3;
+  const size_t o_alpha = wp * 4, o_yofs = o_alpha + wp * 4, o_beta = o_yofs + hp * 8, bytes = o_beta + hp * 4;
+  const int key[4] = {R, C, H, W};
+  if (std::memcmp(key, p->rsz_tab_key, sizeof(key)) != 0 || !p->d_rsz_tab.ptr) {
+    p->h_rsz_tab.assign(bytes, 0);
+    uint8_t* h = p->h_rsz_tab.data();
+    rip::build_resize_tables(R, C, H, W, reinterpret_cast<int32_t*>(h), reinterpret_cast<int16_t*>(h + o_alpha), reinterpret_cast<int32_t*>(h + o_yofs),
+                             reinterpret_cast<int16_t*>(h + o_beta), &p->rsz_tab_area2);
+    p->d_rsz_tab.reserve(bytes);
+    HIP_CHECK(hipMemcpyAsync(p->d_rsz_tab.ptr, h, bytes, hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    std::memcpy(p->rsz_tab_key, key, sizeof(key));
+  }
+  const uint8_t* d = p->d_rsz_tab.as<uint8_t>();
+  return {reinterpret_cast<const int32_t*>(d), reinterpret_cast<const int16_t*>(d + o_alpha), reinterpret_cast<const int32_t*>(d + o_yofs),
+          reinterpret_cast<const int16_t*>(d + o_beta), p->rsz_tab_area2};
+}
+
+// run_batch with the resize and the output stage behind it.  With a target size other than F's, or under a format, the chain's
+// last kernel writes the pipeline's image F into the handle's staging buffer; then one launch of the resize (librip_rsz_hip.so)
+// writes F' -- into the caller's buffer under "native", else into a second staging image -- and one launch of the converter
+// (librip_out_hip.so) writes the caller's buffer from F' (or from F without a target).  Neither: this is run_batch.
 // dst: the DELIVERED frames.
 void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n) {
-  if (pl.out_fmt == rip::OUT_NATIVE) {
+  if (pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active) {
     run_batch(p, pl, src, dst, taps, n);
     return;
   }
@@ -858,16 +890,55 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   p->d_fmt.reserve(staged.frame_stride * (size_t)n);
   staged.ptr = p->d_fmt.as<uint8_t>();
   if (pl.dl_planar) ensure_output_table(p, pl.out_fmt);
+  FrameView converted_from = staged;  // what the converter reads: F, or F' behind a resize
+  ResizeTables rt = {};
+  if (pl.rsz_active) {
+    rt = ensure_resize_tables(p, pl.out_rows, pl.out_cols, pl.dl_rows, pl.dl_cols);
+    if (pl.out_fmt != rip::OUT_NATIVE) {  // the converter's source alignment
+      const size_t pitch = ((size_t)pl.dl_cols * pl.channels + 15) & ~(size_t)15;
+      converted_from = {nullptr, pitch, pitch * (size_t)pl.dl_rows, pl.dl_rows, pl.dl_cols};
+      p->d_rsz.reserve(converted_from.frame_stride * (size_t)n);
+      converted_from.ptr = p->d_rsz.as<uint8_t>();
+    }
+  }
   run_batch(p, pl, src, staged, taps, n);
+  LaunchLogScope log_scope(p);
+  if (pl.rsz_active) {
+    const FrameView to = pl.out_fmt != rip::OUT_NATIVE ? converted_from : dst;
+    rip::ResizeParams r = {};
+    r.src = staged.ptr;
+    r.src_step = staged.step;
+    r.src_frame_stride = staged.frame_stride;
+    r.dst = to.ptr;
+    r.dst_step = to.step;
+    r.dst_frame_stride = to.frame_stride;
+    r.src_rows = pl.out_rows;
+    r.src_cols = pl.out_cols;
+    r.rows = pl.dl_rows;
+    r.cols = pl.dl_cols;
+    r.channels = pl.channels;
+    r.n_frames = n;
+    r.area2 = rt.area2;
+    r.xofs = rt.xofs;
+    r.alpha = rt.alpha;
+    r.yofs = rt.yofs;
+    r.beta = rt.beta;
+    rip::ResizeLaunchInfo info = {};
+    if (!rip::launch_resize(r, p->stream, &info)) throw DeviceError("internal: the resize refused a layout the frame call had accepted");
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+    RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+  }
+  if (pl.out_fmt == rip::OUT_NATIVE) return;
   rip::OutputConvertParams c = {};
-  c.src = staged.ptr;
-  c.src_step = staged.step;
-  c.src_frame_stride = staged.frame_stride;
+  c.src = converted_from.ptr;
+  c.src_step = converted_from.step;
+  c.src_frame_stride = converted_from.frame_stride;
   c.dst = dst.ptr;
   c.dst_step = dst.step;
   c.dst_frame_stride = dst.frame_stride;
-  c.rows = pl.out_rows;
-  c.cols = pl.out_cols;
+  c.rows = pl.dl_rows;
+  c.cols = pl.dl_cols;
   c.n_frames = n;
   c.format = pl.out_fmt;
   c.table = pl.dl_planar ? p->d_out_tab.ptr : nullptr;
@@ -875,7 +946,6 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   if (!rip::launch_output_convert(c, p->stream, &info)) throw DeviceError("internal: the output converter refused a layout the frame call had accepted");
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
-  LaunchLogScope log_scope(p);
   RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
 }
 

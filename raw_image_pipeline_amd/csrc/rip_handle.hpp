@@ -16,6 +16,7 @@
 #include "rip_host.hpp"
 #include "rip_kernels.hpp"
 #include "rip_output.hpp"
+#include "rip_resize.hpp"
 
 namespace rip {
 // Launch record (rip_kernels.hpp): the text of a handle's log, one launch per line
@@ -122,6 +123,10 @@ struct Plan {
   int dl_channels = 3;            // what the frame calls deliver: channels (planes), bytes per element, planar or interleaved
   int dl_elem_bytes = 1;
   bool dl_planar = false;
+  // the resize stage (rip_set_output_size; filled in by apply_output_format too): the delivered rows x cols -- out_rows / out_cols
+  // stay the pipeline's own image F -- and whether a resize kernel runs between F and the converter (a target other than F's size)
+  int dl_rows = 0, dl_cols = 0;
+  bool rsz_active = false;
 };
 
 // n frames of rows x cols pixels in device memory: rows `step` bytes apart, frames `frame_stride` bytes apart (both resolved,
@@ -229,6 +234,12 @@ struct rip_pipeline {
   rip::api::DevBuf d_fmt, d_out_tab;
   std::vector<uint8_t> h_out_tab;
   bool out_tab_dirty = true;
+  // resize stage (rip_set_output_size): the resized image of a batch slice in front of the converter (rows padded to 16 bytes; only
+  // under a format) and the tables of rip::build_resize_tables, rebuilt and uploaded when the (R, C, H, W) they were built for changes
+  rip::api::DevBuf d_rsz, d_rsz_tab;
+  std::vector<uint8_t> h_rsz_tab;
+  int rsz_tab_key[4] = {0, 0, 0, 0};
+  int rsz_tab_area2 = 0;  // build_resize_tables' flag for that key: the 2 x 2 mean replaces the tables
   // compiled remap plan (tiled LDS gather), rebuilt when the maps or the source geometry change
   rip::RemapPlan plan;
   rip::api::DevBuf d_plan_words, d_plan_tiles, d_plan_border, d_plan_counters;

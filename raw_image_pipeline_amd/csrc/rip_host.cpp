@@ -311,6 +311,18 @@ void params_from_node(Modules& m, const YamlNode& node) {
     for (int i = 0; i < 3; i++) (which ? out_std : out_mean)[i] = v[i];
   }
   check_output_normalization(out_divisor, out_mean, out_std);
+  // extension key output: size: [width, height] (rip_set_output_size); absent means off
+  int out_w = 0, out_h = 0;
+  if (o["size"].defined()) {
+    const std::vector<double> v = o.get_vector("size");
+    if (v.size() != 2 || !(v[0] >= 0 && v[0] <= 16384 && v[1] >= 0 && v[1] <= 16384) || v[0] != std::floor(v[0]) || v[1] != std::floor(v[1]))
+      throw std::invalid_argument("output: size: a sequence [width, height] of two integers in 1..16384 (or [0, 0]) is expected");
+    out_w = (int)v[0];
+    out_h = (int)v[1];
+    check_output_size(out_w, out_h);
+  }
+  m.out_w = out_w;
+  m.out_h = out_h;
   m.out_format = out_format;
   m.out_divisor = out_divisor;
   for (int i = 0; i < 3; i++) m.out_mean[i] = out_mean[i], m.out_std[i] = out_std[i];
@@ -471,6 +483,41 @@ void build_output_table(int format, double divisor, const double mean[3], const 
       if (kind == 0) static_cast<float*>(out)[i] = t;
       else static_cast<uint16_t*>(out)[i] = kind == 1 ? f32_to_f16(t) : f32_to_bf16(t);
     }
+}
+
+void check_output_size(int width, int height) {
+  if (width == 0 && height == 0) return;  // off
+  if (width < 1 || height < 1 || width > 16384 || height > 16384)
+    throw std::invalid_argument("output size (" + std::to_string(width) + ", " + std::to_string(height) +
+                                ") not supported: (0, 0) switches it off, otherwise width and height are both in 1..16384");
+}
+
+void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta, int* area2) {
+  for (int side : {R, C, H, W})
+    if (side < 1 || side > 16384) throw std::invalid_argument("resize: every side of the source and of the target must be in 1..16384");
+  if (!xofs || !alpha || !yofs || !beta) throw std::invalid_argument("resize: null table");
+  // imgproc/resize.cpp, the statements of oracle/rip_oracle.c ripo_resize_linear_8u; weights beyond 16 bits cannot occur (f in [0, 1))
+  const double scale_x = (double)C / W, scale_y = (double)R / H;
+  for (int dx = 0; dx < W; dx++) {
+    float fx = (float)((dx + 0.5) * scale_x - 0.5);
+    int sx = (int)std::floor(fx);
+    fx -= sx;
+    if (sx < 0) { fx = 0; sx = 0; }
+    if (sx >= C - 1) { fx = 0; sx = C - 1; }
+    xofs[dx] = sx;
+    alpha[2 * dx] = (int16_t)std::lrintf((1.f - fx) * 2048);
+    alpha[2 * dx + 1] = (int16_t)std::lrintf(fx * 2048);
+  }
+  for (int dy = 0; dy < H; dy++) {
+    float fy = (float)((dy + 0.5) * scale_y - 0.5);
+    const int sy = (int)std::floor(fy);
+    fy -= sy;
+    beta[2 * dy] = (int16_t)std::lrintf((1.f - fy) * 2048);
+    beta[2 * dy + 1] = (int16_t)std::lrintf(fy * 2048);
+    yofs[2 * dy] = std::min(std::max(sy, 0), R - 1);
+    yofs[2 * dy + 1] = std::min(std::max(sy + 1, 0), R - 1);
+  }
+  if (area2) *area2 = (R == 2 * H && C == 2 * W) ? 1 : 0;
 }
 
 void check_debayer_16bit_range(int black, int white) {

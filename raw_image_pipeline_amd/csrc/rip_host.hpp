@@ -62,6 +62,8 @@ struct Modules {
   // the order of the format's planes
   std::string out_format = "native";
   double out_divisor = 255.0, out_mean[3] = {0, 0, 0}, out_std[3] = {1, 1, 1};
+  // extension (rip_set_output_size): the size the delivered frames are resized to, in front of the output format; (0, 0) = off
+  int out_w = 0, out_h = 0;
   // FlipModule (flip.hpp:63-66)
   bool flip_enabled = false;
   int flip_angle = 0;
@@ -113,6 +115,16 @@ void check_output_normalization(double divisor, const double mean[3], const doub
 // y = (v / divisor - mean_c) / std_c in double, every operation rounded, T_c[v] = (float)y; f16 / bf16 entries are that float
 // rounded to nearest even (overflow to +-inf and subnormals as IEEE 754 says).  out: 768 elements of 4 / 2 / 2 bytes.
 void build_output_table(int format, double divisor, const double mean[3], const double sd[3], void* out);
+// the target sizes rip_set_output_size accepts: (0, 0), or both in 1 .. 16384; throws std::invalid_argument naming the rule
+void check_output_size(int width, int height);
+// The tables of the resize stage (rip_resize.hip; cv::resize(8U, INTER_LINEAR), imgproc/resize.cpp, as oracle/rip_oracle.c restates
+// it) from an R x C image to H x W, every side in 1 .. 16384 (std::invalid_argument otherwise).  Per output column x:
+// f = (float)((x + 0.5) * ((double)C / W) - 0.5), sx = floor(f), f -= sx in float; sx < 0: sx = 0, f = 0; sx >= C - 1: sx = C - 1,
+// f = 0; xofs[x] = sx, alpha[2x] = cvRound((1.f - f) * 2048), alpha[2x + 1] = cvRound(f * 2048) (half to even).  Per output row y the
+// same from R / H without the reset of f: beta[2y], beta[2y + 1], and yofs[2y], yofs[2y + 1] = sy, sy + 1 clamped to [0, R - 1].
+// *area2 = 1 when R == 2 H and C == 2 W (OpenCV's switch to the 2 x 2 mean; the tables are filled in all the same).
+// xofs: W, alpha: 2 W, yofs: 2 H, beta: 2 H entries.
+void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta, int* area2);
 bool load_camera_calibration_file(Modules& m, const std::string& path); // undistortion.cpp:157-195
 bool load_color_calibration_file(Modules& m, const std::string& path);  // color_calibration.cpp:52-76
 void apply_example_camera_calibration(Modules& m);  // values of config/alphasense_calib_example.yaml

@@ -29,7 +29,7 @@ int parse_packed(const std::string& e, int& ry, int& rx) {
 }
 
 // tightly packed bytes of one delivered frame
-size_t delivered_bytes(const Plan& pl) { return (size_t)pl.out_rows * pl.out_cols * pl.dl_channels * (size_t)pl.dl_elem_bytes; }
+size_t delivered_bytes(const Plan& pl) { return (size_t)pl.dl_rows * pl.dl_cols * pl.dl_channels * (size_t)pl.dl_elem_bytes; }
 
 // payload bytes of one input row: ceil(cols * B / 8) for a packed format, cols * channels samples otherwise
 size_t row_bytes(const Plan& pl, int cols, int channels) {
@@ -148,6 +148,22 @@ Plan make_plan(const rip::Modules& m, int rows, int cols, int channels, const st
 void apply_output_format(const rip::Modules& m, Plan& pl) {
   pl.dl_channels = pl.channels;
   pl.dl_elem_bytes = pl.out_elem_bytes;
+  // the resize stage (rip_set_output_size) sits between F and the format: the delivered geometry is the target's
+  pl.dl_rows = pl.out_rows;
+  pl.dl_cols = pl.out_cols;
+  if (m.out_w > 0) {
+    if (pl.out_elem_bytes != 1)
+      throw InvalidArgument("output size (" + std::to_string(m.out_w) + ", " + std::to_string(m.out_h) +
+                            ") needs an 8-bit pipeline result; this frame gives bgr16 (set a 16-bit range, or the output size (0, 0))");
+    if (m.out_w != pl.out_cols || m.out_h != pl.out_rows) {
+      if (pl.out_rows > rip::kRszMaxSide || pl.out_cols > rip::kRszMaxSide)
+        throw InvalidArgument("output size: the pipeline's image of " + std::to_string(pl.out_cols) + " x " + std::to_string(pl.out_rows) +
+                              " is larger than the " + std::to_string(rip::kRszMaxSide) + " pixels per side the resize takes");
+      pl.rsz_active = true;
+      pl.dl_rows = m.out_h;
+      pl.dl_cols = m.out_w;
+    }
+  }
   const int fmt = rip::output_format_id(m.out_format);
   if (fmt == rip::OUT_NATIVE) return;
   pl.fmt_active = true;
@@ -169,8 +185,8 @@ void apply_output_format(const rip::Modules& m, Plan& pl) {
 // The tightly packed DELIVERED frames at d_out: what a row pitch and a frame stride of 0 stand for.  Planar formats: `step` is
 // the row pitch inside a plane and a frame is three planes of step * rows.
 FrameView tight_output_view(const Plan& pl, void* d_out) {
-  const size_t step = (size_t)pl.out_cols * (size_t)pl.dl_elem_bytes * (pl.dl_planar ? 1 : (size_t)pl.dl_channels);
-  return {static_cast<uint8_t*>(d_out), step, step * (size_t)pl.out_rows * (pl.dl_planar ? 3 : 1), pl.out_rows, pl.out_cols};
+  const size_t step = (size_t)pl.dl_cols * (size_t)pl.dl_elem_bytes * (pl.dl_planar ? 1 : (size_t)pl.dl_channels);
+  return {static_cast<uint8_t*>(d_out), step, step * (size_t)pl.dl_rows * (pl.dl_planar ? 3 : 1), pl.dl_rows, pl.dl_cols};
 }
 
 // The delivered frames of rip_apply_device (0 = tight), with the checks rip.h promises.  The kernels address one frame with
@@ -181,7 +197,7 @@ FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, si
   const size_t e = (size_t)pl.dl_elem_bytes, row = v.step;
   if (out_step) v.step = out_step;
   if (v.step < row) throw InvalidArgument("output row pitch smaller than a row");
-  const unsigned long long frame = (unsigned long long)v.step * pl.out_rows * (pl.dl_planar ? 3ull : 1ull);
+  const unsigned long long frame = (unsigned long long)v.step * pl.dl_rows * (pl.dl_planar ? 3ull : 1ull);
   v.frame_stride = out_frame_stride ? out_frame_stride : (size_t)frame;
   if (v.frame_stride < frame) throw InvalidArgument("output frame stride smaller than a frame");
   if (v.step >= (1u << 24) || frame >= (1ull << 32)) throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");

@@ -664,6 +664,26 @@ class RawImagePipeline:
         self._call("rip_get_output_normalization", C.byref(d), m, s)
         return d.value, tuple(m), tuple(s)
 
+    def set_output_size(self, width, height):
+        """Extension: resize the delivered frames to ``width`` x ``height`` on the GPU, in front of the output format --
+        cv::resize(F, (width, height), INTER_LINEAR) on the pipeline's final 8-bit image, bit for bit.  (0, 0) (default) is off;
+        a target equal to the image's own size changes nothing.  ``process`` / ``collect`` / ``apply_device`` then return arrays
+        of the delivered height x width; the taps keep the pipeline's geometry.  include/rip.h rip_set_output_size."""
+        self._call("rip_set_output_size", int(width), int(height))
+
+    def get_output_size(self):
+        w, h = C.c_int(), C.c_int()
+        self._call("rip_get_output_size", C.byref(w), C.byref(h))
+        return w.value, h.value
+
+    def get_output_camera_info(self, rows, cols, channels, encoding):
+        """(height, width, K [3, 3], P [3, 4]) of the image the frame calls deliver for such an input frame: the rect (or, without
+        undistortion, dist) matrices scaled to the target size about the pixel centres.  include/rip.h rip_get_output_camera_info."""
+        h, w = C.c_int(), C.c_int()
+        k, pr = (C.c_double * 9)(), (C.c_double * 12)()
+        self._call("rip_get_output_camera_info", int(rows), int(cols), int(channels), encoding.encode(), C.byref(h), C.byref(w), k, pr)
+        return h.value, w.value, np.array(k, dtype=np.float64).reshape(3, 3), np.array(pr, dtype=np.float64).reshape(3, 4)
+
     def set_flip(self, enabled):
         self._call("rip_set_flip", int(bool(enabled)))
 

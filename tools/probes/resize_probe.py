@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Probe: cost of the resize launch (rip_set_output_size, csrc/rip_resize.hip) on the MI355X: 256 resident 2448 x 2048 bgr8 results
+-> 640 x 512, -> 1224 x 1024 (the 2 x 2 mean), -> rgb_chw_f16 at 640 x 512, against what a consumer does today: native delivery +
+torch.nn.functional.interpolate(mode="bilinear") (not bit-identical).  HIP events, warm-up excluded, median / min.
+
+Legs, all in one process on the same seeded frames: the kernel alone (rip::launch_resize of librip_rsz_hip.so called directly on
+host-built tables; one frame of each shape is compared with the oracle first), rip_apply_device with and without a target and a
+format, and the torch expressions.  Every line printed is also written to the output file.
+Usage: resize_probe.py [OUT.txt]   (default profiles/resize_kernel_times.txt)"""
+import ctypes as C
+import os
+import sys
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from raw_image_pipeline_amd import RawImagePipeline, load_library  # noqa: E402
+from raw_image_pipeline_amd import build as B  # noqa: E402
+
+N, R_, C_ = 256, 2048, 2448
+OUT = open(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "resize_kernel_times.txt"), "w")
+
+
+def say(line):
+    print(line, flush=True)
+    OUT.write(line + "\n")
+    OUT.flush()
+
+
+def timed(fn, warm=2, reps=7):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms)), float(np.min(ms))
+
+
+class ResizeParams(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_step", C.c_size_t), ("src_frame_stride", C.c_size_t), ("dst", C.c_void_p), ("dst_step", C.c_size_t),
+                ("dst_frame_stride", C.c_size_t), ("src_rows", C.c_int), ("src_cols", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
+                ("channels", C.c_int), ("n_frames", C.c_int), ("area2", C.c_int), ("xofs", C.c_void_p), ("alpha", C.c_void_p), ("yofs", C.c_void_p),
+                ("beta", C.c_void_p)]
+
+
+def main():
+    lib = load_library()
+    rsz = C.CDLL(B.OUT_RSZ)
+    launch = getattr(rsz, "_ZN3rip13launch_resizeERKNS_12ResizeParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
+    launch.restype = C.c_bool
+    g = torch.Generator(device="cuda").manual_seed(1)
+    frames = torch.randint(0, 256, (N, R_, C_, 3), dtype=torch.uint8, device="cuda", generator=g)
+    say("frames %d x %d x %d x 3 uint8 = %.1f MB; HIP events, median / min of 7 after 2 warm-up runs" % (N, R_, C_, frames.numel() / 1e6))
+
+    # ---- the kernel alone ----
+    for (W, H) in ((640, 512), (1224, 1024)):
+        wp = (W + 3) // 4 * 4
+        xofs, alpha = np.zeros(wp, np.int32), np.zeros((wp, 2), np.int16)
+        yofs, beta = np.zeros((H, 2), np.int32), np.zeros((H, 2), np.int16)
+        area = C.c_int(0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        assert lib.rip_debug_resize_tables(R_, C_, H, W, ptr(xofs), ptr(alpha), ptr(yofs), ptr(beta), C.byref(area)) == 0
+        dev = [torch.from_numpy(a).cuda() for a in (xofs, alpha, yofs, beta)]
+        dst = torch.empty((N, H, W, 3), dtype=torch.uint8, device="cuda")
+        p = ResizeParams(frames.data_ptr(), C_ * 3, R_ * C_ * 3, dst.data_ptr(), W * 3, H * W * 3, R_, C_, H, W, 3, N, area.value,
+                         dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def run():
+            assert launch(C.byref(p), stream, None)
+        med, best = timed(run)
+        read_min = N * H * W * 3 * 4 if not area.value else N * R_ * C_ * 3
+        written = N * H * W * 3
+        say("resize_kernel<3, %s> %dx%d -> %dx%d, %d frames: median %.3f ms, min %.3f ms; written %.1f MB, taps read %.1f MB, source image %.1f MB; "
+            "(taps + written) / min = %.0f GB/s" % ("true" if area.value else "false", C_, R_, W, H, N, med, best, written / 1e6, read_min / 1e6,
+                                                     N * R_ * C_ * 3 / 1e6, (read_min + written) / best / 1e6))
+        # one frame against the CPU definition, so that the timed kernel is the right one
+        import oracle as O
+        O.build()
+        ref = O.resize_linear(frames[3].cpu().numpy(), H, W)
+        assert np.array_equal(dst[3].cpu().numpy(), ref), "timed kernel differs from the oracle"
+
+    # ---- through the library: apply_device on resident bgr8 frames with every stage off ----
+    pipe = RawImagePipeline(False, "", "", "", device=0)
+    for s in ("set_white_balance", "set_undistortion", "set_vignetting_correction", "set_color_calibration", "set_gamma_correction", "set_color_enhancer",
+              "set_flip"):
+        getattr(pipe, s)(False)
+    results = {}
+    for name, fmt, target in (("native, no target", "native", (0, 0)), ("native -> 640x512", "native", (640, 512)), ("native -> 1224x1024", "native", (1224, 1024)),
+                              ("rgb_chw_f16, no target", "rgb_chw_f16", (0, 0)), ("rgb_chw_f16 -> 640x512", "rgb_chw_f16", (640, 512))):
+        pipe.set_output_format(fmt)
+        pipe.set_output_size(*target)
+        out = pipe.apply_device(frames, "bgr8")
+        med, best = timed(lambda: pipe.apply_device(frames, "bgr8", out=out))
+        results[name] = (med, best)
+        say("apply_device %-26s median %.3f ms, min %.3f ms (%s %s)" % (name + ":", med, best, tuple(out.shape), out.dtype))
+        del out
+    pipe.set_output_size(0, 0)
+    pipe.set_output_format("native")
+    native = pipe.apply_device(frames, "bgr8")
+    torch.cuda.synchronize()
+
+    # ---- what a consumer does today: native delivery, then torch's bilinear interpolation (not bit-identical) ----
+    def torch_resize(size, half):
+        x = native.permute(0, 3, 1, 2).float()
+        y = F.interpolate(x, size=size, mode="bilinear", align_corners=False)
+        if half:
+            y = (y.flip(1) / 255.0).half()
+        return y
+    for name, size, half in (("uint8 NHWC -> float NCHW -> bilinear 640x512", (512, 640), False), ("... -> bilinear 1224x1024", (1024, 1224), False),
+                             ("... -> bilinear 640x512 -> rgb / 255 -> f16", (512, 640), True)):
+        med, best = timed(lambda: torch_resize(size, half), warm=2, reps=5)
+        say("torch %-50s median %.3f ms, min %.3f ms" % (name + ":", med, best))
+    x = native.permute(0, 3, 1, 2).float()
+    med, best = timed(lambda: F.interpolate(x, size=(512, 640), mode="bilinear", align_corners=False), warm=2, reps=5)
+    say("torch %-50s median %.3f ms, min %.3f ms" % ("interpolate alone on a float NCHW tensor, 640x512:", med, best))
+    med, best = timed(lambda: F.interpolate(x, size=(1024, 1224), mode="bilinear", align_corners=False), warm=2, reps=5)
+    say("torch %-50s median %.3f ms, min %.3f ms" % ("interpolate alone on a float NCHW tensor, 1224x1024:", med, best))
+    say("done")
+
+
+if __name__ == "__main__":
+    main()
