@@ -70,6 +70,9 @@ def main():
     assert np.array_equal(out, img2) and np.array_equal(img, out) and not np.array_equal(before, img)
     proc.set_output_size(w // 2, h // 2)  # the GPU resizes what it delivers (cv::resize, INTER_LINEAR); here the 2 x 2 mean
     print("half size:", proc.process(before, "bgr8").shape, "camera matrix:", proc.get_output_camera_info(h, w, 3, "bgr8")[2].round(3).tolist())
+    proc.set_output_interpolation("area")  # cv::resize's INTER_AREA: every source pixel under an output pixel counts (downscales only)
+    proc.set_output_size(w // 4, h // 3)
+    print("area,", proc.get_output_interpolation() + ":", proc.process(before, "bgr8").shape)
     try:
         from PIL import Image
         Image.fromarray(img[..., ::-1]).save(os.path.join(args.out_dir, "output_apply.png"))

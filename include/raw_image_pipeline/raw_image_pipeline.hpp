@@ -239,6 +239,9 @@ class RawImagePipeline {
   // is off.  getOutputCameraInfo: size, K (3 x 3) and P (3 x 4) of the delivered image for an input frame of that geometry.
   void setOutputSize(int width, int height) { check(rip_set_output_size(h_, width, height)); }
   void getOutputSize(int& width, int& height) const { check(rip_get_output_size(h_, &width, &height)); }
+  // the filter of that resize (rip.h rip_set_output_interpolation): "linear" (default) or "area", cv::resize's INTER_AREA for downscales
+  void setOutputInterpolation(const std::string& name) { check(rip_set_output_interpolation(h_, name.c_str())); }
+  std::string getOutputInterpolation() const { return str(&rip_get_output_interpolation); }
   void getOutputCameraInfo(int rows, int cols, int channels, const std::string& encoding, int& height, int& width, Mat& K, Mat& P) const {
     K = detail::make_f64(3, 3);
     P = detail::make_f64(3, 4);

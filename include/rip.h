@@ -345,6 +345,25 @@ rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, 
  * absent key means off; an invalid value fails with RIP_ERR_INVALID_ARGUMENT and leaves the parameters as they were. */
 rip_status rip_set_output_size(rip_pipeline* p, int width, int height);
 rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height); /* either pointer may be null */
+/* Extension beyond the reference: the filter of the resize stage, "linear" (the default; the text above) or "area".  Any other name,
+ * or a null one: RIP_ERR_INVALID_ARGUMENT, nothing changed.  Without effect until a target size is active; it never touches the ccc
+ * estimator's own resize, which stays linear.
+ * Under "area" resize(F, H, W) is cv::resize(F, Size(W, H), 0, 0, INTER_AREA) for downscales (PARITY.md "Resize: area
+ * interpolation"), per channel, with R x C the size of F: a target equal to F's size launches nothing; R == 2 H and C == 2 W is the
+ * same 2 x 2 mean (a + b + c + d + 2) >> 2 as under "linear"; R % H == 0 and C % W == 0 otherwise: the integer sum of every
+ * (R / H) x (C / W) block times the float 1.f / ((R / H) * (C / W)), rounded half to even; any other pair of sizes: per-axis lists of
+ * consecutive taps with float weights built on the host in double, summed in float32 in tap order with every product and every sum
+ * rounded (columns first, then rows), rounded half to even and clamped to 0..255.  The result does not depend on
+ * rip_set_fp_contraction.
+ * Refused under "area" with an active target, by the frame calls and by rip_query_output / rip_query_output_bytes /
+ * rip_get_output_camera_info with RIP_ERR_INVALID_ARGUMENT before anything is enqueued (the ccc / Kalman state does not advance), on
+ * top of the refusals above: a target wider or higher than F (area is a downscale filter), and an F more than 256 times the target
+ * on an axis.  Geometry, pitches, taps, white-balance info, the ccc track, the dumps and rip_get_output_camera_info are what they are
+ * under "linear": output pixel u' averages the source interval whose centre is (u' + 0.5) * C / W - 0.5.
+ * Works on RIP_DEVICE_NONE handles.  Params YAML: `output: interpolation: linear | area`; an absent key means linear; an invalid
+ * value fails with RIP_ERR_INVALID_ARGUMENT and leaves the parameters as they were. */
+rip_status rip_set_output_interpolation(rip_pipeline* p, const char* name);
+rip_status rip_get_output_interpolation(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
 /* Camera matrix K (3 x 3) and projection matrix P (3 x 4) of the image the frame calls deliver for such an input frame (arguments as
  * for rip_query_output), with its size in *height / *width.  They start from the rect K / P when that frame would be undistorted,
  * else from the dist K / P; with a target size and a = width / C, b = height / R in double (R x C: the size of F; every operation
@@ -501,6 +520,15 @@ rip_status rip_debug_output_table(const char* name, double divisor, const double
  * *area2 (optional) = 1 when the 2 x 2 mean replaces them.  No device, no handle. */
 rip_status rip_debug_resize_tables(int src_rows, int src_cols, int dst_rows, int dst_cols, int32_t* xofs, int16_t* alpha, int32_t* yofs,
                                    int16_t* beta, int* area2);
+/* Test hook: the tables of the resize stage under the "area" interpolation (rip_set_output_interpolation) from a src_rows x src_cols
+ * image to dst_rows x dst_cols: every side in 1..16384, no axis enlarged, no factor above 256 (RIP_ERR_INVALID_ARGUMENT otherwise, or
+ * for a null table).  Output column x reads the xcount[x] >= 1 consecutive source columns from xfirst[x] on; their float weights
+ * follow each other in xweight in output order (those of column x start at the sum of xcount[0 .. x)); xfirst / xcount: dst_cols
+ * entries, xweight: room for src_cols + 2 * dst_cols.  Rows alike in yfirst / ycount / yweight.  *whole (optional) = 1 when both
+ * factors are whole numbers other than the identity and 2 x 2 -- the kernel then sums blocks and multiplies by *scale (optional) =
+ * 1.f / (ky * kx) -- else 0 and *scale = 0.  No device, no handle. */
+rip_status rip_debug_resize_area_tables(int src_rows, int src_cols, int dst_rows, int dst_cols, int32_t* xfirst, int32_t* xcount, float* xweight,
+                                        int32_t* yfirst, int32_t* ycount, float* yweight, int* whole, float* scale);
 /* Test hook for the debug dumps: writes image (rows x cols x channels bytes, channels 1 or 3 = BGR) to path as the PNG
  * writer of rip_set_debug does, after the reference's min-max normalisation when normalize != 0.  No device needed;
  * p may be NULL. */

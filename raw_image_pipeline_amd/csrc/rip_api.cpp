@@ -383,6 +383,8 @@ RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, cons
            rip::check_output_normalization(divisor, mean, sd); p->m.out_divisor = divisor;
            for (int i = 0; i < 3; i++) { p->m.out_mean[i] = mean[i]; p->m.out_std[i] = sd[i]; } p->out_tab_dirty = true)
 RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), rip::check_output_size(width, height); p->m.out_w = width; p->m.out_h = height)
+RIP_SETTER(rip_set_output_interpolation, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+           (void)rip::output_interpolation_id(s); p->m.out_interp = s)
 RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
 RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)
 RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v != 0)
@@ -455,6 +457,7 @@ int rip_get_rect_image_width(const rip_pipeline* p) { return p ? p->m.rect_w : 0
   }
 RIP_GET_STRING(rip_get_debayer_method, p->m.debayer_method)
 RIP_GET_STRING(rip_get_output_format, p->m.out_format)
+RIP_GET_STRING(rip_get_output_interpolation, p->m.out_interp)
 
 rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, double* mean, double* sd) {
   return guarded(p, [&] {
@@ -513,6 +516,13 @@ rip_status rip_debug_resize_tables(int src_rows, int src_cols, int dst_rows, int
                                    int* area2) {
   return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
     rip::build_resize_tables(src_rows, src_cols, dst_rows, dst_cols, xofs, alpha, yofs, beta, area2);
+  });
+}
+
+rip_status rip_debug_resize_area_tables(int src_rows, int src_cols, int dst_rows, int dst_cols, int32_t* xfirst, int32_t* xcount, float* xweight,
+                                        int32_t* yfirst, int32_t* ycount, float* yweight, int* whole, float* scale) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    rip::build_resize_area_tables(src_rows, src_cols, dst_rows, dst_cols, xfirst, xcount, xweight, yfirst, ycount, yweight, whole, scale);
   });
 }
 

@@ -859,7 +859,7 @@ struct ResizeTables {
 static ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, int W) {
   const size_t wp = rip::resize_table_cols(W), hp = ((size_t)H + 3) & ~(size_t)3;
   const size_t o_alpha = wp * 4, o_yofs = o_alpha + wp * 4, o_beta = o_yofs + hp * 8, bytes = o_beta + hp * 4;
-  const int key[4] = {R, C, H, W};
+  const int key[5] = {R, C, H, W, 0};  // 0: the linear tables (the area interpolation's share the buffer)
   if (std::memcmp(key, p->rsz_tab_key, sizeof(key)) != 0 || !p->d_rsz_tab.ptr) {
     p->h_rsz_tab.assign(bytes, 0);
     uint8_t* h = p->h_rsz_tab.data();
@@ -875,10 +875,47 @@ static ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, i
           reinterpret_cast<const int16_t*>(d + o_beta), p->rsz_tab_area2};
 }
 
+// The tables of the area interpolation (rip::build_resize_area_tables) in the same buffer and under the same key, told apart by the
+// key's last entry: one table set is kept per handle, whichever filter built it.  Parts, all of 4-byte entries: xfirst, xcount, xwofs
+// [W], yfirst, ycount, ywofs [H], xweight [C + 2 W], yweight [R + 2 H]; wofs is the running sum of count.
+struct AreaTables {
+  const int32_t *xfirst, *xcount, *xwofs, *yfirst, *ycount, *ywofs;
+  const float *xweight, *yweight;
+  int whole;
+  float scale;
+};
+static AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W) {
+  const size_t o_y = (size_t)W * 3, o_xw = o_y + (size_t)H * 3, o_yw = o_xw + (size_t)C + 2 * (size_t)W, words = o_yw + (size_t)R + 2 * (size_t)H;
+  const int key[5] = {R, C, H, W, 1};
+  if (std::memcmp(key, p->rsz_tab_key, sizeof(key)) != 0 || !p->d_rsz_tab.ptr) {
+    p->h_rsz_tab.assign(words * 4, 0);
+    int32_t* h = reinterpret_cast<int32_t*>(p->h_rsz_tab.data());
+    rip::build_resize_area_tables(R, C, H, W, h, h + W, reinterpret_cast<float*>(h + o_xw), h + o_y, h + o_y + H, reinterpret_cast<float*>(h + o_yw),
+                                  &p->rsz_tab_whole, &p->rsz_tab_scale);
+    for (int axis = 0; axis < 2; axis++) {
+      const int d = axis ? H : W;
+      const int32_t* count = h + (axis ? o_y : 0) + d;
+      int32_t* wofs = h + (axis ? o_y : 0) + 2 * (size_t)d;
+      int32_t run = 0;
+      for (int i = 0; i < d; i++) {
+        wofs[i] = run;
+        run += count[i];
+      }
+    }
+    p->d_rsz_tab.reserve(words * 4);
+    HIP_CHECK(hipMemcpyAsync(p->d_rsz_tab.ptr, h, words * 4, hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    std::memcpy(p->rsz_tab_key, key, sizeof(key));
+  }
+  const int32_t* d = p->d_rsz_tab.as<int32_t>();
+  return {d, d + W, d + 2 * (size_t)W, d + o_y, d + o_y + H, d + o_y + 2 * (size_t)H, reinterpret_cast<const float*>(d + o_xw),
+          reinterpret_cast<const float*>(d + o_yw), p->rsz_tab_whole, p->rsz_tab_scale};
+}
+
 // run_batch with the resize and the output stage behind it.  With a target size other than F's, or under a format, the chain's
-// last kernel writes the pipeline's image F into the handle's staging buffer; then one launch of the resize (librip_rsz_hip.so)
-// writes F' -- into the caller's buffer under "native", else into a second staging image -- and one launch of the converter
-// (librip_out_hip.so) writes the caller's buffer from F' (or from F without a target).  Neither: this is run_batch.
+// last kernel writes the pipeline's image F into the handle's staging buffer; then one launch of the resize (librip_rsz_hip.so, or
+// librip_area_hip.so under the area interpolation) writes F' -- into the caller's buffer under "native", else into a second
+// staging image -- and one launch of the converter (librip_out_hip.so) writes the caller's buffer from F' (or from F without a target).  Neither: this is run_batch.
 // dst: the DELIVERED frames.
 void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n) {
   if (pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active) {
@@ -892,8 +929,10 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   if (pl.dl_planar) ensure_output_table(p, pl.out_fmt);
   FrameView converted_from = staged;  // what the converter reads: F, or F' behind a resize
   ResizeTables rt = {};
+  AreaTables at = {};
   if (pl.rsz_active) {
-    rt = ensure_resize_tables(p, pl.out_rows, pl.out_cols, pl.dl_rows, pl.dl_cols);
+    if (pl.rsz_area) at = ensure_area_tables(p, pl.out_rows, pl.out_cols, pl.dl_rows, pl.dl_cols);
+    else rt = ensure_resize_tables(p, pl.out_rows, pl.out_cols, pl.dl_rows, pl.dl_cols);
     if (pl.out_fmt != rip::OUT_NATIVE) {  // the converter's source alignment
       const size_t pitch = ((size_t)pl.dl_cols * pl.channels + 15) & ~(size_t)15;
       converted_from = {nullptr, pitch, pitch * (size_t)pl.dl_rows, pl.dl_rows, pl.dl_cols};
@@ -903,7 +942,37 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   }
   run_batch(p, pl, src, staged, taps, n);
   LaunchLogScope log_scope(p);
-  if (pl.rsz_active) {
+  if (pl.rsz_active && pl.rsz_area) {
+    const FrameView to = pl.out_fmt != rip::OUT_NATIVE ? converted_from : dst;
+    rip::AreaParams r = {};
+    r.src = staged.ptr;
+    r.src_step = staged.step;
+    r.src_frame_stride = staged.frame_stride;
+    r.dst = to.ptr;
+    r.dst_step = to.step;
+    r.dst_frame_stride = to.frame_stride;
+    r.src_rows = pl.out_rows;
+    r.src_cols = pl.out_cols;
+    r.rows = pl.dl_rows;
+    r.cols = pl.dl_cols;
+    r.channels = pl.channels;
+    r.n_frames = n;
+    r.whole = at.whole;
+    r.scale = at.scale;
+    r.xfirst = at.xfirst;
+    r.xcount = at.xcount;
+    r.xwofs = at.xwofs;
+    r.xweight = at.xweight;
+    r.yfirst = at.yfirst;
+    r.ycount = at.ycount;
+    r.ywofs = at.ywofs;
+    r.yweight = at.yweight;
+    rip::AreaLaunchInfo info = {};
+    if (!rip::launch_area_reduce(r, p->stream, &info)) throw DeviceError("internal: the area resize refused a layout the frame call had accepted");
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+    RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+  } else if (pl.rsz_active) {
     const FrameView to = pl.out_fmt != rip::OUT_NATIVE ? converted_from : dst;
     rip::ResizeParams r = {};
     r.src = staged.ptr;

@@ -16,6 +16,7 @@
 #include "rip_host.hpp"
 #include "rip_kernels.hpp"
 #include "rip_output.hpp"
+#include "rip_area.hpp"
 #include "rip_resize.hpp"
 
 namespace rip {
@@ -127,6 +128,9 @@ struct Plan {
   // stay the pipeline's own image F -- and whether a resize kernel runs between F and the converter (a target other than F's size)
   int dl_rows = 0, dl_cols = 0;
   bool rsz_active = false;
+  // that kernel is the area interpolation's (rip_set_output_interpolation "area"; rip_area.hpp): false for the exact 2 x 2 case,
+  // which is the mean kernel of the linear path under either name
+  bool rsz_area = false;
 };
 
 // n frames of rows x cols pixels in device memory: rows `step` bytes apart, frames `frame_stride` bytes apart (both resolved,
@@ -235,11 +239,14 @@ struct rip_pipeline {
   std::vector<uint8_t> h_out_tab;
   bool out_tab_dirty = true;
   // resize stage (rip_set_output_size): the resized image of a batch slice in front of the converter (rows padded to 16 bytes; only
-  // under a format) and the tables of rip::build_resize_tables, rebuilt and uploaded when the (R, C, H, W) they were built for changes
+  // under a format) and the tables of rip::build_resize_tables or, under the area interpolation, rip::build_resize_area_tables,
+  // rebuilt and uploaded when the (R, C, H, W, kind of table) they were built for changes
   rip::api::DevBuf d_rsz, d_rsz_tab;
   std::vector<uint8_t> h_rsz_tab;
-  int rsz_tab_key[4] = {0, 0, 0, 0};
+  int rsz_tab_key[5] = {0, 0, 0, 0, 0};
   int rsz_tab_area2 = 0;  // build_resize_tables' flag for that key: the 2 x 2 mean replaces the tables
+  int rsz_tab_whole = 0;  // build_resize_area_tables' flag and scale for that key: whole factors, no table is read
+  float rsz_tab_scale = 0.f;
   // compiled remap plan (tiled LDS gather), rebuilt when the maps or the source geometry change
   rip::RemapPlan plan;
   rip::api::DevBuf d_plan_words, d_plan_tiles, d_plan_border, d_plan_counters;

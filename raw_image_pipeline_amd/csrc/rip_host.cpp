@@ -321,8 +321,14 @@ void params_from_node(Modules& m, const YamlNode& node) {
     out_h = (int)v[1];
     check_output_size(out_w, out_h);
   }
+  // extension key output: interpolation: linear | area (rip_set_output_interpolation); absent means linear
+  const std::string out_interp = o.get("interpolation", std::string("linear"));
+  (void)output_interpolation_id(out_interp);
+  if (o["interpolation"].defined() && o["interpolation"].kind != YamlNode::Scalar)
+    throw std::invalid_argument("output: interpolation: one word is expected, \"linear\" or \"area\"");
   m.out_w = out_w;
   m.out_h = out_h;
+  m.out_interp = out_interp;
   m.out_format = out_format;
   m.out_divisor = out_divisor;
   for (int i = 0; i < 3; i++) m.out_mean[i] = out_mean[i], m.out_std[i] = out_std[i];
@@ -518,6 +524,56 @@ void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alp
     yofs[2 * dy + 1] = std::min(std::max(sy + 1, 0), R - 1);
   }
   if (area2) *area2 = (R == 2 * H && C == 2 * W) ? 1 : 0;
+}
+
+int output_interpolation_id(const std::string& name) {
+  if (name == "linear") return 0;
+  if (name == "area") return 1;
+  throw std::invalid_argument("output interpolation \"" + name + "\" not supported: \"linear\" or \"area\"");
+}
+
+void check_resize_area_sizes(int R, int C, int H, int W) {
+  for (int side : {R, C, H, W})
+    if (side < 1 || side > 16384) throw std::invalid_argument("resize: every side of the source and of the target must be in 1..16384");
+  const std::string sizes = "from " + std::to_string(C) + " x " + std::to_string(R) + " to " + std::to_string(W) + " x " + std::to_string(H);
+  if (W > C || H > R) throw std::invalid_argument("output interpolation \"area\" is a downscale filter: " + sizes + " enlarges an axis (use \"linear\")");
+  if (C > 256 * W || R > 256 * H) throw std::invalid_argument("output interpolation \"area\" takes factors up to 256 per axis: " + sizes + " is beyond that");
+}
+
+size_t build_area_axis(int s, int d, int32_t* first, int32_t* count, float* weights) {
+  const double scale = (double)s / d;
+  size_t n = 0;
+  for (int i = 0; i < d; i++) {
+    const double f1 = i * scale, f2 = f1 + scale, cell = std::min(scale, s - f1);
+    int s1 = (int)std::ceil(f1);
+    const int s2 = std::min((int)std::floor(f2), s - 1);
+    s1 = std::min(s1, s2);
+    const size_t n0 = n;
+    int lead = s1;  // the first source sample of this output
+    if (s1 - f1 > 1e-3) {
+      lead = s1 - 1;
+      weights[n++] = (float)((s1 - f1) / cell);
+    }
+    for (int k = s1; k < s2; k++) weights[n++] = (float)(1.0 / cell);
+    if (f2 - s2 > 1e-3) {
+      if (n == n0) lead = s2;
+      weights[n++] = (float)(std::min(std::min(f2 - s2, 1.0), cell) / cell);
+    }
+    first[i] = lead;
+    count[i] = (int32_t)(n - n0);
+  }
+  return n;
+}
+
+void build_resize_area_tables(int R, int C, int H, int W, int32_t* xfirst, int32_t* xcount, float* xweight, int32_t* yfirst, int32_t* ycount,
+                              float* yweight, int* whole, float* scale) {
+  check_resize_area_sizes(R, C, H, W);
+  if (!xfirst || !xcount || !xweight || !yfirst || !ycount || !yweight) throw std::invalid_argument("resize: null table");
+  build_area_axis(C, W, xfirst, xcount, xweight);
+  build_area_axis(R, H, yfirst, ycount, yweight);
+  const bool is_whole = R % H == 0 && C % W == 0 && !(R == H && C == W) && !(R == 2 * H && C == 2 * W);
+  if (whole) *whole = is_whole ? 1 : 0;
+  if (scale) *scale = is_whole ? 1.f / (float)((R / H) * (C / W)) : 0.f;
 }
 
 void check_debayer_16bit_range(int black, int white) {

@@ -64,6 +64,8 @@ struct Modules {
   double out_divisor = 255.0, out_mean[3] = {0, 0, 0}, out_std[3] = {1, 1, 1};
   // extension (rip_set_output_size): the size the delivered frames are resized to, in front of the output format; (0, 0) = off
   int out_w = 0, out_h = 0;
+  // extension (rip_set_output_interpolation): the filter of that resize, "linear" or "area"; without effect while no target is active
+  std::string out_interp = "linear";
   // FlipModule (flip.hpp:63-66)
   bool flip_enabled = false;
   int flip_angle = 0;
@@ -125,6 +127,22 @@ void check_output_size(int width, int height);
 // *area2 = 1 when R == 2 H and C == 2 W (OpenCV's switch to the 2 x 2 mean; the tables are filled in all the same).
 // xofs: W, alpha: 2 W, yofs: 2 H, beta: 2 H entries.
 void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta, int* area2);
+// the names rip_set_output_interpolation accepts: 0 for "linear", 1 for "area"; throws std::invalid_argument naming both otherwise
+int output_interpolation_id(const std::string& name);
+// The sizes the area interpolation takes, from R x C to H x W: every side in 1 .. 16384, no upscale (H <= R, W <= C) and a factor of at
+// most 256 per axis (R <= 256 H, C <= 256 W: a block sum stays below 2^24).  Throws std::invalid_argument naming the rule.
+void check_resize_area_sizes(int R, int C, int H, int W);
+// The tap list of one axis of the area interpolation (cv::resize(8U, INTER_AREA), imgproc/resize.cpp computeResizeAreaTab, in double;
+// PARITY.md "Resize: area interpolation") from s source to d target samples, d <= s: output i reads the count[i] >= 1 consecutive
+// source samples from first[i] on, all inside [0, s), with the float weights that follow each other in `weights` in output order
+// (those of output i start at the sum of count[0 .. i)).  Returns the number of weights, at most s + 2 d.
+size_t build_area_axis(int s, int d, int32_t* first, int32_t* count, float* weights);
+// Both axes of the area interpolation from R x C to H x W (check_resize_area_sizes; std::invalid_argument for a null table):
+// xfirst / xcount [W] and xweight [up to C + 2 W], yfirst / ycount [H] and yweight [up to R + 2 H].  *whole = 1 when R % H == 0 and
+// C % W == 0 other than the identity and the 2 x 2 mean: the kernel then sums ky x kx blocks and multiplies by *scale =
+// 1.f / (float)(ky * kx); else *scale = 0.  The tables are filled in all the same.  whole and scale may be null.
+void build_resize_area_tables(int R, int C, int H, int W, int32_t* xfirst, int32_t* xcount, float* xweight, int32_t* yfirst, int32_t* ycount,
+                              float* yweight, int* whole, float* scale);
 bool load_camera_calibration_file(Modules& m, const std::string& path); // undistortion.cpp:157-195
 bool load_color_calibration_file(Modules& m, const std::string& path);  // color_calibration.cpp:52-76
 void apply_example_camera_calibration(Modules& m);  // values of config/alphasense_calib_example.yaml

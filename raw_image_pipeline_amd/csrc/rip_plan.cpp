@@ -159,6 +159,11 @@ void apply_output_format(const rip::Modules& m, Plan& pl) {
       if (pl.out_rows > rip::kRszMaxSide || pl.out_cols > rip::kRszMaxSide)
         throw InvalidArgument("output size: the pipeline's image of " + std::to_string(pl.out_cols) + " x " + std::to_string(pl.out_rows) +
                               " is larger than the " + std::to_string(rip::kRszMaxSide) + " pixels per side the resize takes");
+      if (rip::output_interpolation_id(m.out_interp) == 1) {
+        // the area interpolation's own refusals (an upscale, a factor beyond 256); the exact 2 x 2 case is the linear path's mean
+        rip::check_resize_area_sizes(pl.out_rows, pl.out_cols, m.out_h, m.out_w);
+        pl.rsz_area = !(pl.out_rows == 2 * m.out_h && pl.out_cols == 2 * m.out_w);
+      }
       pl.rsz_active = true;
       pl.dl_rows = m.out_h;
       pl.dl_cols = m.out_w;

@@ -676,6 +676,16 @@ class RawImagePipeline:
         self._call("rip_get_output_size", C.byref(w), C.byref(h))
         return w.value, h.value
 
+    def set_output_interpolation(self, name):
+        """Extension: the filter of the resize stage, ``"linear"`` (default) or ``"area"`` -- cv::resize's INTER_AREA for
+        downscales, which averages every source pixel an output pixel covers.  Without effect until ``set_output_size`` has set a
+        target; under ``"area"`` a target larger than the image, or more than 256 times smaller, on an axis is refused by the
+        frame calls (ValueError).  include/rip.h rip_set_output_interpolation."""
+        self._call("rip_set_output_interpolation", name.encode())
+
+    def get_output_interpolation(self):
+        return self._string("rip_get_output_interpolation")
+
     def get_output_camera_info(self, rows, cols, channels, encoding):
         """(height, width, K [3, 3], P [3, 4]) of the image the frame calls deliver for such an input frame: the rect (or, without
         undistortion, dist) matrices scaled to the target size about the pixel centres.  include/rip.h rip_get_output_camera_info."""

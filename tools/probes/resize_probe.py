@@ -6,7 +6,13 @@ torch.nn.functional.interpolate(mode="bilinear") (not bit-identical).  HIP event
 Legs, all in one process on the same seeded frames: the kernel alone (rip::launch_resize of librip_rsz_hip.so called directly on
 host-built tables; one frame of each shape is compared with the oracle first), rip_apply_device with and without a target and a
 format, and the torch expressions.  Every line printed is also written to the output file.
-Usage: resize_probe.py [OUT.txt]   (default profiles/resize_kernel_times.txt)"""
+Usage: resize_probe.py [OUT.txt]   (default profiles/resize_kernel_times.txt)
+
+resize_probe.py --interpolation [OUT.txt] (default profiles/resize_area_kernel_times.txt) is another run: the launches alone of the
+area interpolation (rip::launch_area_reduce of librip_area_hip.so; at exactly half size the 2 x 2 mean kernel of librip_rsz_hip.so)
+and of the linear kernel at the same three targets -- 612 x 512 (whole 4 x 4), 640 x 480 (tap lists), 1224 x 1024 (2 x 2) -- on the
+same resident batch, alternating the two filters; each time with its spread and the fraction of 8 TB/s it stands for on
+3 R C + 3 H W bytes per frame.  One frame of every area launch is compared with tests/area_reference.py first."""
 import ctypes as C
 import os
 import sys
@@ -20,7 +26,9 @@ from raw_image_pipeline_amd import RawImagePipeline, load_library  # noqa: E402
 from raw_image_pipeline_amd import build as B  # noqa: E402
 
 N, R_, C_ = 256, 2048, 2448
-OUT = open(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "resize_kernel_times.txt"), "w")
+INTERPOLATION = "--interpolation" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--interpolation"]
+OUT = open(ARGS[0] if ARGS else os.path.join(ROOT, "profiles", "resize_area_kernel_times.txt" if INTERPOLATION else "resize_kernel_times.txt"), "w")
 
 
 def say(line):
@@ -51,7 +59,100 @@ class ResizeParams(C.Structure):
                 ("beta", C.c_void_p)]
 
 
+class AreaParams(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_step", C.c_size_t), ("src_frame_stride", C.c_size_t), ("dst", C.c_void_p), ("dst_step", C.c_size_t),
+                ("dst_frame_stride", C.c_size_t), ("src_rows", C.c_int), ("src_cols", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
+                ("channels", C.c_int), ("n_frames", C.c_int), ("whole", C.c_int), ("scale", C.c_float), ("xfirst", C.c_void_p), ("xcount", C.c_void_p),
+                ("xwofs", C.c_void_p), ("xweight", C.c_void_p), ("yfirst", C.c_void_p), ("ycount", C.c_void_p), ("ywofs", C.c_void_p), ("yweight", C.c_void_p)]
+
+
+def linear_launch(lib, rsz, frames, dst, H, W):
+    """(callable that enqueues resize_kernel on the current stream, kernel name, objects to keep alive)"""
+    launch = getattr(rsz, "_ZN3rip13launch_resizeERKNS_12ResizeParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
+    launch.restype = C.c_bool
+    wp = (W + 3) // 4 * 4
+    xofs, alpha = np.zeros(wp, np.int32), np.zeros((wp, 2), np.int16)
+    yofs, beta = np.zeros((H, 2), np.int32), np.zeros((H, 2), np.int16)
+    area = C.c_int(0)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert lib.rip_debug_resize_tables(R_, C_, H, W, ptr(xofs), ptr(alpha), ptr(yofs), ptr(beta), C.byref(area)) == 0
+    dev = [torch.from_numpy(a).cuda() for a in (xofs, alpha, yofs, beta)]
+    p = ResizeParams(frames.data_ptr(), C_ * 3, R_ * C_ * 3, dst.data_ptr(), W * 3, H * W * 3, R_, C_, H, W, 3, N, area.value,
+                     dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run():
+        assert launch(C.byref(p), stream, None)
+    return run, "resize_kernel<3, %s>" % ("true" if area.value else "false"), (dev, p)
+
+
+def area_launch(lib, frames, dst, H, W):
+    launch = getattr(C.CDLL(B.OUT_AREA), "_ZN3rip18launch_area_reduceERKNS_10AreaParamsEP12ihipStream_tPNS_14AreaLaunchInfoE")
+    launch.restype = C.c_bool
+    xf, xc, xw = np.zeros(W, np.int32), np.zeros(W, np.int32), np.zeros(C_ + 2 * W, np.float32)
+    yf, yc, yw = np.zeros(H, np.int32), np.zeros(H, np.int32), np.zeros(R_ + 2 * H, np.float32)
+    whole, scale = C.c_int(0), C.c_float(0)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert lib.rip_debug_resize_area_tables(R_, C_, H, W, ptr(xf), ptr(xc), ptr(xw), ptr(yf), ptr(yc), ptr(yw), C.byref(whole), C.byref(scale)) == 0
+    wofs = lambda c: (np.cumsum(c) - c).astype(np.int32)
+    dev = [torch.from_numpy(a).cuda() for a in (xf, xc, wofs(xc), xw, yf, yc, wofs(yc), yw)]
+    p = AreaParams(frames.data_ptr(), C_ * 3, R_ * C_ * 3, dst.data_ptr(), W * 3, H * W * 3, R_, C_, H, W, 3, N, whole.value, scale.value,
+                   *[d.data_ptr() for d in dev])
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run():
+        assert launch(C.byref(p), stream, None)
+    return run, "area_reduce_kernel<3, %s>" % ("true" if whole.value else "false"), (dev, p)
+
+
+def interpolation_main():
+    """The three-target table, area against linear: launches alone, the two filters alternating, 5 rounds of 4 launches each after a
+    warm-up of 2 launches per kernel."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import area_reference as A
+    lib = load_library()
+    rsz = C.CDLL(B.OUT_RSZ)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    frames = torch.randint(0, 256, (N, R_, C_, 3), dtype=torch.uint8, device="cuda", generator=g)
+    say("frames %d x %d x %d x 3 uint8 = %.1f MB resident; HIP events around 4 launches, 5 rounds per kernel alternating area / linear, after 2 "
+        "warm-up launches each; ms per launch of %d frames" % (N, R_, C_, frames.numel() / 1e6, N))
+    say("%-12s %-8s %-30s %9s %9s %9s  %s" % ("target", "filter", "kernel", "median", "min", "max", "share of 8 TB/s on 3RC + 3HW bytes per frame (median)"))
+    for (W, H, path) in ((612, 512, "whole 4 x 4"), (640, 480, "tap lists"), (1224, 1024, "2 x 2 mean")):
+        dsts = [torch.empty((N, H, W, 3), dtype=torch.uint8, device="cuda") for _ in range(2)]
+        legs = []
+        if (R_, C_) == (2 * H, 2 * W):
+            legs.append(("area",) + linear_launch(lib, rsz, frames, dsts[0], H, W))      # the area setting routes this size to the mean kernel
+        else:
+            legs.append(("area",) + area_launch(lib, frames, dsts[0], H, W))
+        legs.append(("linear",) + linear_launch(lib, rsz, frames, dsts[1], H, W))
+        for _, run, _, _ in legs:
+            run()
+            run()
+        torch.cuda.synchronize()
+        assert np.array_equal(dsts[0][3].cpu().numpy(), A.resize(frames[3].cpu().numpy(), H, W)), "timed area kernel differs from the reference"
+        times = {name: [] for name, _, _, _ in legs}
+        for _ in range(5):
+            for name, run, _, _ in legs:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(4):
+                    run()
+                b.record()
+                b.synchronize()
+                times[name].append(a.elapsed_time(b) / 4)
+        nbytes = N * 3 * (R_ * C_ + H * W)
+        for name, _, kernel, _ in legs:
+            t = times[name]
+            med = float(np.median(t))
+            say("%-12s %-8s %-30s %9.3f %9.3f %9.3f  %.3f (%s; %.0f GB/s)" % ("%dx%d" % (W, H), name, kernel, med, min(t), max(t),
+                                                                              nbytes / (med * 1e-3) / 8e12, path, nbytes / med / 1e6))
+        del dsts, legs
+    say("done")
+
+
 def main():
+    if INTERPOLATION:
+        return interpolation_main()
     lib = load_library()
     rsz = C.CDLL(B.OUT_RSZ)
     launch = getattr(rsz, "_ZN3rip13launch_resizeERKNS_12ResizeParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
