@@ -1062,6 +1062,15 @@ __device__ __forceinline__ uint32_t gains_q8_swar(uint32_t v, unsigned q) {
 }
 
 // item index -> (row pair, 4-px group) without an integer division per item
+//
+// Domain.  The estimate fl(fl(item) * fl(1 / g)) carries three float32 roundings, so it lies within (item / g) * 3.0000004 * 2^-24
+// of the true quotient; truncated it is at most one off, which the single correction step repairs, while that error stays below 1:
+// for every quotient -- row or row pair -- below 2^24 / 3 = 5 592 405, whatever groups_per_row is.  make_plan (rip_plan.cpp) accepts
+// at most 2^22 rows, an error of at most 0.75, and fewer than 2^32 / 12 items per frame, so item, q * groups_per_row and the corrected
+// values fit an int.  The chain and statistics kernels split (rows or rows / 2) x (cols / 4) of an accepted frame; the vec4 remap
+// splits drows x (dcols / 4) of the calibration's size, which rip_apply_device's 4 GiB limit on the delivered frame bounds -- at 4
+// columns a calibration higher than 5 592 405 rows would leave the domain (its maps alone would hold 180 MB; nothing refuses it).
+// tests/test_item_split.py restates split() in numpy float32 and checks it against integer division over the accepted frames.
 struct ItemMap {
   int groups_per_row;
   float inv_groups;

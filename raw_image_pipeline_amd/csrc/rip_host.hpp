@@ -248,7 +248,9 @@ void compile_remap_footprint(const float* map_xy, int drows, int dcols, int src_
 // The items of the fused Bayer chain kernel (pair << 16 | grp: the 4 x 2 pixels at source rows 2 pair, 2 pair + 1 and columns
 // 4 grp .. 4 grp + 3 of its input, row-major) whose output lies in the footprint, for a chain of rows x cols pixels that
 // writes the remap's source image flipped by flip_angle (0 or 180): item (pair, grp) writes row pair rows / 2 - 1 - pair and
-// group cols / 4 - 1 - grp under the 180-degree flip.  rows even, cols a multiple of 4, both below 2^17.
+// group cols / 4 - 1 - grp under the 180-degree flip.  rows even, cols a multiple of 4, rows / 2 <= 65535 and cols / 4 <= 65535
+// (each index fills 16 bits: up to 131070 rows and 262140 columns; the callers -- rip_batch.cpp plan_route,
+// rip_debug_chain_footprint -- walk densely or refuse past that).
 void chain_footprint_items(const std::vector<int>& lo, const std::vector<int>& hi, int rows, int cols, int flip_angle,
                            std::vector<uint32_t>& items);
 
