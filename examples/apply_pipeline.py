@@ -73,6 +73,12 @@ def main():
     proc.set_output_interpolation("area")  # cv::resize's INTER_AREA: every source pixel under an output pixel counts (downscales only)
     proc.set_output_size(w // 4, h // 3)
     print("area,", proc.get_output_interpolation() + ":", proc.process(before, "bgr8").shape)
+    proc.set_output_size(w // 4, w // 4)  # a square network input: keep the aspect and pad ("letterbox"), or cut the centre ("crop")
+    for fit in ("letterbox", "crop"):
+        proc.set_output_fit(fit)
+        read, picture = proc.get_output_window(h, w, 3, "bgr8")
+        print("%s: reads %s of the image, picture at %s of %s" % (fit, read, picture, proc.process(before, "bgr8").shape))
+    proc.set_output_fit("stretch")
     try:
         from PIL import Image
         Image.fromarray(img[..., ::-1]).save(os.path.join(args.out_dir, "output_apply.png"))

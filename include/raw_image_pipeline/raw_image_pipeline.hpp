@@ -242,6 +242,19 @@ class RawImagePipeline {
   // the filter of that resize (rip.h rip_set_output_interpolation): "linear" (default) or "area", cv::resize's INTER_AREA for downscales
   void setOutputInterpolation(const std::string& name) { check(rip_set_output_interpolation(h_, name.c_str())); }
   std::string getOutputInterpolation() const { return str(&rip_get_output_interpolation); }
+  // the window of the final image that stage reads, how it is placed in the target -- "stretch" (default), "letterbox" or "crop" --
+  // and the B, G, R colour a letterbox pads with (rip.h rip_set_output_roi, rip_set_output_fit, rip_set_output_pad).
+  // getOutputWindow: the rectangle (x, y, width, height) of the final image that is read and the rectangle of the delivered
+  // image that holds picture, for an input frame of that geometry.
+  void setOutputRoi(int x, int y, int width, int height) { check(rip_set_output_roi(h_, x, y, width, height)); }
+  void getOutputRoi(int& x, int& y, int& width, int& height) const { check(rip_get_output_roi(h_, &x, &y, &width, &height)); }
+  void setOutputFit(const std::string& name) { check(rip_set_output_fit(h_, name.c_str())); }
+  std::string getOutputFit() const { return str(&rip_get_output_fit); }
+  void setOutputPad(int b, int g, int r) { check(rip_set_output_pad(h_, b, g, r)); }
+  void getOutputPad(int& b, int& g, int& r) const { check(rip_get_output_pad(h_, &b, &g, &r)); }
+  void getOutputWindow(int rows, int cols, int channels, const std::string& encoding, int src_xywh[4], int dst_xywh[4]) const {
+    check(rip_get_output_window(h_, rows, cols, channels, encoding.c_str(), src_xywh, dst_xywh));
+  }
   void getOutputCameraInfo(int rows, int cols, int channels, const std::string& encoding, int& height, int& width, Mat& K, Mat& P) const {
     K = detail::make_f64(3, 3);
     P = detail::make_f64(3, 4);

@@ -364,11 +364,53 @@ rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height); 
  * value fails with RIP_ERR_INVALID_ARGUMENT and leaves the parameters as they were. */
 rip_status rip_set_output_interpolation(rip_pipeline* p, const char* name);
 rip_status rip_get_output_interpolation(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
+/* Extension beyond the reference: the window and the fit mode of the resize stage (PARITY.md "Resize: window and fit").  All three
+ * settings are off by default, and with the defaults every call behaves bit for bit as without them.
+ * rip_set_output_roi: the rectangle (x, y, width, height) of F, the pipeline's final image, that the stage reads in place of all of F.
+ * (0, 0, 0, 0) is off; otherwise x, y >= 0 and width, height in 1..16384.  Without a target size the frame calls deliver the window
+ * itself, height x width; a window equal to all of F launches nothing.
+ * rip_set_output_fit: how the window is placed in the target size, without effect while none is set.  "stretch" (default):
+ * resize(window, H, W), each axis with its own ratio.  "crop": the window is first shrunk to the centred sub-window that has the
+ * target's aspect, then stretched.  "letterbox": the whole window is resized to the largest Wi x Hi picture with the window's aspect
+ * that fits the target (rounded to nearest, at least 1), centred at (left, top) = ((W - Wi) / 2, (H - Hi) / 2); every other pixel
+ * of the H x W image gets the pad colour.  With equal aspects letterbox is stretch and nothing is padded.
+ * rip_set_output_pad: that colour as B, G, R of F', each in 0..255, default (114, 114, 114).  It is applied before the output
+ * format, so padded pixels show what the format makes of those bytes; a one-channel result is padded with the grey value
+ * (3735 b + 19235 g + 9798 r + 16384) >> 15.
+ * The bytes of the picture are those the stage delivers for a frame that holds only the window, under the handle's interpolation,
+ * with the rule (copy, 2 x 2 mean, whole factors, tap lists, linear tables) decided on window size -> picture size; pixels of F
+ * outside the window never influence them.  The window is read where F lies: there is no copy of it.
+ * Invalid values (a negative origin, a side of 0 or above 16384, an unknown or null name, a component outside 0..255):
+ * RIP_ERR_INVALID_ARGUMENT naming the rule, nothing changed.  A window that does not lie inside F (x + width > C or y + height > R)
+ * can only be told when a frame's geometry is known: the frame calls, rip_query_output, rip_query_output_bytes,
+ * rip_get_output_camera_info and rip_get_output_window refuse it with RIP_ERR_INVALID_ARGUMENT before anything is enqueued (the
+ * ccc / Kalman state does not advance).  The refusals of rip_set_output_size and rip_set_output_interpolation apply as before, in
+ * this order: a bgr16 result (also for a window without a target), the window outside F, an F above 16384 on a side, and under
+ * "area" the upscale and factor-256 rules on window size -> picture size.
+ * Everything rip_set_output_size lists as staying on F stays on F; RIP_IMAGE_PROCESSED is empty with a window and no target too.
+ * Work on RIP_DEVICE_NONE handles.  Params YAML: `output: roi: [x, y, w, h]`, `output: fit: stretch | letterbox | crop`,
+ * `output: pad: [b, g, r]`; absent keys mean the defaults; an invalid value fails with RIP_ERR_INVALID_ARGUMENT and leaves the
+ * parameters as they were. */
+rip_status rip_set_output_roi(rip_pipeline* p, int x, int y, int width, int height);
+rip_status rip_get_output_roi(const rip_pipeline* p, int* x, int* y, int* width, int* height); /* any pointer may be null */
+rip_status rip_set_output_fit(rip_pipeline* p, const char* name);
+rip_status rip_get_output_fit(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
+rip_status rip_set_output_pad(rip_pipeline* p, int b, int g, int r);
+rip_status rip_get_output_pad(const rip_pipeline* p, int* b, int* g, int* r); /* any pointer may be null */
+/* For an input frame of that geometry (arguments as for rip_query_output): src_xywh, the rectangle (x, y, width, height) of F that is
+ * read -- the window, after "crop" -- and dst_xywh, the rectangle of the delivered image that holds picture; everything outside it
+ * is pad.  Maps detections back to the source: u = (u' - dst x + 0.5) * src width / dst width - 0.5 + src x, rows alike.  Without
+ * a window, a fit mode or a target both are (0, 0, C, R).  Either pointer may be null.  Fails where rip_query_output fails.  Works
+ * on RIP_DEVICE_NONE handles. */
+rip_status rip_get_output_window(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int src_xywh[4], int dst_xywh[4]);
 /* Camera matrix K (3 x 3) and projection matrix P (3 x 4) of the image the frame calls deliver for such an input frame (arguments as
  * for rip_query_output), with its size in *height / *width.  They start from the rect K / P when that frame would be undistorted,
  * else from the dist K / P; with a target size and a = width / C, b = height / R in double (R x C: the size of F; every operation
  * rounded): K[0] *= a, K[1] *= a, K[2] = a * (K[2] + 0.5) - 0.5, K[4] *= b, K[5] = b * (K[5] + 0.5) - 0.5, rows 0 and 1 of P
- * likewise with P[3] *= a and P[7] *= b -- the inverse of the pixel-centre mapping u = (u' + 0.5) / a - 0.5 the resize uses.  Without
+ * likewise with P[3] *= a and P[7] *= b -- the inverse of the pixel-centre mapping u = (u' + 0.5) / a - 0.5 the resize uses.  With a window
+ * or a fit mode (rip_set_output_roi, rip_set_output_fit), (xs, ys, ws, hs) and (left, top, Wi, Hi) the two rectangles of
+ * rip_get_output_window, a = Wi / ws and b = Hi / hs: K[0] *= a, K[1] *= a, K[2] = (a * ((K[2] - xs) + 0.5) - 0.5) + left, K[4] *= b,
+ * K[5] = (b * ((K[5] - ys) + 0.5) - 0.5) + top, P likewise; the size is the target's, or the window's without a target.  Without
  * an active resize the matrices come back unchanged with F's size.  Any output pointer may be null.  Fails where rip_query_output
  * fails.  Works on RIP_DEVICE_NONE handles. */
 rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* height, int* width,
@@ -529,6 +571,12 @@ rip_status rip_debug_resize_tables(int src_rows, int src_cols, int dst_rows, int
  * 1.f / (ky * kx) -- else 0 and *scale = 0.  No device, no handle. */
 rip_status rip_debug_resize_area_tables(int src_rows, int src_cols, int dst_rows, int dst_cols, int32_t* xfirst, int32_t* xcount, float* xweight,
                                         int32_t* yfirst, int32_t* ycount, float* yweight, int* whole, float* scale);
+/* Test hook: the geometry of the resize stage with a window and a fit mode (PARITY.md "Resize: window and fit") for a final image
+ * of cols x rows: roi_xywh as for rip_set_output_roi, (width, height) as for rip_set_output_size, fit as for rip_set_output_fit;
+ * src_xywh / dst_xywh as rip_get_output_window gives them.  RIP_ERR_INVALID_ARGUMENT for what those setters refuse, a window outside
+ * the image or a null pointer.  No device, no handle. */
+rip_status rip_debug_output_window(int cols, int rows, const int roi_xywh[4], int width, int height, const char* fit, int src_xywh[4],
+                                   int dst_xywh[4]);
 /* Test hook for the debug dumps: writes image (rows x cols x channels bytes, channels 1 or 3 = BGR) to path as the PNG
  * writer of rip_set_debug does, after the reference's min-max normalisation when normalize != 0.  No device needed;
  * p may be NULL. */

@@ -1,6 +1,7 @@
 """Builds librip_hip.so (the C-ABI library, include/rip.h) and its companions librip_out_hip.so (the kernels of the output
 stage, csrc/rip_output.hip), librip_rsz_hip.so (the kernels of the resize stage, csrc/rip_resize.hip) and librip_area_hip.so (the
-resize stage's area interpolation, csrc/rip_area.hip) for gfx950 with hipcc.
+resize stage's area interpolation, csrc/rip_area.hip) and librip_fit_hip.so (the resize stage on a window of the image and the
+letterbox bands, csrc/rip_fit.hip) for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
@@ -12,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", os.path.join("..", "..", "include", "rip.h")]
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion library: the output stage's kernels (rip_set_output_format) and their one launch function (rip_output.hpp).  A
 # library of its own so that librip_hip.so's kernel table stays what tests/variant_cases.py closes over; the companion's table
 # is closed by tests/output_variant_cases.py.  librip_hip.so -- every build of it: the default one, the sanitizer build and the
@@ -30,6 +31,12 @@ RSZ_HEADERS = ["rip_resize.hpp"]
 OUT_AREA = os.path.join(HERE, "librip_area_hip.so")
 AREA_SOURCES = ["rip_area.hip"]
 AREA_HEADERS = ["rip_area.hpp"]
+# The fourth companion, on the same terms: the resize stage's kernels that read a window of the image, and the pad kernel of the
+# letterbox (rip_set_output_roi, rip_set_output_fit) behind rip_fit.hpp, which takes its parameter structs from the two headers
+# above; its table is closed by tests/fit_variant_cases.py.
+OUT_FIT = os.path.join(HERE, "librip_fit_hip.so")
+FIT_SOURCES = ["rip_fit.hip"]
+FIT_HEADERS = ["rip_fit.hpp", "rip_resize.hpp", "rip_area.hpp"]
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -68,8 +75,12 @@ def area_up_to_date():
     return _companion_up_to_date(OUT_AREA, AREA_SOURCES, AREA_HEADERS)
 
 
+def fit_up_to_date():
+    return _companion_up_to_date(OUT_FIT, FIT_SOURCES, FIT_HEADERS)
+
+
 def up_to_date():
-    if not os.path.exists(OUT) or not companion_up_to_date() or not rsz_up_to_date() or not area_up_to_date():
+    if not os.path.exists(OUT) or not companion_up_to_date() or not rsz_up_to_date() or not area_up_to_date() or not fit_up_to_date():
         return False
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
@@ -120,6 +131,14 @@ def build_area(force=False, verbose=False):
     return _build_companion(OUT_AREA, AREA_SOURCES, "build_area", verbose)
 
 
+def build_fit(force=False, verbose=False):
+    """librip_fit_hip.so, next to librip_hip.so; its interface is rip_fit.hpp (with the parameter structs of rip_resize.hpp and
+    rip_area.hpp)."""
+    if not force and fit_up_to_date():
+        return OUT_FIT
+    return _build_companion(OUT_FIT, FIT_SOURCES, "build_fit", verbose)
+
+
 # --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under
 # AddressSanitizer + UndefinedBehaviorSanitizer, compiled with g++ against GCC's runtimes; the device code is compiled by hipcc
 # as always.  (Not clang's runtime: the ROCm build of compiler-rt intercepts hsa_amd_memory_pool_allocate for device-side ASan and
@@ -147,13 +166,14 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
     out=".../variants/x.so"; the default build takes no extra flags beyond $RIP_EXTRA_FLAGS."""
     if asan:
         out, tag = out or ASAN_OUT, tag or "_asan"
-        if not force and os.path.exists(out) and companion_up_to_date() and rsz_up_to_date() and area_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
+        if not force and os.path.exists(out) and companion_up_to_date() and rsz_up_to_date() and area_up_to_date() and fit_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
             return out
     if out is None and not force and up_to_date():
         return OUT
-    build_companion(verbose=verbose)  # every build of librip_hip.so links against all three; `force` is about the library asked for
+    build_companion(verbose=verbose)  # every build of librip_hip.so links against all four; `force` is about the library asked for
     build_rsz(verbose=verbose)
     build_area(verbose=verbose)
+    build_fit(verbose=verbose)
     out = out or OUT
     objs = []
     procs = []
@@ -176,7 +196,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
         if verbose and log.strip():
             print(log)
     # the companions are found next to the library ($ORIGIN) or one directory up (variants/*.so)
-    companion = ["-L" + HERE, "-l:" + os.path.basename(OUT_COMPANION), "-l:" + os.path.basename(OUT_RSZ), "-l:" + os.path.basename(OUT_AREA), "-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    companion = ["-L" + HERE, "-l:" + os.path.basename(OUT_COMPANION), "-l:" + os.path.basename(OUT_RSZ), "-l:" + os.path.basename(OUT_AREA), "-l:" + os.path.basename(OUT_FIT), "-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
     cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -385,6 +385,12 @@ RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, cons
 RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), rip::check_output_size(width, height); p->m.out_w = width; p->m.out_h = height)
 RIP_SETTER(rip_set_output_interpolation, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            (void)rip::output_interpolation_id(s); p->m.out_interp = s)
+RIP_SETTER(rip_set_output_roi, (rip_pipeline * p, int x, int y, int width, int height), rip::check_output_roi(x, y, width, height);
+           p->m.roi_x = x; p->m.roi_y = y; p->m.roi_w = width; p->m.roi_h = height)
+RIP_SETTER(rip_set_output_fit, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+           (void)rip::output_fit_id(s); p->m.out_fit = s)
+RIP_SETTER(rip_set_output_pad, (rip_pipeline * p, int b, int g, int r), rip::check_output_pad(b, g, r);
+           p->m.out_pad[0] = b; p->m.out_pad[1] = g; p->m.out_pad[2] = r)
 RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
 RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)
 RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v != 0)
@@ -458,6 +464,7 @@ int rip_get_rect_image_width(const rip_pipeline* p) { return p ? p->m.rect_w : 0
 RIP_GET_STRING(rip_get_debayer_method, p->m.debayer_method)
 RIP_GET_STRING(rip_get_output_format, p->m.out_format)
 RIP_GET_STRING(rip_get_output_interpolation, p->m.out_interp)
+RIP_GET_STRING(rip_get_output_fit, p->m.out_fit)
 
 rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, double* mean, double* sd) {
   return guarded(p, [&] {
@@ -478,6 +485,47 @@ rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height) {
   });
 }
 
+rip_status rip_get_output_roi(const rip_pipeline* p, int* x, int* y, int* width, int* height) {
+  return guarded(p, [&] {
+    need(p);
+    if (x) *x = p->m.roi_x;
+    if (y) *y = p->m.roi_y;
+    if (width) *width = p->m.roi_w;
+    if (height) *height = p->m.roi_h;
+  });
+}
+
+rip_status rip_get_output_pad(const rip_pipeline* p, int* b, int* g, int* r) {
+  return guarded(p, [&] {
+    need(p);
+    if (b) *b = p->m.out_pad[0];
+    if (g) *g = p->m.out_pad[1];
+    if (r) *r = p->m.out_pad[2];
+  });
+}
+
+rip_status rip_get_output_window(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int src_xywh[4], int dst_xywh[4]) {
+  return guarded(p, [&] {
+    need(p);
+    if (!encoding) throw InvalidArgument("encoding is null");
+    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
+    apply_output_format(p->m, pl);
+    const int src[4] = {pl.win_x, pl.win_y, pl.win_w, pl.win_h}, dst[4] = {pl.pic_x, pl.pic_y, pl.pic_w, pl.pic_h};
+    if (src_xywh) std::memcpy(src_xywh, src, sizeof(src));
+    if (dst_xywh) std::memcpy(dst_xywh, dst, sizeof(dst));
+  });
+}
+
+rip_status rip_debug_output_window(int cols, int rows, const int roi_xywh[4], int width, int height, const char* fit, int src_xywh[4], int dst_xywh[4]) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    if (!roi_xywh || !fit || !src_xywh || !dst_xywh) throw InvalidArgument("rip_debug_output_window: null argument");
+    if (cols < 1 || rows < 1) throw InvalidArgument("rip_debug_output_window: empty image");
+    rip::check_output_roi(roi_xywh[0], roi_xywh[1], roi_xywh[2], roi_xywh[3]);
+    rip::check_output_size(width, height);
+    rip::output_window_geometry(cols, rows, roi_xywh, width, height, rip::output_fit_id(fit), src_xywh, dst_xywh);
+  });
+}
+
 rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* height, int* width, double K[9],
                                       double P[12]) {
   return guarded(p, [&] {
@@ -489,7 +537,24 @@ rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int c
     double k[9], pr[12];
     for (int i = 0; i < 9; i++) k[i] = pl.remap ? m.rect_K[i] : m.dist_K[i];
     for (int i = 0; i < 12; i++) pr[i] = pl.remap ? m.rect_P[i] : m.dist_P[i];
-    if (pl.rsz_active) {
+    if (pl.fit_geometry) {
+      // the same mapping from the window that is read to the picture's rectangle: u = (u' - left + 0.5) / a - 0.5 + xs (PARITY.md
+      // "Resize: window and fit"); every operation rounded, in this order
+      const double a = (double)pl.pic_w / pl.win_w, b = (double)pl.pic_h / pl.win_h;
+      const double xs = pl.win_x, ys = pl.win_y, left = pl.pic_x, top = pl.pic_y;
+      k[0] *= a;
+      k[1] *= a;
+      k[2] = (a * ((k[2] - xs) + 0.5) - 0.5) + left;
+      k[4] *= b;
+      k[5] = (b * ((k[5] - ys) + 0.5) - 0.5) + top;
+      pr[0] *= a;
+      pr[1] *= a;
+      pr[2] = (a * ((pr[2] - xs) + 0.5) - 0.5) + left;
+      pr[3] *= a;
+      pr[5] *= b;
+      pr[6] = (b * ((pr[6] - ys) + 0.5) - 0.5) + top;
+      pr[7] *= b;
+    } else if (pl.rsz_active) {
       // the inverse of the tables' pixel-centre mapping u = (u' + 0.5) / a - 0.5 (PARITY.md "Resize")
       const double a = (double)pl.dl_cols / pl.out_cols, b = (double)pl.dl_rows / pl.out_rows;
       k[0] *= a;

@@ -914,8 +914,9 @@ static AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W
 
 // run_batch with the resize and the output stage behind it.  With a target size other than F's, or under a format, the chain's
 // last kernel writes the pipeline's image F into the handle's staging buffer; then one launch of the resize (librip_rsz_hip.so, or
-// librip_area_hip.so under the area interpolation) writes F' -- into the caller's buffer under "native", else into a second
-// staging image -- and one launch of the converter (librip_out_hip.so) writes the caller's buffer from F' (or from F without a target).  Neither: this is run_batch.
+// librip_area_hip.so under the area interpolation; librip_fit_hip.so when it reads a window of F, rip_set_output_roi) writes F' --
+// into the caller's buffer under "native", else into a second staging image; under a letterbox it writes the picture's rectangle of
+// F' and one launch of the pad kernel fills the rest -- and one launch of the converter (librip_out_hip.so) writes the caller's buffer from F' (or from F without a target).  Neither: this is run_batch.
 // dst: the DELIVERED frames.
 void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n) {
   if (pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active) {
@@ -931,8 +932,9 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   ResizeTables rt = {};
   AreaTables at = {};
   if (pl.rsz_active) {
-    if (pl.rsz_area) at = ensure_area_tables(p, pl.out_rows, pl.out_cols, pl.dl_rows, pl.dl_cols);
-    else rt = ensure_resize_tables(p, pl.out_rows, pl.out_cols, pl.dl_rows, pl.dl_cols);
+    // from the window that is read to the picture that is written: all of F and all of F' unless a window or a fit mode is set
+    if (pl.rsz_area) at = ensure_area_tables(p, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
+    else rt = ensure_resize_tables(p, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
     if (pl.out_fmt != rip::OUT_NATIVE) {  // the converter's source alignment
       const size_t pitch = ((size_t)pl.dl_cols * pl.channels + 15) & ~(size_t)15;
       converted_from = {nullptr, pitch, pitch * (size_t)pl.dl_rows, pl.dl_rows, pl.dl_cols};
@@ -942,8 +944,19 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   }
   run_batch(p, pl, src, staged, taps, n);
   LaunchLogScope log_scope(p);
+  // F': the caller's buffer under "native", else the second staging image; the picture's rectangle of it is what the resize writes
+  const FrameView whole_to = pl.out_fmt != rip::OUT_NATIVE ? converted_from : dst;
+  FrameView to = whole_to;
+  to.ptr += (size_t)pl.pic_y * to.step + (size_t)pl.pic_x * pl.channels;
+  // a window other than F is read in place by the kernels of librip_fit_hip.so, which take the window's origin; no copy of it is made
+  const rip::FitWindow win = {pl.win_x, pl.win_y, pl.out_cols, pl.out_rows};
+  const auto log_fit = [&](bool launched, const rip::FitLaunchInfo& info, const char* what) {
+    if (!launched) throw DeviceError(std::string("internal: ") + what + " refused a layout the frame call had accepted");
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+    RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+  };
   if (pl.rsz_active && pl.rsz_area) {
-    const FrameView to = pl.out_fmt != rip::OUT_NATIVE ? converted_from : dst;
     rip::AreaParams r = {};
     r.src = staged.ptr;
     r.src_step = staged.step;
@@ -951,10 +964,10 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
     r.dst = to.ptr;
     r.dst_step = to.step;
     r.dst_frame_stride = to.frame_stride;
-    r.src_rows = pl.out_rows;
-    r.src_cols = pl.out_cols;
-    r.rows = pl.dl_rows;
-    r.cols = pl.dl_cols;
+    r.src_rows = pl.win_h;
+    r.src_cols = pl.win_w;
+    r.rows = pl.pic_h;
+    r.cols = pl.pic_w;
     r.channels = pl.channels;
     r.n_frames = n;
     r.whole = at.whole;
@@ -967,13 +980,17 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
     r.ycount = at.ycount;
     r.ywofs = at.ywofs;
     r.yweight = at.yweight;
-    rip::AreaLaunchInfo info = {};
-    if (!rip::launch_area_reduce(r, p->stream, &info)) throw DeviceError("internal: the area resize refused a layout the frame call had accepted");
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
-    RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+    if (!pl.win_is_frame()) {
+      rip::FitLaunchInfo fit_info = {};
+      log_fit(rip::launch_fit_area(r, win, p->stream, &fit_info), fit_info, "the area resize of a window");
+    } else {
+      rip::AreaLaunchInfo info = {};
+      if (!rip::launch_area_reduce(r, p->stream, &info)) throw DeviceError("internal: the area resize refused a layout the frame call had accepted");
+      hipError_t le = hipGetLastError();
+      if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+      RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+    }
   } else if (pl.rsz_active) {
-    const FrameView to = pl.out_fmt != rip::OUT_NATIVE ? converted_from : dst;
     rip::ResizeParams r = {};
     r.src = staged.ptr;
     r.src_step = staged.step;
@@ -981,10 +998,10 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
     r.dst = to.ptr;
     r.dst_step = to.step;
     r.dst_frame_stride = to.frame_stride;
-    r.src_rows = pl.out_rows;
-    r.src_cols = pl.out_cols;
-    r.rows = pl.dl_rows;
-    r.cols = pl.dl_cols;
+    r.src_rows = pl.win_h;
+    r.src_cols = pl.win_w;
+    r.rows = pl.pic_h;
+    r.cols = pl.pic_w;
     r.channels = pl.channels;
     r.n_frames = n;
     r.area2 = rt.area2;
@@ -992,11 +1009,33 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
     r.alpha = rt.alpha;
     r.yofs = rt.yofs;
     r.beta = rt.beta;
-    rip::ResizeLaunchInfo info = {};
-    if (!rip::launch_resize(r, p->stream, &info)) throw DeviceError("internal: the resize refused a layout the frame call had accepted");
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
-    RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+    if (!pl.win_is_frame()) {
+      rip::FitLaunchInfo fit_info = {};
+      log_fit(rip::launch_fit_resize(r, win, p->stream, &fit_info), fit_info, "the resize of a window");
+    } else {
+      rip::ResizeLaunchInfo info = {};
+      if (!rip::launch_resize(r, p->stream, &info)) throw DeviceError("internal: the resize refused a layout the frame call had accepted");
+      hipError_t le = hipGetLastError();
+      if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
+      RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+    }
+  }
+  if (pl.rsz_active && !pl.pic_is_delivered()) {  // a letterbox: the bands around the picture get the pad colour
+    rip::FitPadParams f = {};
+    f.dst = whole_to.ptr;
+    f.dst_step = whole_to.step;
+    f.dst_frame_stride = whole_to.frame_stride;
+    f.rows = pl.dl_rows;
+    f.cols = pl.dl_cols;
+    f.pic_x = pl.pic_x;
+    f.pic_y = pl.pic_y;
+    f.pic_w = pl.pic_w;
+    f.pic_h = pl.pic_h;
+    f.channels = pl.channels;
+    f.n_frames = n;
+    for (int i = 0; i < 4; i++) f.color[i] = pl.pad[i];
+    rip::FitLaunchInfo fit_info = {};
+    log_fit(rip::launch_fit_pad(f, p->stream, &fit_info), fit_info, "the letterbox pad");
   }
   if (pl.out_fmt == rip::OUT_NATIVE) return;
   rip::OutputConvertParams c = {};

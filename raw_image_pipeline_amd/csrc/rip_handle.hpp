@@ -17,6 +17,7 @@
 #include "rip_kernels.hpp"
 #include "rip_output.hpp"
 #include "rip_area.hpp"
+#include "rip_fit.hpp"
 #include "rip_resize.hpp"
 
 namespace rip {
@@ -131,6 +132,16 @@ struct Plan {
   // that kernel is the area interpolation's (rip_set_output_interpolation "area"; rip_area.hpp): false for the exact 2 x 2 case,
   // which is the mean kernel of the linear path under either name
   bool rsz_area = false;
+  // the window and the fit mode (rip_set_output_roi, rip_set_output_fit; rip::output_window_geometry): win_* is the rectangle of F
+  // the resize reads, pic_* the rectangle of the delivered dl_rows x dl_cols image it writes; every other delivered pixel gets `pad`
+  // (channels bytes).  fit_geometry: a window or a fit mode other than "stretch" is set, so these fields decide (without either
+  // the window is F, the picture is the delivered image and the code paths are the ones from before there was a window).
+  bool fit_geometry = false;
+  int win_x = 0, win_y = 0, win_w = 0, win_h = 0;
+  int pic_x = 0, pic_y = 0, pic_w = 0, pic_h = 0;
+  uint8_t pad[4] = {0, 0, 0, 0};
+  bool win_is_frame() const { return win_x == 0 && win_y == 0 && win_w == out_cols && win_h == out_rows; }
+  bool pic_is_delivered() const { return pic_w == dl_cols && pic_h == dl_rows; }
 };
 
 // n frames of rows x cols pixels in device memory: rows `step` bytes apart, frames `frame_stride` bytes apart (both resolved,

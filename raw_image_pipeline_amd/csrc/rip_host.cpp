@@ -326,6 +326,30 @@ void params_from_node(Modules& m, const YamlNode& node) {
   (void)output_interpolation_id(out_interp);
   if (o["interpolation"].defined() && o["interpolation"].kind != YamlNode::Scalar)
     throw std::invalid_argument("output: interpolation: one word is expected, \"linear\" or \"area\"");
+  // extension keys output: roi: [x, y, w, h] / fit: stretch | letterbox | crop / pad: [b, g, r] (rip_set_output_roi,
+  // rip_set_output_fit, rip_set_output_pad); absent keys mean the defaults
+  int roi[4] = {0, 0, 0, 0}, pad[3] = {114, 114, 114};
+  for (int which = 0; which < 2; which++) {
+    const char* key = which ? "pad" : "roi";
+    const size_t n = which ? 3 : 4;
+    if (!o[key].defined()) continue;
+    const std::vector<double> v = o.get_vector(key);
+    bool ok = v.size() == n;
+    for (size_t i = 0; ok && i < n; i++) ok = v[i] >= 0 && v[i] <= (1 << 22) && v[i] == std::floor(v[i]);
+    if (!ok)
+      throw std::invalid_argument(which ? "output: pad: a sequence [b, g, r] of three integers in 0..255 is expected"
+                                        : "output: roi: a sequence [x, y, width, height] of four integers is expected, x and y at least 0, width and height in 1..16384 (or four zeros)");
+    for (size_t i = 0; i < n; i++) (which ? pad : roi)[i] = (int)v[i];
+  }
+  check_output_roi(roi[0], roi[1], roi[2], roi[3]);
+  check_output_pad(pad[0], pad[1], pad[2]);
+  const std::string out_fit = o.get("fit", std::string("stretch"));
+  (void)output_fit_id(out_fit);
+  if (o["fit"].defined() && o["fit"].kind != YamlNode::Scalar)
+    throw std::invalid_argument("output: fit: one word is expected, \"stretch\", \"letterbox\" or \"crop\"");
+  m.roi_x = roi[0], m.roi_y = roi[1], m.roi_w = roi[2], m.roi_h = roi[3];
+  m.out_fit = out_fit;
+  for (int i = 0; i < 3; i++) m.out_pad[i] = pad[i];
   m.out_w = out_w;
   m.out_h = out_h;
   m.out_interp = out_interp;
@@ -524,6 +548,58 @@ void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alp
     yofs[2 * dy + 1] = std::min(std::max(sy + 1, 0), R - 1);
   }
   if (area2) *area2 = (R == 2 * H && C == 2 * W) ? 1 : 0;
+}
+
+void check_output_roi(int x, int y, int width, int height) {
+  if (x == 0 && y == 0 && width == 0 && height == 0) return;  // off
+  if (x < 0 || y < 0 || width < 1 || height < 1 || width > 16384 || height > 16384)
+    throw std::invalid_argument("output roi (" + std::to_string(x) + ", " + std::to_string(y) + ", " + std::to_string(width) + ", " + std::to_string(height) +
+                                ") not supported: (0, 0, 0, 0) switches it off, otherwise x and y are at least 0 and width and height are in 1..16384");
+}
+
+int output_fit_id(const std::string& name) {
+  if (name == "stretch") return 0;
+  if (name == "letterbox") return 1;
+  if (name == "crop") return 2;
+  throw std::invalid_argument("output fit \"" + name + "\" not supported: \"stretch\", \"letterbox\" or \"crop\"");
+}
+
+void check_output_pad(int b, int g, int r) {
+  for (int v : {b, g, r})
+    if (v < 0 || v > 255)
+      throw std::invalid_argument("output pad (" + std::to_string(b) + ", " + std::to_string(g) + ", " + std::to_string(r) + ") not supported: every component is in 0..255");
+}
+
+int output_pad_grey(int b, int g, int r) { return (3735 * b + 19235 * g + 9798 * r + 16384) >> 15; }
+
+void output_window_geometry(int C, int R, const int roi[4], int W, int H, int fit, int src[4], int dst[4]) {
+  int x = 0, y = 0, w = C, h = R;
+  if (roi[2] > 0) {
+    x = roi[0], y = roi[1], w = roi[2], h = roi[3];
+    if (x > C - w || y > R - h)  // x + w > C or y + h > R, without the sum
+      throw std::invalid_argument("output roi (" + std::to_string(x) + ", " + std::to_string(y) + ", " + std::to_string(w) + ", " + std::to_string(h) +
+                                  ") does not lie inside the pipeline's image of " + std::to_string(C) + " x " + std::to_string(R));
+  }
+  const auto clamp = [](long long v, int lo, int hi) { return (int)std::min<long long>(std::max<long long>(v, lo), hi); };
+  int left = 0, top = 0, wi = W > 0 ? W : w, hi = W > 0 ? H : h;
+  if (W > 0 && fit == 2) {  // the centred sub-window with the target's aspect
+    if ((long long)w * H >= (long long)h * W) {
+      const int w2 = clamp((2ll * h * W + H) / (2ll * H), 1, w);
+      x += (w - w2) / 2;
+      w = w2;
+    } else {
+      const int h2 = clamp((2ll * w * H + W) / (2ll * W), 1, h);
+      y += (h - h2) / 2;
+      h = h2;
+    }
+  } else if (W > 0 && fit == 1) {  // the whole window, centred in the target
+    if ((long long)W * h <= (long long)H * w) hi = clamp((2ll * h * W + w) / (2ll * w), 1, H);
+    else wi = clamp((2ll * w * H + h) / (2ll * h), 1, W);
+    left = (W - wi) / 2;
+    top = (H - hi) / 2;
+  }
+  src[0] = x, src[1] = y, src[2] = w, src[3] = h;
+  dst[0] = left, dst[1] = top, dst[2] = wi, dst[3] = hi;
 }
 
 int output_interpolation_id(const std::string& name) {

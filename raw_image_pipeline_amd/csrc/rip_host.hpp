@@ -66,6 +66,12 @@ struct Modules {
   int out_w = 0, out_h = 0;
   // extension (rip_set_output_interpolation): the filter of that resize, "linear" or "area"; without effect while no target is active
   std::string out_interp = "linear";
+  // extension (rip_set_output_roi, rip_set_output_fit, rip_set_output_pad; PARITY.md "Resize: window and fit"): the window of the
+  // final image the resize stage reads ((0, 0, 0, 0) = all of it), how the window is placed in the target ("stretch", "letterbox",
+  // "crop"; without effect while no target is active) and the colour (B, G, R) of what a letterbox leaves uncovered
+  int roi_x = 0, roi_y = 0, roi_w = 0, roi_h = 0;
+  std::string out_fit = "stretch";
+  int out_pad[3] = {114, 114, 114};
   // FlipModule (flip.hpp:63-66)
   bool flip_enabled = false;
   int flip_angle = 0;
@@ -132,6 +138,20 @@ int output_interpolation_id(const std::string& name);
 // The sizes the area interpolation takes, from R x C to H x W: every side in 1 .. 16384, no upscale (H <= R, W <= C) and a factor of at
 // most 256 per axis (R <= 256 H, C <= 256 W: a block sum stays below 2^24).  Throws std::invalid_argument naming the rule.
 void check_resize_area_sizes(int R, int C, int H, int W);
+// the windows rip_set_output_roi accepts: (0, 0, 0, 0), or x, y >= 0 with width and height in 1 .. 16384; throws std::invalid_argument
+void check_output_roi(int x, int y, int width, int height);
+// the names rip_set_output_fit accepts: 0 for "stretch", 1 for "letterbox", 2 for "crop"; throws std::invalid_argument naming them otherwise
+int output_fit_id(const std::string& name);
+// the pad colours rip_set_output_pad accepts: every component in 0 .. 255; throws std::invalid_argument
+void check_output_pad(int b, int g, int r);
+// the pad byte of a one-channel result: the grey value (3735 b + 19235 g + 9798 r + 16384) >> 15 of the colour, as "mono8" computes it
+int output_pad_grey(int b, int g, int r);
+// The geometry of the resize stage with a window and a fit mode (PARITY.md "Resize: window and fit"; integers, C division), for a
+// final image F of R x C: roi = (x, y, w, h) or four zeros for all of F; (W, H) the target or (0, 0) for none; fit as
+// output_fit_id numbers it.  src_xywh: the rectangle of F that is read (the window, shrunk to the target's aspect under "crop");
+// dst_xywh: the rectangle of the delivered image that holds picture (all of it except under "letterbox"); the delivered image is
+// H x W, or the window's size without a target.  Throws std::invalid_argument for a window that does not lie inside F.
+void output_window_geometry(int C, int R, const int roi[4], int W, int H, int fit, int src_xywh[4], int dst_xywh[4]);
 // The tap list of one axis of the area interpolation (cv::resize(8U, INTER_AREA), imgproc/resize.cpp computeResizeAreaTab, in double;
 // PARITY.md "Resize: area interpolation") from s source to d target samples, d <= s: output i reads the count[i] >= 1 consecutive
 // source samples from first[i] on, all inside [0, s), with the float weights that follow each other in `weights` in output order

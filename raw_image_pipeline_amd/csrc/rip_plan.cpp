@@ -151,7 +151,37 @@ void apply_output_format(const rip::Modules& m, Plan& pl) {
   // the resize stage (rip_set_output_size) sits between F and the format: the delivered geometry is the target's
   pl.dl_rows = pl.out_rows;
   pl.dl_cols = pl.out_cols;
-  if (m.out_w > 0) {
+  pl.win_w = pl.pic_w = pl.out_cols;
+  pl.win_h = pl.pic_h = pl.out_rows;
+  const int fit = rip::output_fit_id(m.out_fit);
+  pl.fit_geometry = m.roi_w > 0 || (m.out_w > 0 && fit != 0);
+  if (pl.fit_geometry) {
+    // a window, or a fit mode that changes what a target means (PARITY.md "Resize: window and fit").  The refusals in their order:
+    // a bgr16 result, a window outside F, an F beyond the resize's sides, the area interpolation's rules on window -> picture.
+    if (pl.out_elem_bytes != 1)
+      throw InvalidArgument("output roi / fit need an 8-bit pipeline result; this frame gives bgr16 (set a 16-bit range, or the roi (0, 0, 0, 0) and the fit 'stretch')");
+    const int roi[4] = {m.roi_x, m.roi_y, m.roi_w, m.roi_h};
+    int src[4], dst[4];
+    rip::output_window_geometry(pl.out_cols, pl.out_rows, roi, m.out_w, m.out_h, fit, src, dst);
+    pl.win_x = src[0], pl.win_y = src[1], pl.win_w = src[2], pl.win_h = src[3];
+    pl.pic_x = dst[0], pl.pic_y = dst[1], pl.pic_w = dst[2], pl.pic_h = dst[3];
+    pl.dl_cols = m.out_w > 0 ? m.out_w : pl.win_w;
+    pl.dl_rows = m.out_w > 0 ? m.out_h : pl.win_h;
+    if (pl.channels == 1) pl.pad[0] = (uint8_t)rip::output_pad_grey(m.out_pad[0], m.out_pad[1], m.out_pad[2]);
+    else for (int i = 0; i < 3; i++) pl.pad[i] = (uint8_t)m.out_pad[i];
+    // all of F delivered as it is: today's identity rule, nothing is launched
+    if (!(pl.win_is_frame() && pl.pic_is_delivered() && pl.dl_cols == pl.out_cols && pl.dl_rows == pl.out_rows)) {
+      if (pl.out_rows > rip::kRszMaxSide || pl.out_cols > rip::kRszMaxSide)
+        throw InvalidArgument("output size: the pipeline's image of " + std::to_string(pl.out_cols) + " x " + std::to_string(pl.out_rows) +
+                              " is larger than the " + std::to_string(rip::kRszMaxSide) + " pixels per side the resize takes");
+      // a picture of the window's own size is a copy, which the linear tables are (weights 2048 and 0) under either interpolation
+      if (rip::output_interpolation_id(m.out_interp) == 1 && !(pl.win_w == pl.pic_w && pl.win_h == pl.pic_h)) {
+        rip::check_resize_area_sizes(pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
+        pl.rsz_area = !(pl.win_h == 2 * pl.pic_h && pl.win_w == 2 * pl.pic_w);
+      }
+      pl.rsz_active = true;
+    }
+  } else if (m.out_w > 0) {
     if (pl.out_elem_bytes != 1)
       throw InvalidArgument("output size (" + std::to_string(m.out_w) + ", " + std::to_string(m.out_h) +
                             ") needs an 8-bit pipeline result; this frame gives bgr16 (set a 16-bit range, or the output size (0, 0))");
@@ -167,6 +197,8 @@ void apply_output_format(const rip::Modules& m, Plan& pl) {
       pl.rsz_active = true;
       pl.dl_rows = m.out_h;
       pl.dl_cols = m.out_w;
+      pl.pic_w = pl.dl_cols;
+      pl.pic_h = pl.dl_rows;
     }
   }
   const int fmt = rip::output_format_id(m.out_format);

@@ -686,6 +686,43 @@ class RawImagePipeline:
     def get_output_interpolation(self):
         return self._string("rip_get_output_interpolation")
 
+    def set_output_roi(self, x, y, width, height):
+        """Extension: the window (x, y, width, height) of the pipeline's final image that the resize stage reads in place of the whole
+        image; (0, 0, 0, 0) (default) is off.  Without a target size the frame calls deliver the window itself.  A window that does
+        not lie inside the image is refused by the frame calls and the queries (ValueError).  include/rip.h rip_set_output_roi."""
+        self._call("rip_set_output_roi", int(x), int(y), int(width), int(height))
+
+    def get_output_roi(self):
+        v = [C.c_int() for _ in range(4)]
+        self._call("rip_get_output_roi", *[C.byref(i) for i in v])
+        return tuple(i.value for i in v)
+
+    def set_output_fit(self, name):
+        """Extension: how the window is placed in the target size -- ``"stretch"`` (default), ``"letterbox"`` (aspect kept, the
+        rest padded) or ``"crop"`` (the centred part with the target's aspect).  Without effect until ``set_output_size`` has set
+        a target.  include/rip.h rip_set_output_fit."""
+        self._call("rip_set_output_fit", name.encode())
+
+    def get_output_fit(self):
+        return self._string("rip_get_output_fit")
+
+    def set_output_pad(self, b, g, r):
+        """Extension: the colour (B, G, R of the image in front of the output format, each 0..255, default 114) of what a
+        letterbox leaves uncovered.  include/rip.h rip_set_output_pad."""
+        self._call("rip_set_output_pad", int(b), int(g), int(r))
+
+    def get_output_pad(self):
+        v = [C.c_int() for _ in range(3)]
+        self._call("rip_get_output_pad", *[C.byref(i) for i in v])
+        return tuple(i.value for i in v)
+
+    def get_output_window(self, rows, cols, channels, encoding):
+        """((x, y, w, h) of the final image that is read, (x, y, w, h) of the delivered image that holds picture) for such an input
+        frame; everything outside the second rectangle is pad.  include/rip.h rip_get_output_window."""
+        src, dst = (C.c_int * 4)(), (C.c_int * 4)()
+        self._call("rip_get_output_window", int(rows), int(cols), int(channels), encoding.encode(), src, dst)
+        return tuple(src), tuple(dst)
+
     def get_output_camera_info(self, rows, cols, channels, encoding):
         """(height, width, K [3, 3], P [3, 4]) of the image the frame calls deliver for such an input frame: the rect (or, without
         undistortion, dist) matrices scaled to the target size about the pixel centres.  include/rip.h rip_get_output_camera_info."""

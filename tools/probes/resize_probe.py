@@ -12,7 +12,12 @@ resize_probe.py --interpolation [OUT.txt] (default profiles/resize_area_kernel_t
 area interpolation (rip::launch_area_reduce of librip_area_hip.so; at exactly half size the 2 x 2 mean kernel of librip_rsz_hip.so)
 and of the linear kernel at the same three targets -- 612 x 512 (whole 4 x 4), 640 x 480 (tap lists), 1224 x 1024 (2 x 2) -- on the
 same resident batch, alternating the two filters; each time with its spread and the fraction of 8 TB/s it stands for on
-3 R C + 3 H W bytes per frame.  One frame of every area launch is compared with tests/area_reference.py first."""
+3 R C + 3 H W bytes per frame.  One frame of every area launch is compared with tests/area_reference.py first.
+
+resize_probe.py --fit [OUT.txt] (default profiles/resize_fit_times.txt) is a third run: rip_apply_device on the same resident batch
+with every stage off, 2448 x 2048 -> 640 x 480 under "stretch", "letterbox" and "crop" (rip_set_output_fit), linear and area, the
+six settings alternating on one handle; one frame of each is compared with tests/fit_reference.py first.  The stretch legs read
+all of the image through the existing kernels; crop reads a window through librip_fit_hip.so; letterbox adds the pad launch."""
 import ctypes as C
 import os
 import sys
@@ -27,8 +32,10 @@ from raw_image_pipeline_amd import build as B  # noqa: E402
 
 N, R_, C_ = 256, 2048, 2448
 INTERPOLATION = "--interpolation" in sys.argv[1:]
-ARGS = [a for a in sys.argv[1:] if a != "--interpolation"]
-OUT = open(ARGS[0] if ARGS else os.path.join(ROOT, "profiles", "resize_area_kernel_times.txt" if INTERPOLATION else "resize_kernel_times.txt"), "w")
+FIT = "--fit" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a not in ("--interpolation", "--fit")]
+OUT = open(ARGS[0] if ARGS else os.path.join(ROOT, "profiles", "resize_fit_times.txt" if FIT else
+                                             "resize_area_kernel_times.txt" if INTERPOLATION else "resize_kernel_times.txt"), "w")
 
 
 def say(line):
@@ -150,7 +157,58 @@ def interpolation_main():
     say("done")
 
 
+def fit_main():
+    """2448 x 2048 -> 640 x 480 through rip_apply_device under the three fit modes and both filters, 5 rounds of 2 calls each per
+    setting, the settings alternating, after a warm-up call each."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fit_reference as FR
+    W, H = 640, 480
+    g = torch.Generator(device="cuda").manual_seed(1)
+    frames = torch.randint(0, 256, (N, R_, C_, 3), dtype=torch.uint8, device="cuda", generator=g)
+    pipe = RawImagePipeline(False, "", "", "", device=0)
+    for s in ("set_white_balance", "set_undistortion", "set_vignetting_correction", "set_color_calibration", "set_gamma_correction", "set_color_enhancer",
+              "set_flip"):
+        getattr(pipe, s)(False)
+    pipe.set_output_size(W, H)
+    out = torch.empty((N, H, W, 3), dtype=torch.uint8, device="cuda")
+    say("frames %d x %d x %d x 3 uint8 = %.1f MB resident, every stage off; rip_apply_device -> %d x %d; HIP events around 2 calls, 5 rounds per "
+        "setting, the six settings alternating, after a warm-up call each; ms per call of %d frames" % (N, R_, C_, frames.numel() / 1e6, W, H, N))
+    legs = [(fit, interp) for interp in ("linear", "area") for fit in ("stretch", "letterbox", "crop")]
+
+    def call(fit, interp):
+        pipe.set_output_fit(fit)
+        pipe.set_output_interpolation(interp)
+        pipe.apply_device(frames, "bgr8", out=out)
+    host = frames[3].cpu().numpy()
+    kernels = {}
+    for fit, interp in legs:
+        with pipe.launch_log() as log:
+            call(fit, interp)
+            torch.cuda.synchronize()
+        kernels[fit, interp] = " + ".join(n for n in log.names() if n.startswith(("fit_", "resize_kernel", "area_reduce_kernel")))
+        assert np.array_equal(out[3].cpu().numpy(), FR.expected(host, None, (W, H), fit, interp)), "the timed call differs from the reference: %s %s" % (fit, interp)
+    times = {leg: [] for leg in legs}
+    for _ in range(5):
+        for leg in legs:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            call(*leg)
+            call(*leg)
+            b.record()
+            b.synchronize()
+            times[leg].append(a.elapsed_time(b) / 2)
+    say("%-10s %-8s %9s %9s %9s %9s  %s" % ("fit", "filter", "median", "min", "max", "/stretch", "window read, picture written, kernels of the stage"))
+    for fit, interp in legs:
+        t, base = times[fit, interp], float(np.median(times["stretch", interp]))
+        src, dst = pipe.set_output_fit(fit) or pipe.get_output_window(R_, C_, 3, "bgr8")
+        say("%-10s %-8s %9.3f %9.3f %9.3f %9.3f  %s -> %s, %s" % (fit, interp, float(np.median(t)), min(t), max(t), float(np.median(t)) / base, src, dst,
+                                                               kernels[fit, interp]))
+    say("done")
+
+
 def main():
+    if FIT:
+        return fit_main()
     if INTERPOLATION:
         return interpolation_main()
     lib = load_library()
