@@ -1,10 +1,9 @@
-"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companions librip_out_hip.so (the kernels of the output
-stage, csrc/rip_output.hip), librip_rsz_hip.so (the kernels of the resize stage, csrc/rip_resize.hip) and librip_area_hip.so (the
-resize stage's area interpolation, csrc/rip_area.hip) and librip_fit_hip.so (the resize stage on a window of the image and the
-letterbox bands, csrc/rip_fit.hip) for gfx950 with hipcc.
+"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the table COMPANIONS below: the kernels
+of the output stage and the three libraries of the resize stage -- for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
+import functools
 import os
 import subprocess
 import sys
@@ -14,29 +13,28 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
 HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", os.path.join("..", "..", "include", "rip.h")]
-# The companion library: the output stage's kernels (rip_set_output_format) and their one launch function (rip_output.hpp).  A
-# library of its own so that librip_hip.so's kernel table stays what tests/variant_cases.py closes over; the companion's table
-# is closed by tests/output_variant_cases.py.  librip_hip.so -- every build of it: the default one, the sanitizer build and the
-# A/B variants under variants/ -- links against this one file and finds it through its $ORIGIN rpath.
-OUT_COMPANION = os.path.join(HERE, "librip_out_hip.so")
-COMPANION_SOURCES = ["rip_output.hip"]
-COMPANION_HEADERS = ["rip_output.hpp"]
-# The second companion, on the same terms: the resize stage's kernels (rip_set_output_size) behind rip_resize.hpp; its table is
-# closed by tests/resize_variant_cases.py.
-OUT_RSZ = os.path.join(HERE, "librip_rsz_hip.so")
-RSZ_SOURCES = ["rip_resize.hip"]
-RSZ_HEADERS = ["rip_resize.hpp"]
-# The third companion, on the same terms: the kernels of the resize stage's area interpolation (rip_set_output_interpolation)
-# behind rip_area.hpp; its table is closed by tests/area_variant_cases.py.
-OUT_AREA = os.path.join(HERE, "librip_area_hip.so")
-AREA_SOURCES = ["rip_area.hip"]
-AREA_HEADERS = ["rip_area.hpp"]
-# The fourth companion, on the same terms: the resize stage's kernels that read a window of the image, and the pad kernel of the
-# letterbox (rip_set_output_roi, rip_set_output_fit) behind rip_fit.hpp, which takes its parameter structs from the two headers
-# above; its table is closed by tests/fit_variant_cases.py.
-OUT_FIT = os.path.join(HERE, "librip_fit_hip.so")
-FIT_SOURCES = ["rip_fit.hip"]
-FIT_HEADERS = ["rip_fit.hpp", "rip_resize.hpp", "rip_area.hpp"]
+# The companion libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
+# what tests/variant_cases.py closes over; each companion's table is closed by a tests/*_variant_cases.py of its own.
+# librip_hip.so -- every build of it: the default one, the sanitizer build and the A/B variants under variants/ -- links against
+# these files and finds them through its $ORIGIN rpath.  A companion's interface is its headers alone, so a rebuild of it does not
+# ask for a relink of the libraries that use it.  One row each: (library, sources, headers, build directory).
+#   out   the output stage's kernels (rip_set_output_format) and their one launch function; tests/output_variant_cases.py
+#   rsz   the resize stage's kernels (rip_set_output_size); tests/resize_variant_cases.py
+#   area  the resize stage's area interpolation (rip_set_output_interpolation); tests/area_variant_cases.py
+#   fit   the resize stage's kernels that read a window of the image, and the pad kernel of the letterbox (rip_set_output_roi,
+#         rip_set_output_fit); rip_fit.hpp takes its parameter structs from the two headers before it; tests/fit_variant_cases.py
+# rip_resize_dev.hpp is the device code and the launch checks the three libraries of the resize stage share.
+RESIZE_SHARED = ["rip_resize_dev.hpp", "rip_resize.hpp", "rip_area.hpp"]
+COMPANIONS = {
+    "out": (os.path.join(HERE, "librip_out_hip.so"), ["rip_output.hip"], ["rip_output.hpp"], "build_out"),
+    "rsz": (os.path.join(HERE, "librip_rsz_hip.so"), ["rip_resize.hip"], RESIZE_SHARED, "build_rsz"),
+    "area": (os.path.join(HERE, "librip_area_hip.so"), ["rip_area.hip"], RESIZE_SHARED, "build_area"),
+    "fit": (os.path.join(HERE, "librip_fit_hip.so"), ["rip_fit.hip"], ["rip_fit.hpp"] + RESIZE_SHARED, "build_fit"),
+}
+OUT_COMPANION, COMPANION_SOURCES, COMPANION_HEADERS = COMPANIONS["out"][:3]
+OUT_RSZ, RSZ_SOURCES, RSZ_HEADERS = COMPANIONS["rsz"][:3]
+OUT_AREA, AREA_SOURCES, AREA_HEADERS = COMPANIONS["area"][:3]
+OUT_FIT, FIT_SOURCES, FIT_HEADERS = COMPANIONS["fit"][:3]
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -55,7 +53,8 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def _companion_up_to_date(out, sources, headers):
+def _companion_up_to_date(key):
+    out, sources, headers, _ = COMPANIONS[key]
     if not os.path.exists(out):
         return False
     t = os.path.getmtime(out)
@@ -63,31 +62,23 @@ def _companion_up_to_date(out, sources, headers):
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def companion_up_to_date():
-    return _companion_up_to_date(OUT_COMPANION, COMPANION_SOURCES, COMPANION_HEADERS)
-
-
-def rsz_up_to_date():
-    return _companion_up_to_date(OUT_RSZ, RSZ_SOURCES, RSZ_HEADERS)
-
-
-def area_up_to_date():
-    return _companion_up_to_date(OUT_AREA, AREA_SOURCES, AREA_HEADERS)
-
-
-def fit_up_to_date():
-    return _companion_up_to_date(OUT_FIT, FIT_SOURCES, FIT_HEADERS)
+def companions_up_to_date():
+    return all(_companion_up_to_date(key) for key in COMPANIONS)
 
 
 def up_to_date():
-    if not os.path.exists(OUT) or not companion_up_to_date() or not rsz_up_to_date() or not area_up_to_date() or not fit_up_to_date():
+    if not os.path.exists(OUT) or not companions_up_to_date():
         return False
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def _build_companion(out, sources, bdir_name, verbose):
+def _build_companion(key, force=False, verbose=False):
+    """One companion library, next to librip_hip.so."""
+    out, sources, _, bdir_name = COMPANIONS[key]
+    if not force and _companion_up_to_date(key):
+        return out
     bdir = os.path.join(HERE, bdir_name)
     os.makedirs(bdir, exist_ok=True)
     objs = []
@@ -109,34 +100,11 @@ def _build_companion(out, sources, bdir_name, verbose):
     return out
 
 
-def build_companion(force=False, verbose=False):
-    """librip_out_hip.so, next to librip_hip.so.  Its interface is rip_output.hpp alone, so a rebuild of it does not ask for a
-    relink of the libraries that use it."""
-    if not force and companion_up_to_date():
-        return OUT_COMPANION
-    return _build_companion(OUT_COMPANION, COMPANION_SOURCES, "build_out", verbose)
-
-
-def build_rsz(force=False, verbose=False):
-    """librip_rsz_hip.so, next to librip_hip.so; its interface is rip_resize.hpp alone."""
-    if not force and rsz_up_to_date():
-        return OUT_RSZ
-    return _build_companion(OUT_RSZ, RSZ_SOURCES, "build_rsz", verbose)
-
-
-def build_area(force=False, verbose=False):
-    """librip_area_hip.so, next to librip_hip.so; its interface is rip_area.hpp alone."""
-    if not force and area_up_to_date():
-        return OUT_AREA
-    return _build_companion(OUT_AREA, AREA_SOURCES, "build_area", verbose)
-
-
-def build_fit(force=False, verbose=False):
-    """librip_fit_hip.so, next to librip_hip.so; its interface is rip_fit.hpp (with the parameter structs of rip_resize.hpp and
-    rip_area.hpp)."""
-    if not force and fit_up_to_date():
-        return OUT_FIT
-    return _build_companion(OUT_FIT, FIT_SOURCES, "build_fit", verbose)
+# the names the tests and the probes use
+companion_up_to_date, build_companion = functools.partial(_companion_up_to_date, "out"), functools.partial(_build_companion, "out")
+rsz_up_to_date, build_rsz = functools.partial(_companion_up_to_date, "rsz"), functools.partial(_build_companion, "rsz")
+area_up_to_date, build_area = functools.partial(_companion_up_to_date, "area"), functools.partial(_build_companion, "area")
+fit_up_to_date, build_fit = functools.partial(_companion_up_to_date, "fit"), functools.partial(_build_companion, "fit")
 
 
 # --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under
@@ -166,14 +134,12 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
     out=".../variants/x.so"; the default build takes no extra flags beyond $RIP_EXTRA_FLAGS."""
     if asan:
         out, tag = out or ASAN_OUT, tag or "_asan"
-        if not force and os.path.exists(out) and companion_up_to_date() and rsz_up_to_date() and area_up_to_date() and fit_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
+        if not force and os.path.exists(out) and companions_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
             return out
     if out is None and not force and up_to_date():
         return OUT
-    build_companion(verbose=verbose)  # every build of librip_hip.so links against all four; `force` is about the library asked for
-    build_rsz(verbose=verbose)
-    build_area(verbose=verbose)
-    build_fit(verbose=verbose)
+    for key in COMPANIONS:  # every build of librip_hip.so links against all of them; `force` is about the library asked for
+        _build_companion(key, verbose=verbose)
     out = out or OUT
     objs = []
     procs = []
@@ -196,7 +162,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
         if verbose and log.strip():
             print(log)
     # the companions are found next to the library ($ORIGIN) or one directory up (variants/*.so)
-    companion = ["-L" + HERE, "-l:" + os.path.basename(OUT_COMPANION), "-l:" + os.path.basename(OUT_RSZ), "-l:" + os.path.basename(OUT_AREA), "-l:" + os.path.basename(OUT_FIT), "-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    companion = ["-L" + HERE] + ["-l:" + os.path.basename(c[0]) for c in COMPANIONS.values()] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
     cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

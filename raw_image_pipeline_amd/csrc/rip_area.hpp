@@ -10,6 +10,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_resize.hpp"
+
 namespace rip {
 
 // Geometry of the kernel: a workgroup of kAreaBlock lanes (kAreaWaves waves) owns a rectangle of kAreaTileCols x kAreaTileRows
@@ -44,15 +46,9 @@ struct AreaParams {
   const float* yweight;
 };
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so)
-struct AreaLaunchInfo {
-  const char* kernel;  // the instantiation as the demangler prints it, without namespaces
-  unsigned grid_x, grid_y, block;
-};
-
 // Enqueues one area resize of n_frames frames on `stream`.  false -- nothing launched -- for sizes or channel counts outside the
 // limits, an upscale on either axis, the identity, pitches that break the alignment rules above, a `whole` flag that does not match
 // the sizes, or a missing table.
-__attribute__((visibility("default"))) bool launch_area_reduce(const AreaParams& p, hipStream_t stream, AreaLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_area_reduce(const AreaParams& p, hipStream_t stream, ResizeLaunchInfo* info);
 
 }  // namespace rip

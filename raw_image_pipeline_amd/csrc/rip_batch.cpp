@@ -912,6 +912,26 @@ static AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W
           reinterpret_cast<const float*>(d + o_yw), p->rsz_tab_whole, p->rsz_tab_scale};
 }
 
+// The fields ResizeParams and AreaParams (P) have in common: the window of F in `staged` that is read -- its size; its origin goes to
+// the launch -- and the picture's rectangle `to` of F' that is written, for n frames.
+template <typename P>
+P resize_params(const FrameView& staged, const FrameView& to, const Plan& pl, int n) {
+  P r = {};
+  r.src = staged.ptr;
+  r.src_step = staged.step;
+  r.src_frame_stride = staged.frame_stride;
+  r.dst = to.ptr;
+  r.dst_step = to.step;
+  r.dst_frame_stride = to.frame_stride;
+  r.src_rows = pl.win_h;
+  r.src_cols = pl.win_w;
+  r.rows = pl.pic_h;
+  r.cols = pl.pic_w;
+  r.channels = pl.channels;
+  r.n_frames = n;
+  return r;
+}
+
 // run_batch with the resize and the output stage behind it.  With a target size other than F's, or under a format, the chain's
 // last kernel writes the pipeline's image F into the handle's staging buffer; then one launch of the resize (librip_rsz_hip.so, or
 // librip_area_hip.so under the area interpolation; librip_fit_hip.so when it reads a window of F, rip_set_output_roi) writes F' --
@@ -950,26 +970,16 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   to.ptr += (size_t)pl.pic_y * to.step + (size_t)pl.pic_x * pl.channels;
   // a window other than F is read in place by the kernels of librip_fit_hip.so, which take the window's origin; no copy of it is made
   const rip::FitWindow win = {pl.win_x, pl.win_y, pl.out_cols, pl.out_rows};
-  const auto log_fit = [&](bool launched, const rip::FitLaunchInfo& info, const char* what) {
-    if (!launched) throw DeviceError(std::string("internal: ") + what + " refused a layout the frame call had accepted");
+  // every launch below: a refusal is a bug of the frame call's checks; then the launch error, then the launch record
+  const auto launched = [&](bool accepted, const auto& info, const char* what) {
+    if (!accepted) throw DeviceError(std::string("internal: ") + what + " refused a layout the frame call had accepted");
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
     RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
   };
+  rip::ResizeLaunchInfo info = {};
   if (pl.rsz_active && pl.rsz_area) {
-    rip::AreaParams r = {};
-    r.src = staged.ptr;
-    r.src_step = staged.step;
-    r.src_frame_stride = staged.frame_stride;
-    r.dst = to.ptr;
-    r.dst_step = to.step;
-    r.dst_frame_stride = to.frame_stride;
-    r.src_rows = pl.win_h;
-    r.src_cols = pl.win_w;
-    r.rows = pl.pic_h;
-    r.cols = pl.pic_w;
-    r.channels = pl.channels;
-    r.n_frames = n;
+    rip::AreaParams r = resize_params<rip::AreaParams>(staged, to, pl, n);
     r.whole = at.whole;
     r.scale = at.scale;
     r.xfirst = at.xfirst;
@@ -980,45 +990,17 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
     r.ycount = at.ycount;
     r.ywofs = at.ywofs;
     r.yweight = at.yweight;
-    if (!pl.win_is_frame()) {
-      rip::FitLaunchInfo fit_info = {};
-      log_fit(rip::launch_fit_area(r, win, p->stream, &fit_info), fit_info, "the area resize of a window");
-    } else {
-      rip::AreaLaunchInfo info = {};
-      if (!rip::launch_area_reduce(r, p->stream, &info)) throw DeviceError("internal: the area resize refused a layout the frame call had accepted");
-      hipError_t le = hipGetLastError();
-      if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
-      RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
-    }
+    if (!pl.win_is_frame()) launched(rip::launch_fit_area(r, win, p->stream, &info), info, "the area resize of a window");
+    else launched(rip::launch_area_reduce(r, p->stream, &info), info, "the area resize");
   } else if (pl.rsz_active) {
-    rip::ResizeParams r = {};
-    r.src = staged.ptr;
-    r.src_step = staged.step;
-    r.src_frame_stride = staged.frame_stride;
-    r.dst = to.ptr;
-    r.dst_step = to.step;
-    r.dst_frame_stride = to.frame_stride;
-    r.src_rows = pl.win_h;
-    r.src_cols = pl.win_w;
-    r.rows = pl.pic_h;
-    r.cols = pl.pic_w;
-    r.channels = pl.channels;
-    r.n_frames = n;
+    rip::ResizeParams r = resize_params<rip::ResizeParams>(staged, to, pl, n);
     r.area2 = rt.area2;
     r.xofs = rt.xofs;
     r.alpha = rt.alpha;
     r.yofs = rt.yofs;
     r.beta = rt.beta;
-    if (!pl.win_is_frame()) {
-      rip::FitLaunchInfo fit_info = {};
-      log_fit(rip::launch_fit_resize(r, win, p->stream, &fit_info), fit_info, "the resize of a window");
-    } else {
-      rip::ResizeLaunchInfo info = {};
-      if (!rip::launch_resize(r, p->stream, &info)) throw DeviceError("internal: the resize refused a layout the frame call had accepted");
-      hipError_t le = hipGetLastError();
-      if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
-      RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
-    }
+    if (!pl.win_is_frame()) launched(rip::launch_fit_resize(r, win, p->stream, &info), info, "the resize of a window");
+    else launched(rip::launch_resize(r, p->stream, &info), info, "the resize");
   }
   if (pl.rsz_active && !pl.pic_is_delivered()) {  // a letterbox: the bands around the picture get the pad colour
     rip::FitPadParams f = {};
@@ -1034,8 +1016,7 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
     f.channels = pl.channels;
     f.n_frames = n;
     for (int i = 0; i < 4; i++) f.color[i] = pl.pad[i];
-    rip::FitLaunchInfo fit_info = {};
-    log_fit(rip::launch_fit_pad(f, p->stream, &fit_info), fit_info, "the letterbox pad");
+    launched(rip::launch_fit_pad(f, p->stream, &info), info, "the letterbox pad");
   }
   if (pl.out_fmt == rip::OUT_NATIVE) return;
   rip::OutputConvertParams c = {};
@@ -1050,11 +1031,8 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   c.n_frames = n;
   c.format = pl.out_fmt;
   c.table = pl.dl_planar ? p->d_out_tab.ptr : nullptr;
-  rip::OutputLaunchInfo info = {};
-  if (!rip::launch_output_convert(c, p->stream, &info)) throw DeviceError("internal: the output converter refused a layout the frame call had accepted");
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
-  RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
+  rip::OutputLaunchInfo out_info = {};
+  launched(rip::launch_output_convert(c, p->stream, &out_info), out_info, "the output converter");
 }
 
 // setDebug(true): raw_image_pipeline.hpp:143-172 writes the image after EVERY module -- enabled or not -- to

@@ -40,7 +40,18 @@ struct ResizeParams {
   const int16_t* beta;
 };
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so)
+// Where a window lies in F (rip_fit.hpp; the kernels of rip_resize_dev.hpp).  The params of a launch on a window describe the window
+// as the whole-frame launches describe a frame -- src_rows x src_cols is the window's size and the tables are those of that size --
+// while src, src_step and src_frame_stride stay those of F: pixel (u, v) of the window is pixel (x + u, y + v) of F.  frame_cols is
+// C of F: the last dword of a row of F that may be read is the one that holds its last byte.
+struct FitWindow {
+  int x, y;        // >= 0
+  int frame_cols;  // x + src_cols <= frame_cols
+  int frame_rows;  // y + src_rows <= frame_rows
+};
+
+// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so): the one
+// record of every launch function of the resize stage (this header, rip_area.hpp, rip_fit.hpp)
 struct ResizeLaunchInfo {
   const char* kernel;  // the instantiation as the demangler prints it, without namespaces
   unsigned grid_x, grid_y, block;

@@ -340,9 +340,28 @@ def test_facade_sets_gets_and_throws(tmp_path, rip_lib, branch):
 LAYOUTS = ((0, 0, 0), (5, 1, 3), (16, 3, 0))      # (row padding, offset of the base, gap between frames) of the destination
 
 
+# A window that is all of F -- origin (0, 0), F's size -- through the window kernels, which the library never does (it sends such a
+# resize to the whole-frame kernels): the one point at which both settings of the bodies' window switch must give the same bytes.
+# One shape per arithmetic, a few dozen pixels, the picture's width no multiple of a lane's 4 pixels.
+WHOLE_FRAME = {"linear": ("linear", (37, 23), (22, 13)), "mean2": ("linear", (42, 26), (21, 13)), "whole": ("area", (63, 36), (21, 12)),
+               "taps": ("area", (37, 23), (22, 13))}
+
+
+def whole_frame_cases():
+    return [FC.case(cn, size, None, target, "stretch", interp) for _, (interp, size, target) in sorted(WHOLE_FRAME.items()) for cn in (1, 3)]
+
+
 def host_cases():
-    """Every shape of tests/fit_cases.py -- the ones the GPU tests run -- each under one of three destination layouts, two frames."""
-    return [(c._replace(n=2), LAYOUTS[i % 3]) for i, c in enumerate(FC.kernel_cases())]
+    """Every shape of tests/fit_cases.py -- the ones the GPU tests run -- and the whole-frame windows above, each under one of three
+    destination layouts, two frames."""
+    return [(c._replace(n=2), LAYOUTS[i % 3]) for i, c in enumerate(FC.kernel_cases() + whole_frame_cases())]
+
+
+def test_the_whole_frame_cases_take_the_four_paths():
+    for name, (interp, size, target) in WHOLE_FRAME.items():
+        assert FR.rule(size, target, interp) == name
+    for c in whole_frame_cases():
+        assert FC.geometry(c)[:2] == ((0, 0) + c.size, (0, 0) + c.target) and c.target[0] % 4
 
 
 def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, rip_lib):

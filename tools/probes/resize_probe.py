@@ -94,7 +94,7 @@ def linear_launch(lib, rsz, frames, dst, H, W):
 
 
 def area_launch(lib, frames, dst, H, W):
-    launch = getattr(C.CDLL(B.OUT_AREA), "_ZN3rip18launch_area_reduceERKNS_10AreaParamsEP12ihipStream_tPNS_14AreaLaunchInfoE")
+    launch = getattr(C.CDLL(B.OUT_AREA), "_ZN3rip18launch_area_reduceERKNS_10AreaParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
     launch.restype = C.c_bool
     xf, xc, xw = np.zeros(W, np.int32), np.zeros(W, np.int32), np.zeros(C_ + 2 * W, np.float32)
     yf, yc, yw = np.zeros(H, np.int32), np.zeros(H, np.int32), np.zeros(R_ + 2 * H, np.float32)
