@@ -50,8 +50,9 @@ Tunables tunables_from_env() {
 }
 }  // namespace rip
 
+// The body selects the handle's device and does not put the caller's back: the members' destructors run right behind it, so
+// every DevBuf of the handle frees its memory under that device without being named here.
 rip_pipeline::~rip_pipeline() {
-  using rip::api::DevBuf;
   if (device < 0) return;
   (void)hipSetDevice(device);
   for (hipEvent_t e : prof_events) (void)hipEventDestroy(e);
@@ -63,10 +64,6 @@ rip_pipeline::~rip_pipeline() {
   for (auto& sl : ring) sl->release();
   if (ul_stream) (void)hipStreamDestroy(ul_stream);
   if (dl_stream) (void)hipStreamDestroy(dl_stream);
-  for (DevBuf* b : {&d_tabs, &d_vig_image, &d_map, &d_map_ckpt, &d_filter_fft, &d_bias_fft, &d_accum, &d_ccc_state, &d_geom, &d_stats, &d_wb,
-                    &d_hist, &d_work, &d_rowbest, &d_argmax, &d_mid, &d_in, &d_out, &d_tap_deb, &d_tap_col, &d_vig, &d_plan_words,
-                    &d_plan_tiles, &d_plan_border, &d_plan_counters, &d_plan_fp, &d_chain_items, &d_dbg, &d_mht, &d_fmt, &d_out_tab, &d_rsz, &d_rsz_tab})
-    b->release();
 }
 
 namespace rip::api {
@@ -170,7 +167,7 @@ rip_status rip_create(int device, int use_gpu, const char* params_path, const ch
       if ((e[0] != '0' && e[0] != '1') || e[1] != 0) throw rip::YamlError(std::string("RIP_FP_CONTRACT=[") + e + "]: 0 (uncontracted) or 1 (contracted) expected");
       p->fp_contract = e[0] == '1' ? 1 : 0;
     }
-    if (!p->ccc_model_env.empty()) rip::ccc_load_model_file(p->ccc, p->ccc_model_env);
+    if (!p->ccc_model_env.empty()) rip::ccc_load_model_file(p->ccc.model, p->ccc_model_env);
     *out = p;
     return RIP_OK;
   } catch (const std::exception& e) {
@@ -304,9 +301,9 @@ rip_status rip_load_params(rip_pipeline* p, const char* path) {
       for (int i = 0; i < 4; i++) p->m.cc_bias[i] = 0;
       p->m.cc_available = false;
       p->m.und_available = false;
-      p->ccc_state_init = false;
+      p->ccc.state_init = false;
     }
-    p->tabs_dirty = p->vig_dirty = p->ccc_cfg_dirty = p->out_tab_dirty = true;
+    p->tables.dirty = p->vignette.dirty = p->ccc.cfg_dirty = p->out_table.dirty = true;
     und_init(p);  // setBalance / setFovScale re-run init()
   });
 }
@@ -342,16 +339,16 @@ rip_status rip_load_ccc_model(rip_pipeline* p, const char* path) {
   return guarded(p, [&] {
     need(p);
     if (!path) throw InvalidArgument("path is null");
-    if (!rip::ccc_load_model_file(p->ccc, path)) throw rip::YamlError(std::string("cannot read CCC model ") + path);
-    p->ccc_uploaded = false;
+    if (!rip::ccc_load_model_file(p->ccc.model, path)) throw rip::YamlError(std::string("cannot read CCC model ") + path);
+    p->ccc.uploaded = false;
   });
 }
 rip_status rip_set_ccc_model(rip_pipeline* p, int w, int h, const float* filter, const float* bias) {
   return guarded(p, [&] {
     need(p);
     if (!filter || !bias) throw InvalidArgument("null model planes");
-    rip::ccc_build_model(p->ccc, w, h, filter, bias);
-    p->ccc_uploaded = false;
+    rip::ccc_build_model(p->ccc.model, w, h, filter, bias);
+    p->ccc.uploaded = false;
   });
 }
 // ---- setters -----------------------------------------------------------------------------------
@@ -365,8 +362,8 @@ rip_status rip_set_ccc_model(rip_pipeline* p, int w, int h, const float* filter,
 
 RIP_SETTER(rip_set_taps, (rip_pipeline * p, int mask), p->tap_mask = mask & 7)
 RIP_SETTER(rip_set_tap_download, (rip_pipeline * p, int mask), p->tap_download_mask = mask & (RIP_TAP_DEBAYERED | RIP_TAP_COLOR))
-RIP_SETTER(rip_set_ccc_kalman_model, (rip_pipeline * p, double h, double r), p->kf_h = h; p->kf_r = r; p->ccc_cfg_dirty = true)
-RIP_SETTER(rip_reset_white_balance_temporal_consistency, (rip_pipeline * p), if (p->m.wb_method == "ccc") p->ccc_reset_pending = true)  // white_balance.cpp:42-47
+RIP_SETTER(rip_set_ccc_kalman_model, (rip_pipeline * p, double h, double r), p->ccc.kf_h = h; p->ccc.kf_r = r; p->ccc.cfg_dirty = true)
+RIP_SETTER(rip_reset_white_balance_temporal_consistency, (rip_pipeline * p), if (p->m.wb_method == "ccc") p->ccc.reset_pending = true)  // white_balance.cpp:42-47
 RIP_SETTER(rip_set_gpu, (rip_pipeline * p, int v), p->m.use_gpu = v != 0)
 RIP_SETTER(rip_set_debug, (rip_pipeline * p, int v), p->m.debug = v != 0)
 RIP_SETTER(rip_set_debayer, (rip_pipeline * p, int v), p->m.debayer_enabled = v != 0)
@@ -377,11 +374,11 @@ RIP_SETTER(rip_set_debayer_encoding, (rip_pipeline * p, const char* s), if (!s) 
 RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            rip::check_debayer_method(s); p->m.debayer_method = s)
 RIP_SETTER(rip_set_output_format, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
-           (void)rip::output_format_id(s); if (p->m.out_format != s) p->out_tab_dirty = true; p->m.out_format = s)
+           (void)rip::output_format_id(s); if (p->m.out_format != s) p->out_table.dirty = true; p->m.out_format = s)
 RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, const double* mean, const double* sd),
            if (!mean || !sd) throw InvalidArgument("null mean or std");
            rip::check_output_normalization(divisor, mean, sd); p->m.out_divisor = divisor;
-           for (int i = 0; i < 3; i++) { p->m.out_mean[i] = mean[i]; p->m.out_std[i] = sd[i]; } p->out_tab_dirty = true)
+           for (int i = 0; i < 3; i++) { p->m.out_mean[i] = mean[i]; p->m.out_std[i] = sd[i]; } p->out_table.dirty = true)
 RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), rip::check_output_size(width, height); p->m.out_w = width; p->m.out_h = height)
 RIP_SETTER(rip_set_output_interpolation, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            (void)rip::output_interpolation_id(s); p->m.out_interp = s)
@@ -397,7 +394,7 @@ RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v
 RIP_SETTER(rip_set_white_balance_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.wb_method = s)
 RIP_SETTER(rip_set_white_balance_percentile, (rip_pipeline * p, double v), p->m.wb_percentile = v)
 RIP_SETTER(rip_set_white_balance_saturation_threshold, (rip_pipeline * p, double b, double d), p->m.wb_bright_thr = b; p->m.wb_dark_thr = d)
-RIP_SETTER(rip_set_white_balance_temporal_consistency, (rip_pipeline * p, int v), p->m.wb_temporal = v != 0; p->ccc_cfg_dirty = true)
+RIP_SETTER(rip_set_white_balance_temporal_consistency, (rip_pipeline * p, int v), p->m.wb_temporal = v != 0; p->ccc.cfg_dirty = true)
 RIP_SETTER(rip_set_color_calibration, (rip_pipeline * p, int v), p->m.cc_enabled = v != 0)
 RIP_SETTER(rip_set_color_calibration_matrix, (rip_pipeline * p, const double* v, int n),
            if (!v || n != 9) throw InvalidArgument("color calibration matrix needs 9 values");
@@ -405,16 +402,16 @@ RIP_SETTER(rip_set_color_calibration_matrix, (rip_pipeline * p, const double* v,
 RIP_SETTER(rip_set_color_calibration_bias, (rip_pipeline * p, const double* v, int n),
            if (!v || n < 3) throw InvalidArgument("color calibration bias needs 3 values");  // vector::at throws
            for (int i = 0; i < 3; i++) p->m.cc_bias[i] = v[i]; p->m.cc_bias[3] = 0)
-RIP_SETTER(rip_set_gamma_correction, (rip_pipeline * p, int v), p->m.gamma_enabled = v != 0; p->tabs_dirty = true)
+RIP_SETTER(rip_set_gamma_correction, (rip_pipeline * p, int v), p->m.gamma_enabled = v != 0; p->tables.dirty = true)
 RIP_SETTER(rip_set_gamma_correction_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.gamma_method = s)
-RIP_SETTER(rip_set_gamma_correction_k, (rip_pipeline * p, double k), p->m.gamma_k = k; p->tabs_dirty = true)
+RIP_SETTER(rip_set_gamma_correction_k, (rip_pipeline * p, double k), p->m.gamma_k = k; p->tables.dirty = true)
 RIP_SETTER(rip_set_fp_contraction, (rip_pipeline * p, int mode),
            if (mode != 0 && mode != 1) throw InvalidArgument("fp contraction model must be 0 (none) or 1 (fused)");
-           if (mode != p->fp_contract) p->vig_dirty = true;  // the mask plane's k = r^2 a2 + r^4 a4 is one of the contracted expressions
+           if (mode != p->fp_contract) p->vignette.dirty = true;  // the mask plane's k = r^2 a2 + r^4 a4 is one of the contracted expressions
            p->fp_contract = mode)
 RIP_SETTER(rip_set_vignetting_correction, (rip_pipeline * p, int v), p->m.vig_enabled = v != 0)
 RIP_SETTER(rip_set_vignetting_correction_parameters, (rip_pipeline * p, double s, double a2, double a4),
-           p->m.vig_scale = s; p->m.vig_a2 = a2; p->m.vig_a4 = a4; p->vig_dirty = true)
+           p->m.vig_scale = s; p->m.vig_a2 = a2; p->m.vig_a4 = a4; p->vignette.dirty = true)
 RIP_SETTER(rip_set_color_enhancer, (rip_pipeline * p, int v), p->m.ce_enabled = v != 0)
 // cross-wired exactly as color_enhancer.cpp:23-33
 RIP_SETTER(rip_set_color_enhancer_hue_gain, (rip_pipeline * p, double g), p->m.ce_value_gain = g)
@@ -704,8 +701,8 @@ rip_status rip_get_undistortion_maps(rip_pipeline* p, float* map_x, float* map_y
     size_t n = (size_t)p->m.dist_w * p->m.dist_h;
     if (cap < n) throw CapacityError("map buffers too small");
     for (size_t i = 0; i < n; i++) {
-      map_x[i] = p->h_map[2 * i];
-      map_y[i] = p->h_map[2 * i + 1];
+      map_x[i] = p->maps.host[2 * i];
+      map_y[i] = p->maps.host[2 * i + 1];
     }
   });
 }
@@ -806,13 +803,13 @@ rip_status rip_debug_plan_info(rip_pipeline* p, int src_rows, int src_cols, int 
     if (!info) throw InvalidArgument("null info");
     DeviceGuard device_guard(p->device);
     ensure_plan(p, src_rows, src_cols);
-    info[0] = p->plan.tiles_x;
-    info[1] = p->plan.tiles_y;
-    info[2] = p->plan_n_border;
-    info[3] = (int)p->plan.max_lds_bytes;
-    info[4] = p->plan.max_rect_w;
-    info[5] = p->plan.max_rect_h;
-    info[6] = p->plan_on_device ? 1 : 0;
+    info[0] = p->plan.host.tiles_x;
+    info[1] = p->plan.host.tiles_y;
+    info[2] = p->plan.n_border;
+    info[3] = (int)p->plan.host.max_lds_bytes;
+    info[4] = p->plan.host.max_rect_w;
+    info[5] = p->plan.host.max_rect_h;
+    info[6] = p->plan.on_device ? 1 : 0;
     info[7] = rip::kRemapTileW;
     info[8] = rip::kRemapTileH;
   });
@@ -831,12 +828,12 @@ rip_status rip_debug_chain_footprint(rip_pipeline* p, int src_rows, int src_cols
     std::vector<int> lo, hi;
     if (p->device == RIP_DEVICE_NONE) {  // no plan on such a handle: the host compiler's footprint of the host-built maps
       ensure_host_maps(p);
-      rip::compile_remap_footprint(p->h_map.data(), p->m.dist_h, p->m.dist_w, src_rows, src_cols, lo, hi);
+      rip::compile_remap_footprint(p->maps.host.data(), p->m.dist_h, p->m.dist_w, src_rows, src_cols, lo, hi);
     } else {
       DeviceGuard device_guard(p->device);
       ensure_plan(p, src_rows, src_cols);
-      lo = p->plan.fp_lo;
-      hi = p->plan.fp_hi;
+      lo = p->plan.host.fp_lo;
+      hi = p->plan.host.fp_hi;
     }
     std::vector<uint32_t> items;
     rip::chain_footprint_items(lo, hi, src_rows, src_cols, flip_angle, items);

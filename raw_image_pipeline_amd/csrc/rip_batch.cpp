@@ -1,6 +1,6 @@
-// rip_batch.cpp -- everything between a Plan and the kernels: the device-resident constants a batch needs (maps, remap plan,
-// tables, ccc model), the route a batch takes through the kernels of rip_chain/stats/ccc/remap/fused/demosaic.hip, the output
-// stage behind it and the debug dumps.  Everything is enqueued on the handle's stream.
+// rip_batch.cpp -- from a Plan to the kernels: the route a batch takes through the kernels of rip_chain/stats/ccc/remap/fused/
+// demosaic.hip (enqueue_*, plan_route, run_chain, run_batch), the output stage behind it (run_batch_formatted) and the debug
+// dumps.  The device-resident constants a batch needs come from rip_constants.cpp.  Everything is enqueued on the handle's stream.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -8,363 +8,6 @@
 #include "rip_handle.hpp"
 
 namespace rip::api {
-
-// ------------------------------------------------------------------------------------------------
-// undistortion bookkeeping: UndistortionModule::init() (undistortion.cpp:197-238) minus the map
-// generation, which is deferred until a frame (or rip_init_undistortion) needs it.
-// ------------------------------------------------------------------------------------------------
-void und_init(rip_pipeline* p) {
-  rip::Modules& m = p->m;
-  double newK[9];
-  if (rip::is_pinhole_model(m.dist_model)) {
-    // plumb_bob / radtan / rational_polynomial: cv::getOptimalNewCameraMatrix with alpha = balance (not in the reference)
-    double k[8];
-    rip::pinhole_coefficients(m.dist_model, m.dist_D, k);
-    rip::pinhole_estimate_new_camera_matrix(m.dist_K, k, m.dist_w, m.dist_h, m.balance, m.rect_w, m.rect_h, m.fov_scale, newK);
-  } else {
-    rip::fisheye_estimate_new_camera_matrix(m.dist_K, m.dist_D, m.dist_w, m.dist_h, m.dist_R, m.balance, m.rect_w, m.rect_h,
-                                            m.fov_scale, newK);
-  }
-  std::memcpy(m.rect_K, newK, sizeof(newK));
-  for (int i = 0; i < 8; i++) m.rect_D[i] = 0;
-  const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  std::memcpy(m.rect_R, eye, sizeof(eye));
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) m.rect_P[i * 4 + j] = m.rect_K[i * 3 + j];
-  p->map_dirty = true;
-}
-
-// Where the maps are built: on the device for device handles (rip_maps.hip: one thread per map row, FP64, double-double
-// atan -- milliseconds instead of 0.25-0.5 s of host threads per calibration change), on the host for RIP_DEVICE_NONE handles
-// and when RIP_MAPS_ON_HOST is set (A/B and debugging).  Both produce the same floats (tests/test_parity_gpu.py).
-static bool maps_on_device(const rip_pipeline* p) { return p->device != RIP_DEVICE_NONE && !p->maps_on_host; }
-
-void ensure_host_maps(rip_pipeline* p) {
-  if (!p->map_dirty) return;
-  const rip::Modules& m = p->m;
-  if (m.dist_w <= 0 || m.dist_h <= 0) throw AssertError("undistortion: image size is not set");
-  const size_t n = (size_t)m.dist_w * m.dist_h * 2;
-  p->h_map.resize(n);
-  // maps have the *dist* image size even after setNewImageSize (undistortion.cpp:216)
-  const bool pinhole = rip::is_pinhole_model(m.dist_model);  // every other name builds fisheye maps, as the reference does
-  if (maps_on_device(p)) {
-    DeviceGuard device_guard(p->device);
-    LaunchLogScope log_scope(p);
-    rip::UndistortMapParams fp = {};
-    std::memcpy(fp.K, m.dist_K, sizeof(fp.K));
-    fp.pinhole = pinhole ? 1 : 0;
-    if (pinhole)
-      rip::pinhole_coefficients(m.dist_model, m.dist_D, fp.D);
-    else
-      std::memcpy(fp.D, m.dist_D, 4 * sizeof(double));
-    rip::fisheye_inverse_PR(m.rect_K, m.dist_R, fp.iR);
-    fp.w = m.dist_w;
-    fp.h = m.dist_h;
-    p->d_map.reserve(n * sizeof(float));
-    fp.map_xy = p->d_map.as<float>();
-    p->d_map_ckpt.reserve(rip::undistort_ckpt_bytes(fp.w, fp.h));
-    fp.ckpt = p->d_map_ckpt.as<double>();
-    rip::launch_undistort_maps(fp, p->stream);
-    // no host copy yet: the remap-plan compiler runs on the device too; need_host_map() fetches the floats for
-    // rip_get_undistortion_maps or for a plan compiled on the host
-    p->map_dirty = false;
-    p->map_uploaded = true;
-    p->h_map_valid = false;
-    p->plan.valid = false;
-    return;
-  }
-  if (pinhole) {
-    double k[8];
-    rip::pinhole_coefficients(m.dist_model, m.dist_D, k);
-    rip::pinhole_init_undistort_rectify_map(m.dist_K, k, m.dist_R, m.rect_K, m.dist_w, m.dist_h, p->h_map.data());
-  } else {
-    rip::fisheye_init_undistort_rectify_map(m.dist_K, m.dist_D, m.dist_R, m.rect_K, m.dist_w, m.dist_h, p->h_map.data());
-  }
-  p->map_dirty = false;
-  p->map_uploaded = false;
-  p->h_map_valid = true;
-  p->plan.valid = false;
-}
-
-// the maps as floats on the host
-void need_host_map(rip_pipeline* p) {
-  ensure_host_maps(p);
-  if (p->h_map_valid) return;
-  DeviceGuard device_guard(p->device);
-  HIP_CHECK(hipMemcpyAsync(p->h_map.data(), p->d_map.ptr, p->h_map.size() * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-  HIP_CHECK(hipStreamSynchronize(p->stream));
-  p->h_map_valid = true;
-}
-
-static_assert(rip::kRemapOutside == rip::kPlanOutside && rip::kRemapBorder == rip::kPlanBorder, "plan sentinels");
-static_assert(sizeof(rip::RemapTile) == sizeof(rip::RemapTileDesc), "tile descriptor layout");
-
-void ensure_plan(rip_pipeline* p, int src_rows, int src_cols) {
-  ensure_maps(p);
-  LaunchLogScope log_scope(p);
-  const rip::Modules& m = p->m;
-  if (!p->plan.valid || p->plan.src_rows != src_rows || p->plan.src_cols != src_cols || p->plan.drows != m.dist_h ||
-      p->plan.dcols != m.dist_w) {
-    p->plan_on_device = false;
-    p->chain_items_flip = -1;
-    if (maps_on_device(p) && !p->plan_on_host) {
-      // Compile the plan where the maps are (rip_maps.hip remap_plan_kernel: one workgroup per tile; the same words, tile
-      // rectangles and border pixels as rip::compile_remap_plan, the border list in another order): no 8 B/px map read-back,
-      // no 4 B/px plan upload, no host threads -- a calibration change costs the map kernel plus ~0.1 ms.
-      rip::RemapPlan& pl = p->plan;
-      pl = rip::RemapPlan();
-      pl.drows = m.dist_h;
-      pl.dcols = m.dist_w;
-      pl.src_rows = src_rows;
-      pl.src_cols = src_cols;
-      pl.tiles_x = (pl.dcols + rip::kRemapTileW - 1) / rip::kRemapTileW;
-      pl.tiles_y = (pl.drows + rip::kRemapTileH - 1) / rip::kRemapTileH;
-      const size_t ntiles = (size_t)pl.tiles_x * pl.tiles_y;
-      const unsigned border_cap = 1u << 20;  // pixels; more than that (a map that mostly straddles the border) goes to the host
-      p->d_plan_words.reserve(ntiles * rip::kRemapTilePx * sizeof(uint32_t));
-      p->d_plan_tiles.reserve(ntiles * sizeof(rip::RemapTileDesc));
-      p->d_plan_border.reserve((size_t)border_cap * sizeof(uint32_t));
-      p->d_plan_counters.reserve(4 * sizeof(unsigned));
-      HIP_CHECK(hipMemsetAsync(p->d_plan_counters.ptr, 0, 4 * sizeof(unsigned), p->stream));
-      rip::RemapPlanBuildParams bp = {};
-      bp.map_xy = p->d_map.as<float>();
-      bp.drows = pl.drows;
-      bp.dcols = pl.dcols;
-      bp.src_rows = src_rows;
-      bp.src_cols = src_cols;
-      bp.tiles_x = pl.tiles_x;
-      bp.tiles_y = pl.tiles_y;
-      bp.words = p->d_plan_words.as<uint32_t>();
-      bp.tiles = p->d_plan_tiles.as<rip::RemapTileDesc>();
-      bp.border = p->d_plan_border.as<uint32_t>();
-      bp.border_cap = border_cap;
-      bp.counters = p->d_plan_counters.as<unsigned>();
-      rip::launch_remap_plan_build(bp, p->stream);
-      // the footprint of the same quantised taps (rip::compile_remap_footprint's hull): lo starts at 0x7F7F7F7F, hi at 0
-      const int pairs = (src_rows + 1) / 2;
-      p->d_plan_fp.reserve(2 * (size_t)pairs * sizeof(int));
-      HIP_CHECK(hipMemsetAsync(p->d_plan_fp.ptr, 0x7F, (size_t)pairs * sizeof(int), p->stream));
-      HIP_CHECK(hipMemsetAsync(p->d_plan_fp.as<int>() + pairs, 0, (size_t)pairs * sizeof(int), p->stream));
-      rip::RemapFootprintParams fq = {};
-      fq.map_xy = bp.map_xy;
-      fq.drows = pl.drows;
-      fq.dcols = pl.dcols;
-      fq.src_rows = src_rows;
-      fq.src_cols = src_cols;
-      fq.tiles_x = pl.tiles_x;
-      fq.tiles_y = pl.tiles_y;
-      fq.lo = p->d_plan_fp.as<int>();
-      fq.hi = p->d_plan_fp.as<int>() + pairs;
-      rip::launch_remap_footprint(fq, p->stream);
-      pl.fp_lo.resize(pairs);
-      pl.fp_hi.resize(pairs);
-      unsigned counters[4] = {0, 0, 0, 0};
-      HIP_CHECK(hipMemcpyAsync(counters, p->d_plan_counters.ptr, sizeof(counters), hipMemcpyDeviceToHost, p->stream));
-      HIP_CHECK(hipMemcpyAsync(pl.fp_lo.data(), fq.lo, (size_t)pairs * sizeof(int), hipMemcpyDeviceToHost, p->stream));
-      HIP_CHECK(hipMemcpyAsync(pl.fp_hi.data(), fq.hi, (size_t)pairs * sizeof(int), hipMemcpyDeviceToHost, p->stream));
-      HIP_CHECK(hipStreamSynchronize(p->stream));
-      for (int i = 0; i < pairs; i++)
-        if (pl.fp_lo[i] >= pl.fp_hi[i]) pl.fp_lo[i] = INT32_MAX, pl.fp_hi[i] = 0;  // the host compiler's "no tap" form
-      if (counters[0] <= border_cap) {
-        p->plan_n_border = (int)counters[0];
-        pl.max_lds_bytes = counters[1];
-        pl.max_rect_w = (int)counters[2];
-        pl.max_rect_h = (int)counters[3];
-        pl.valid = true;
-        p->plan_on_device = true;
-        p->plan_uploaded = true;
-      }
-    }
-    if (!p->plan_on_device) {
-      need_host_map(p);
-      rip::compile_remap_plan(p->plan, p->h_map.data(), m.dist_h, m.dist_w, src_rows, src_cols);
-      p->plan_n_border = (int)p->plan.border.size();
-      p->plan_uploaded = false;
-    }
-  }
-  if (!p->plan_uploaded) {
-    p->d_plan_words.reserve(p->plan.words.size() * sizeof(uint32_t));
-    p->d_plan_tiles.reserve(p->plan.tiles.size() * sizeof(rip::RemapTile));
-    HIP_CHECK(hipMemcpyAsync(p->d_plan_words.ptr, p->plan.words.data(), p->plan.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                             p->stream));
-    HIP_CHECK(hipMemcpyAsync(p->d_plan_tiles.ptr, p->plan.tiles.data(), p->plan.tiles.size() * sizeof(rip::RemapTile),
-                             hipMemcpyHostToDevice, p->stream));
-    p->d_plan_border.reserve(std::max<size_t>(4, p->plan.border.size() * sizeof(uint32_t)));
-    if (!p->plan.border.empty())
-      HIP_CHECK(hipMemcpyAsync(p->d_plan_border.ptr, p->plan.border.data(), p->plan.border.size() * sizeof(uint32_t),
-                               hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipStreamSynchronize(p->stream));
-    p->plan_uploaded = true;
-  }
-}
-
-// The fast chain kernel's items whose output the remap reads (rip::chain_footprint_items on the current plan's footprint), on
-// the device; uploaded once per (plan, flip).  Returns how many there are, or -1 when the footprint covers more than 95 % of
-// the frame (balance 1, wide fields of view): the dense walk is as good there and needs no table.
-static int ensure_chain_items(rip_pipeline* p, int rows, int cols, int flip_angle) {
-  if (p->chain_items_flip != flip_angle) {
-    std::vector<uint32_t> items;
-    rip::chain_footprint_items(p->plan.fp_lo, p->plan.fp_hi, rows, cols, flip_angle, items);
-    const long long dense = (long long)(rows / 2) * (cols / 4);
-    p->chain_items_n = (long long)items.size() * 20 > dense * 19 ? -1 : (int)items.size();
-    if (p->chain_items_n >= 0) {
-      p->d_chain_items.reserve(std::max<size_t>(4, items.size() * sizeof(uint32_t)));
-      if (!items.empty())
-        HIP_CHECK(hipMemcpyAsync(p->d_chain_items.ptr, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
-      HIP_CHECK(hipStreamSynchronize(p->stream));
-    }
-    p->chain_items_flip = flip_angle;
-  }
-  return p->chain_items_n;
-}
-
-void ensure_maps(rip_pipeline* p) {
-  ensure_host_maps(p);
-  if (p->map_uploaded) return;
-  p->d_map.reserve(p->h_map.size() * sizeof(float));
-  HIP_CHECK(hipMemcpyAsync(p->d_map.ptr, p->h_map.data(), p->h_map.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
-  HIP_CHECK(hipStreamSynchronize(p->stream));
-  p->map_uploaded = true;
-}
-
-static void ensure_tables(rip_pipeline* p) {
-  if (!p->tabs_dirty) return;
-  LaunchLogScope log_scope(p);
-  rip::DevTables& t = p->h_tabs;
-  const rip::ColorTables& c = rip::color_tables();
-  rip::build_gamma_lut(p->m.gamma_k, t.gamma_lut);
-  for (int i = 0; i < 256; i++) t.lin_tab[i] = c.srgb_gamma[p->m.gamma_enabled ? t.gamma_lut[i] : i];
-  std::memcpy(t.cbrt_tab, c.cbrt, sizeof(t.cbrt_tab));
-  for (int i = 0; i < 256; i++) t.yf_tab[i] = (uint32_t)c.lab_to_yf[2 * i] | ((uint32_t)c.lab_to_yf[2 * i + 1] << 16);
-  for (int i = 0; i < 4096; i++) t.inv_gamma[i] = (uint8_t)std::min<int>(255, c.inv_gamma[i]);
-  std::memcpy(t.sdiv, c.sdiv, sizeof(t.sdiv));
-  std::memcpy(t.hdiv, c.hdiv180, sizeof(t.hdiv));
-  std::memcpy(t.lab_fwd, c.fwd, sizeof(t.lab_fwd));
-  std::memcpy(t.lab_inv, c.inv, sizeof(t.lab_inv));
-  for (int ch = 0; ch < 3; ch++) {
-    if (c.inv[ch * 3] < -32768 || c.inv[ch * 3] > 32767 || c.inv[ch * 3 + 1] < -32768 || c.inv[ch * 3 + 1] > 32767)
-      throw std::runtime_error("Lab inverse coefficients do not fit 16 bits");
-    t.lab_inv_pk[ch * 2] = (int32_t)(((uint32_t)c.inv[ch * 3] & 0xffffu) | ((uint32_t)c.inv[ch * 3 + 1] << 16));
-    t.lab_inv_pk[ch * 2 + 1] = c.inv[ch * 3 + 2];
-  }
-  std::vector<float> accum;
-  rip::ccc_build_scalar_tables(t.log_tab, accum, t.exp_neg_tab);
-  rip::fft256_twiddles(t.tw_re, t.tw_im);
-  p->d_tabs.reserve(sizeof(rip::DevTables));
-  HIP_CHECK(hipMemcpyAsync(p->d_tabs.ptr, &t, sizeof(t), hipMemcpyHostToDevice, p->stream));
-  p->d_vig_image.reserve(rip::vig_image_bytes());
-  rip::launch_vig_image(p->d_tabs.as<rip::DevTables>(), p->d_vig_image.as<uint32_t>(), p->stream);
-  if (!p->d_accum.ptr) {
-    p->d_accum.reserve(accum.size() * sizeof(float));
-    HIP_CHECK(hipMemcpyAsync(p->d_accum.ptr, accum.data(), accum.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
-  }
-  HIP_CHECK(hipStreamSynchronize(p->stream));  // host staging buffers go out of scope
-  p->tabs_dirty = false;
-}
-
-static void ensure_vignette(rip_pipeline* p, int rows, int cols) {
-  if (!p->vig_dirty && p->vig_rows == rows && p->vig_cols == cols) return;
-  rip::build_vignette_mask(rows, cols, p->m.vig_scale, p->m.vig_a2, p->m.vig_a4, p->h_vig, p->fp_contract);
-  p->d_vig.reserve(p->h_vig.size() * sizeof(float));
-  HIP_CHECK(hipMemcpyAsync(p->d_vig.ptr, p->h_vig.data(), p->h_vig.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
-  HIP_CHECK(hipStreamSynchronize(p->stream));
-  p->vig_rows = rows;
-  p->vig_cols = cols;
-  p->vig_dirty = false;
-}
-
-static void ensure_ccc(rip_pipeline* p, int rows, int cols) {
-  if (!p->ccc.loaded) {
-    if (!p->ccc_model_env.empty()) {
-      if (!rip::ccc_load_model_file(p->ccc, p->ccc_model_env)) throw InvalidArgument("RIP_CCC_MODEL: cannot read " + p->ccc_model_env);
-      p->ccc_uploaded = false;
-    } else {
-      throw InvalidArgument(
-          "white balance method [ccc] needs a model: call rip_load_ccc_model()/rip_set_ccc_model() or set RIP_CCC_MODEL "
-          "(the reference loads raw_image_pipeline_white_balance/model/default.bin)");
-    }
-  }
-  if (!p->ccc_uploaded) {
-    size_t bytes = 65536 * 2 * sizeof(float);
-    p->d_filter_fft.reserve(bytes);
-    p->d_bias_fft.reserve(bytes);
-    HIP_CHECK(hipMemcpyAsync(p->d_filter_fft.ptr, p->ccc.filter_fft.data(), bytes, hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipMemcpyAsync(p->d_bias_fft.ptr, p->ccc.bias_fft.data(), bytes, hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipStreamSynchronize(p->stream));
-    p->ccc_uploaded = true;
-  }
-  if (!p->ccc_state_init) {
-    rip::CccState s = {};
-    s.first_frame = 1;
-    s.uv_x = s.uv_y = 128;  // uv_pos_ = (height/2, width/2), :178
-    s.st_x = s.st_y = 128.f;
-    s.kf_h = (float)p->kf_h;
-    s.kf_r = (float)p->kf_r;
-    s.temporal = p->m.wb_temporal ? 1 : 0;
-    p->d_ccc_state.reserve(sizeof(s));
-    HIP_CHECK(hipMemcpyAsync(p->d_ccc_state.ptr, &s, sizeof(s), hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipStreamSynchronize(p->stream));
-    p->ccc_state_init = true;
-    p->ccc_reset_pending = false;
-    p->ccc_cfg_dirty = false;
-  }
-  if (p->ccc_reset_pending || p->ccc_cfg_dirty) {
-    // patch individual fields, stream-ordered, keeping the filter state
-    rip::CccState* d = p->d_ccc_state.as<rip::CccState>();
-    if (p->ccc_reset_pending) {
-      static const int one = 1;
-      HIP_CHECK(hipMemcpyAsync(&d->first_frame, &one, sizeof(int), hipMemcpyHostToDevice, p->stream));
-    }
-    float hr[2] = {(float)p->kf_h, (float)p->kf_r};
-    int temporal = p->m.wb_temporal ? 1 : 0;
-    HIP_CHECK(hipMemcpyAsync(&d->kf_h, hr, sizeof(hr), hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipMemcpyAsync(&d->temporal, &temporal, sizeof(int), hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipStreamSynchronize(p->stream));
-    p->ccc_reset_pending = false;
-    p->ccc_cfg_dirty = false;
-  }
-  if (p->geom_rows != rows || p->geom_cols != cols) {
-    // cv::resize(src, small, Size(360,270)) coefficient tables (imgproc/resize.cpp)
-    struct Geom {
-      int xofs[360];
-      short ialpha[720];
-      int yofs[540];
-      short ibeta[540];
-      int area_fast;
-    };
-    static_assert(sizeof(Geom) % 4 == 0, "geom");
-    std::vector<uint8_t> raw(sizeof(Geom));
-    Geom& g = *reinterpret_cast<Geom*>(raw.data());
-    double scale_x = (double)cols / 360, scale_y = (double)rows / 270;
-    int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
-    g.area_fast = (std::fabs(scale_x - isx) < 2.220446049250313e-16 && std::fabs(scale_y - isy) < 2.220446049250313e-16 && isx == 2 && isy == 2) ? 1 : 0;
-    auto sat16 = [](int v) { return (short)std::min(32767, std::max(-32768, v)); };
-    for (int dx = 0; dx < 360; dx++) {
-      float fx = (float)((dx + 0.5) * scale_x - 0.5);
-      int sx = (int)std::floor(fx);
-      fx -= sx;
-      if (sx < 0) { fx = 0; sx = 0; }
-      if (sx >= cols - 1) { fx = 0; sx = cols - 1; }
-      g.xofs[dx] = sx;
-      g.ialpha[2 * dx] = sat16((int)std::lrintf((1.f - fx) * 2048));
-      g.ialpha[2 * dx + 1] = sat16((int)std::lrintf(fx * 2048));
-    }
-    for (int dy = 0; dy < 270; dy++) {
-      float fy = (float)((dy + 0.5) * scale_y - 0.5);
-      int sy = (int)std::floor(fy);
-      fy -= sy;
-      g.ibeta[2 * dy] = sat16((int)std::lrintf((1.f - fy) * 2048));
-      g.ibeta[2 * dy + 1] = sat16((int)std::lrintf(fy * 2048));
-      g.yofs[2 * dy] = std::min(std::max(sy, 0), rows - 1);
-      g.yofs[2 * dy + 1] = std::min(std::max(sy + 1, 0), rows - 1);
-    }
-    p->d_geom.reserve(sizeof(Geom));
-    HIP_CHECK(hipMemcpyAsync(p->d_geom.ptr, raw.data(), sizeof(Geom), hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipStreamSynchronize(p->stream));
-    p->geom_rows = rows;
-    p->geom_cols = cols;
-  }
-}
 
 namespace {
 
@@ -480,25 +123,25 @@ rip::RemapTiledParams remap_params(const rip_pipeline* p, const Plan& pl, ConstF
   rip::RemapParams& r = tp.base;
   set_source(r, src);
   r.channels = pl.channels;
-  r.map_xy = p->d_map.as<float>();
+  r.map_xy = p->maps.dev.as<float>();
   r.dst = dst.ptr + (size_t)f0 * dst.frame_stride;
   r.dst_step = dst.step;
   r.dst_frame_stride = dst.frame_stride;
   r.drows = pl.out_rows;
   r.dcols = pl.out_cols;
   r.n_frames = ng;
-  tp.words = p->d_plan_words.as<uint32_t>();
-  tp.tiles = p->d_plan_tiles.as<rip::RemapTileDesc>();
-  tp.tiles_x = p->plan.tiles_x;
-  tp.tiles_y = p->plan.tiles_y;
-  tp.border_list = p->d_plan_border.as<uint32_t>();
-  tp.n_border = p->plan_n_border;
-  tp.lds_bytes = (unsigned)p->plan.max_lds_bytes;
+  tp.words = p->plan.words.as<uint32_t>();
+  tp.tiles = p->plan.tiles.as<rip::RemapTileDesc>();
+  tp.tiles_x = p->plan.host.tiles_x;
+  tp.tiles_y = p->plan.host.tiles_y;
+  tp.border_list = p->plan.border.as<uint32_t>();
+  tp.n_border = p->plan.n_border;
+  tp.lds_bytes = (unsigned)p->plan.host.max_lds_bytes;
   return tp;
 }
 // DIRECT_MONO: the chain's two operations, done by the ring kernel
 rip::RemapTiledParams mono_ops(const rip_pipeline* p, const Plan& pl, rip::RemapTiledParams tp) {
-  tp.mono_lut = (pl.stage_bits & rip::ST_GAMMA) ? p->d_tabs.as<uint8_t>() + offsetof(rip::DevTables, gamma_lut) : nullptr;
+  tp.mono_lut = (pl.stage_bits & rip::ST_GAMMA) ? p->tables.dev.as<uint8_t>() + offsetof(rip::DevTables, gamma_lut) : nullptr;
   tp.mono_flip180 = pl.flip_angle == 180 ? 1 : 0;
   return tp;
 }
@@ -519,13 +162,13 @@ rip::ChainParams chain_params(const rip_pipeline* p, const Plan& pl, ConstFrameV
   c.stage_bits = pl.stage_bits;
   for (int i = 0; i < 9; i++) c.cc_m[i] = p->m.cc_matrix[i];
   for (int i = 0; i < 3; i++) c.cc_bias[i] = (float)p->m.cc_bias[i];
-  if (pl.stage_bits & rip::ST_VIG) c.vig_mask = p->d_vig.as<float>();
+  if (pl.stage_bits & rip::ST_VIG) c.vig_mask = p->vignette.dev.as<float>();
   // cv::Scalar(hue_gain_, saturation_gain_, value_gain_) on (H,S,V), color_enhancer.cpp:42
   c.hsv_gain[0] = (float)p->m.ce_hue_gain;
   c.hsv_gain[1] = (float)p->m.ce_saturation_gain;
   c.hsv_gain[2] = (float)p->m.ce_value_gain;
-  c.tabs = p->d_tabs.as<rip::DevTables>();
-  c.vig_image = p->d_vig_image.as<uint32_t>();
+  c.tabs = p->tables.dev.as<rip::DevTables>();
+  c.vig_image = p->tables.lds_image.as<uint32_t>();
   c.fp_contract = p->fp_contract;
   return c;
 }
@@ -559,8 +202,8 @@ BatchRoute plan_route(rip_pipeline* p, const Plan& pl, ConstFrameView src, Frame
     // Memory-rate stage sets with neither tap requested: the remap's tiles demosaic and colour their own source rectangles
     // out of the Bayer frames (rip_fused.hip) -- no intermediate image is written, read or even allocated.
     if (rt.tiled && rt.no_tap && pl.src_kind == rip::SRC_BAYER &&
-        rip::launch_remap_fused(remap_params(p, pl, src, dst, 0, n), chain_params(p, pl, src, p->d_wb.as<rip::FrameWb>(), n), p->plan.max_rect_w,
-                                p->plan.max_rect_h, p->tn, p->stream, /*dry_run=*/true))
+        rip::launch_remap_fused(remap_params(p, pl, src, dst, 0, n), chain_params(p, pl, src, p->d_wb.as<rip::FrameWb>(), n), p->plan.host.max_rect_w,
+                                p->plan.host.max_rect_h, p->tn, p->stream, /*dry_run=*/true))
       rt.remap = BatchRoute::FUSED_BAYER;
     // bgr8 / mono8 frames with nothing to do before the undistortion (no flip, no white balance, no stage, no tap): the
     // chain would be a copy -- the remap gathers from the caller's frames as they lie
@@ -588,7 +231,7 @@ BatchRoute plan_route(rip_pipeline* p, const Plan& pl, ConstFrameView src, Frame
   const int rows = src.rows, cols = src.cols;
   if (rt.tiled && rt.remap == BatchRoute::AFTER_CHAIN && rt.no_tap && p->tn.chain_footprint && pl.src_kind == rip::SRC_BAYER && pl.channels == 3 &&
       (pl.flip_angle == 0 || pl.flip_angle == 180) && rows % 2 == 0 && cols % 4 == 0 && rows / 2 <= 65535 && cols / 4 <= 65535 &&
-      rows == pl.mid_rows && cols == pl.mid_cols && p->plan.fp_lo.size() == (size_t)(rows + 1) / 2)
+      rows == pl.mid_rows && cols == pl.mid_cols && p->plan.host.fp_lo.size() == (size_t)(rows + 1) / 2)
     rt.chain_items = ensure_chain_items(p, rows, cols, pl.flip_angle);
   if (pl.stage_bits & rip::ST_VIG) ensure_vignette(p, pl.mid_rows, pl.mid_cols);
   // Frame groups (tunable overlap_groups > 1; OFF by default): with the batch cut into G groups of frames, remap(g) runs on the
@@ -622,7 +265,7 @@ void enqueue_wb_estimate(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, 
   if (wb_from_sums(pl)) {
     rip::FrameStats* stats_g = p->d_stats.as<rip::FrameStats>() + f0;
     unsigned* hist_g = pl.wb_mode == rip::WB_SIMPLE ? p->d_hist.as<unsigned>() + (size_t)f0 * 768 : nullptr;
-    if (hist_g) p->hist_clean_bytes = 0;  // the same buffer serves SimpleWB's histograms
+    if (hist_g) p->d_hist.clean_bytes = 0;  // the same buffer serves SimpleWB's histograms
     // grey-world / pca: the statistics kernel itself finishes a frame (gains written by the workgroup that ends last) and
     // hands its FrameStats back zeroed, so neither a memset nor a finalisation launch separates the batches -- two
     // dependent launches less on the single-frame path.  The records are cleared here only when they are not known to be
@@ -630,7 +273,7 @@ void enqueue_wb_estimate(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, 
     const bool fused_finalize = pl.wb_mode != rip::WB_SIMPLE;
     const size_t stats_bytes = sizeof(rip::FrameStats) * (size_t)n;
     if (!fused_finalize || stats_clean_before < stats_bytes) HIP_CHECK(hipMemsetAsync(stats_g, 0, sizeof(rip::FrameStats) * (size_t)ng, front));
-    p->stats_clean_bytes = 0;  // until this batch has been enqueued completely
+    p->d_stats.clean_bytes = 0;  // until this batch has been enqueued completely
     if (hist_g) HIP_CHECK(hipMemsetAsync(hist_g, 0, (size_t)ng * 768 * sizeof(unsigned), front));
     rip::StatsParams sp = {};
     set_source(sp, src);
@@ -649,7 +292,7 @@ void enqueue_wb_estimate(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, 
     }
     // SimpleWB::setP(clipping_percentile_) (white_balance.cpp:55); total = pixels per channel plane
     if (!fused_finalize)
-      rip::launch_wb_finalize(pl.wb_mode, sp.stats, nullptr, nullptr, p->d_tabs.as<rip::DevTables>(), wb_g, ng, front, sp.hist3,
+      rip::launch_wb_finalize(pl.wb_mode, sp.stats, nullptr, nullptr, p->tables.dev.as<rip::DevTables>(), wb_g, ng, front, sp.hist3,
                               (float)p->m.wb_percentile, src.rows * src.cols);
   } else if (pl.wb_mode == rip::WB_FLOAT) {
     rip::CccParams cp = {};  // the launcher zeroes the histogram when its kernel accumulates in HBM
@@ -661,27 +304,27 @@ void enqueue_wb_estimate(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, 
     cp.drows = pl.mid_rows;
     cp.dcols = pl.mid_cols;
     cp.n_frames = ng;
-    const uint8_t* gm = p->d_geom.as<uint8_t>();
-    cp.geom.xofs = reinterpret_cast<const int*>(gm);
-    cp.geom.ialpha = reinterpret_cast<const short*>(gm + 360 * 4);
-    cp.geom.yofs = reinterpret_cast<const int*>(gm + 360 * 4 + 720 * 2);
-    cp.geom.ibeta = reinterpret_cast<const short*>(gm + 360 * 4 + 720 * 2 + 540 * 4);
-    cp.geom.area_fast = ((double)pl.mid_cols / 360 == 2.0 && (double)pl.mid_rows / 270 == 2.0) ? 1 : 0;
+    const uint8_t* gm = p->ccc.geom.as<uint8_t>();
+    cp.geom.xofs = reinterpret_cast<const int*>(gm + CccGeomLayout::xofs);
+    cp.geom.ialpha = reinterpret_cast<const short*>(gm + CccGeomLayout::ialpha);
+    cp.geom.yofs = reinterpret_cast<const int*>(gm + CccGeomLayout::yofs);
+    cp.geom.ibeta = reinterpret_cast<const short*>(gm + CccGeomLayout::ibeta);
+    cp.geom.area_fast = CccGeomLayout::area_fast(pl.mid_rows, pl.mid_cols) ? 1 : 0;
     // setSaturationThreshold(float, float): thresholds are held as float (:437-440); 255 * thr in float
     cp.upper = 255 * (float)p->m.wb_bright_thr;
     cp.lower = 255 * (float)p->m.wb_dark_thr;
     cp.hist_split = rip::ccc_hist_split(n);  // of the whole batch: what d_hist was sized for
     cp.hist_counts = p->d_hist.as<unsigned>() + (size_t)f0 * cp.hist_split * 65536;
-    cp.accum_tab = p->d_accum.as<float>();
+    cp.accum_tab = p->tables.ccc_accum.as<float>();
     cp.work = p->d_work.as<float>() + (size_t)f0 * 65536 * 2;
-    cp.filter_fft = p->d_filter_fft.as<float>();
-    cp.bias_fft = p->d_bias_fft.as<float>();
+    cp.filter_fft = p->ccc.filter_fft.as<float>();
+    cp.bias_fft = p->ccc.bias_fft.as<float>();
     cp.row_best = p->d_rowbest.as<float>() + (size_t)f0 * 256 * 2;
     cp.argmax = p->d_argmax.as<int>() + (size_t)f0 * 2;
-    cp.tabs = p->d_tabs.as<rip::DevTables>();
+    cp.tabs = p->tables.dev.as<rip::DevTables>();
     const size_t hist_bytes = (size_t)ng * 65536 * sizeof(unsigned);  // what the global-atomic kernel accumulates into
-    cp.hist_is_clean = (rt.groups == 1 && p->hist_clean_ptr == p->d_hist.ptr && p->hist_clean_cap == p->d_hist.cap && p->hist_clean_bytes >= hist_bytes) ? 1 : 0;
-    p->hist_clean_bytes = 0;  // until the estimator has been enqueued completely
+    cp.hist_is_clean = (rt.groups == 1 && p->d_hist.clean_bytes >= hist_bytes) ? 1 : 0;
+    p->d_hist.clean_bytes = 0;  // until the estimator has been enqueued completely
     bool estimated;
     int left_clean = 0;
     {
@@ -690,13 +333,9 @@ void enqueue_wb_estimate(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, 
     }
     // no histogram, no estimate: fail before the finalisation advances the persistent Kalman state on stale data
     if (!estimated) throw DeviceError("ccc white balance: a kernel of the estimator could not be launched");
-    if (left_clean && rt.groups == 1) {
-      p->hist_clean_ptr = p->d_hist.ptr;
-      p->hist_clean_cap = p->d_hist.cap;
-      p->hist_clean_bytes = hist_bytes;
-    }
+    if (left_clean && rt.groups == 1) p->d_hist.clean_bytes = hist_bytes;
     const bool inline_argmax = rip::ccc_argmax_in_finalize(ng);
-    rip::launch_wb_finalize(rip::WB_FLOAT, nullptr, cp.argmax, p->d_ccc_state.as<rip::CccState>(), cp.tabs, wb_g, ng, front, nullptr, 0.f, 0,
+    rip::launch_wb_finalize(rip::WB_FLOAT, nullptr, cp.argmax, p->ccc.state.as<rip::CccState>(), cp.tabs, wb_g, ng, front, nullptr, 0.f, 0,
                             inline_argmax ? cp.row_best : nullptr, inline_argmax ? cp.argmax : nullptr);
   }
 }
@@ -706,7 +345,7 @@ void enqueue_fused_remap(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   ProfScope ps(p, RIP_KERNEL_REMAP, p->stream);
   rip::ChainParams fc = chain_params(p, pl, src, p->d_wb.as<rip::FrameWb>() + f0, ng);
   fc.dst_streaming = (n >= 8 && p->tn.chain_nt != 0) ? 1 : 0;  // the kernel's output is the batch's final image: non-temporal stores for batches
-  if (!rip::launch_remap_fused(remap_params(p, pl, src, dst, f0, ng), fc, p->plan.max_rect_w, p->plan.max_rect_h, p->tn, p->stream, /*dry_run=*/false))
+  if (!rip::launch_remap_fused(remap_params(p, pl, src, dst, f0, ng), fc, p->plan.host.max_rect_w, p->plan.host.max_rect_h, p->tn, p->stream, /*dry_run=*/false))
     throw DeviceError("internal: the fused remap refused a geometry it had accepted");
 }
 
@@ -727,7 +366,7 @@ void enqueue_chain(rip_pipeline* p, const Plan& pl, const BatchRoute& rt, ConstF
   c.tap_frame_stride = tap_frame;
   c.deal = pl.remap ? -1 : 0;  // hint for launch_chain: the remap gathers from this image next (Tunables::chain_deal)
   if (rt.chain_items >= 0 && rip::chain_uses_fast_path(c)) {
-    c.item_list = p->d_chain_items.as<uint32_t>();
+    c.item_list = p->plan.items.as<uint32_t>();
     c.n_list_items = rt.chain_items;
   }
   p->last_chain_walked = c.item_list ? rt.chain_items : (src.rows / 2) * (src.cols / 4);
@@ -764,7 +403,7 @@ void enqueue_remap(rip_pipeline* p, const BatchRoute& rt, const rip::RemapTiledP
 void run_chain(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb) {
   ensure_tables(p);
   const BatchRoute rt = plan_route(p, pl, src, dst, taps, n, reuse_wb);
-  const size_t stats_clean_before = (p->stats_clean_ptr == p->d_stats.ptr && p->stats_clean_cap == p->d_stats.cap) ? p->stats_clean_bytes : 0;
+  const size_t stats_clean_before = p->d_stats.clean_bytes;  // behind plan_route's reserve: 0 when that grew the buffer
   const hipStream_t front = p->stream, back = rt.back;
   const int groups = rt.groups;
   // Whatever was enqueued on the internal stream is joined into the caller's stream when this function is left -- also by
@@ -805,11 +444,8 @@ void run_chain(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView ds
   p->last_batch_frames = n;
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
-  if (wb_from_sums(pl) && !reuse_wb && pl.wb_mode != rip::WB_SIMPLE) {  // every statistics launch went out: its records come back zeroed
-    p->stats_clean_ptr = p->d_stats.ptr;
-    p->stats_clean_cap = p->d_stats.cap;
-    p->stats_clean_bytes = std::max(stats_clean_before, sizeof(rip::FrameStats) * (size_t)n);
-  }
+  if (wb_from_sums(pl) && !reuse_wb && pl.wb_mode != rip::WB_SIMPLE)  // every statistics launch went out: its records come back zeroed
+    p->d_stats.clean_bytes = std::max(stats_clean_before, sizeof(rip::FrameStats) * (size_t)n);
 }
 
 }  // namespace
@@ -831,86 +467,6 @@ void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView ds
 
 // pitch of the staging image in front of the resize and the converter: every source row starts 16-byte aligned
 size_t fmt_pitch(const Plan& pl) { return ((size_t)pl.out_cols * pl.channels + 15) & ~(size_t)15; }
-
-// The planar formats' table on the device, rebuilt on the host (rip::build_output_table) when the format or the normalisation
-// has changed since the last frame
-static void ensure_output_table(rip_pipeline* p, int fmt) {
-  if (!p->out_tab_dirty) return;
-  const size_t bytes = 768 * (size_t)rip::output_format_elem_bytes(fmt);
-  p->h_out_tab.resize(bytes);
-  rip::build_output_table(fmt, p->m.out_divisor, p->m.out_mean, p->m.out_std, p->h_out_tab.data());
-  p->d_out_tab.reserve(768 * 4);
-  HIP_CHECK(hipMemcpyAsync(p->d_out_tab.ptr, p->h_out_tab.data(), bytes, hipMemcpyHostToDevice, p->stream));
-  HIP_CHECK(hipStreamSynchronize(p->stream));
-  p->out_tab_dirty = false;
-}
-
-// The tables of the resize stage on the device, rebuilt on the host (rip::build_resize_tables) when the sizes they were built for
-// change.  One buffer: xofs, alpha (both padded to whole lanes), yofs, beta -- every part starts 16-byte aligned.
-struct ResizeTables {
-  const int32_t* xofs;
-  const int16_t* alpha;
-  const int32_t* yofs;
-  const int16_t* beta;
-  int area2;
-};
-// The upload goes through the handle's pageable copy and waits for the stream, like the other ensure_* functions: a handle that
-// alternates between targets pays that wait on every change (one table set is kept, not one per target).
-static ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, int W) {
-  const size_t wp = rip::resize_table_cols(W), hp = ((size_t)H + 3) & ~(size_t)3;
-  const size_t o_alpha = wp * 4, o_yofs = o_alpha + wp * 4, o_beta = o_yofs + hp * 8, bytes = o_beta + hp * 4;
-  const int key[5] = {R, C, H, W, 0};  // 0: the linear tables (the area interpolation's share the buffer)
-  if (std::memcmp(key, p->rsz_tab_key, sizeof(key)) != 0 || !p->d_rsz_tab.ptr) {
-    p->h_rsz_tab.assign(bytes, 0);
-    uint8_t* h = p->h_rsz_tab.data();
-    rip::build_resize_tables(R, C, H, W, reinterpret_cast<int32_t*>(h), reinterpret_cast<int16_t*>(h + o_alpha), reinterpret_cast<int32_t*>(h + o_yofs),
-                             reinterpret_cast<int16_t*>(h + o_beta), &p->rsz_tab_area2);
-    p->d_rsz_tab.reserve(bytes);
-    HIP_CHECK(hipMemcpyAsync(p->d_rsz_tab.ptr, h, bytes, hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipStreamSynchronize(p->stream));
-    std::memcpy(p->rsz_tab_key, key, sizeof(key));
-  }
-  const uint8_t* d = p->d_rsz_tab.as<uint8_t>();
-  return {reinterpret_cast<const int32_t*>(d), reinterpret_cast<const int16_t*>(d + o_alpha), reinterpret_cast<const int32_t*>(d + o_yofs),
-          reinterpret_cast<const int16_t*>(d + o_beta), p->rsz_tab_area2};
-}
-
-// The tables of the area interpolation (rip::build_resize_area_tables) in the same buffer and under the same key, told apart by the
-// key's last entry: one table set is kept per handle, whichever filter built it.  Parts, all of 4-byte entries: xfirst, xcount, xwofs
-// [W], yfirst, ycount, ywofs [H], xweight [C + 2 W], yweight [R + 2 H]; wofs is the running sum of count.
-struct AreaTables {
-  const int32_t *xfirst, *xcount, *xwofs, *yfirst, *ycount, *ywofs;
-  const float *xweight, *yweight;
-  int whole;
-  float scale;
-};
-static AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W) {
-  const size_t o_y = (size_t)W * 3, o_xw = o_y + (size_t)H * 3, o_yw = o_xw + (size_t)C + 2 * (size_t)W, words = o_yw + (size_t)R + 2 * (size_t)H;
-  const int key[5] = {R, C, H, W, 1};
-  if (std::memcmp(key, p->rsz_tab_key, sizeof(key)) != 0 || !p->d_rsz_tab.ptr) {
-    p->h_rsz_tab.assign(words * 4, 0);
-    int32_t* h = reinterpret_cast<int32_t*>(p->h_rsz_tab.data());
-    rip::build_resize_area_tables(R, C, H, W, h, h + W, reinterpret_cast<float*>(h + o_xw), h + o_y, h + o_y + H, reinterpret_cast<float*>(h + o_yw),
-                                  &p->rsz_tab_whole, &p->rsz_tab_scale);
-    for (int axis = 0; axis < 2; axis++) {
-      const int d = axis ? H : W;
-      const int32_t* count = h + (axis ? o_y : 0) + d;
-      int32_t* wofs = h + (axis ? o_y : 0) + 2 * (size_t)d;
-      int32_t run = 0;
-      for (int i = 0; i < d; i++) {
-        wofs[i] = run;
-        run += count[i];
-      }
-    }
-    p->d_rsz_tab.reserve(words * 4);
-    HIP_CHECK(hipMemcpyAsync(p->d_rsz_tab.ptr, h, words * 4, hipMemcpyHostToDevice, p->stream));
-    HIP_CHECK(hipStreamSynchronize(p->stream));
-    std::memcpy(p->rsz_tab_key, key, sizeof(key));
-  }
-  const int32_t* d = p->d_rsz_tab.as<int32_t>();
-  return {d, d + W, d + 2 * (size_t)W, d + o_y, d + o_y + H, d + o_y + 2 * (size_t)H, reinterpret_cast<const float*>(d + o_xw),
-          reinterpret_cast<const float*>(d + o_yw), p->rsz_tab_whole, p->rsz_tab_scale};
-}
 
 // The fields ResizeParams and AreaParams (P) have in common: the window of F in `staged` that is read -- its size; its origin goes to
 // the launch -- and the picture's rectangle `to` of F' that is written, for n frames.
@@ -1030,7 +586,7 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   c.cols = pl.dl_cols;
   c.n_frames = n;
   c.format = pl.out_fmt;
-  c.table = pl.dl_planar ? p->d_out_tab.ptr : nullptr;
+  c.table = pl.dl_planar ? p->out_table.dev.ptr : nullptr;
   rip::OutputLaunchInfo out_info = {};
   launched(rip::launch_output_convert(c, p->stream, &out_info), out_info, "the output converter");
 }

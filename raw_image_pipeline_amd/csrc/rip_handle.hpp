@@ -1,6 +1,7 @@
 // rip_handle.hpp -- internal to librip_hip.so (not installed): the handle behind include/rip.h and what the host units
-// share.  rip_plan.cpp turns a frame's geometry and encoding into a Plan, rip_batch.cpp enqueues the kernels of a batch,
-// rip_ring.cpp holds the host-frame calls and their ring, rip_api.cpp the rest of the C ABI.
+// share.  rip_plan.cpp turns a frame's geometry and encoding into a Plan, rip_constants.cpp keeps the device-resident constants
+// current, rip_batch.cpp enqueues the kernels of a batch, rip_ring.cpp holds the host-frame calls and their ring, rip_api.cpp the
+// rest of the C ABI.
 #pragma once
 #include "../../include/rip.h"
 
@@ -50,11 +51,13 @@ struct CapacityError : std::runtime_error {
                         ":" + std::to_string(__LINE__) + ")");                                           \
   } while (0)
 
-// Grow-only device buffer; frees its memory when it goes out of scope (on the device that is current then: handles
-// release theirs explicitly under their own device in ~rip_pipeline)
+// Grow-only device buffer; frees its memory when it goes out of scope (on the device that is current then: ~rip_pipeline
+// selects the handle's device before its members go)
 struct DevBuf {
   void* ptr = nullptr;
   size_t cap = 0;
+  // the leading bytes known to be zero, for the owners that track it (d_stats, d_hist); a new allocation knows nothing
+  size_t clean_bytes = 0;
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
@@ -64,6 +67,7 @@ struct DevBuf {
     if (ptr) HIP_CHECK(hipFree(ptr));
     ptr = nullptr;
     cap = 0;
+    clean_bytes = 0;
     size_t want = bytes + bytes / 8;
     HIP_CHECK(hipMalloc(&ptr, want));
     cap = want;
@@ -76,6 +80,7 @@ struct DevBuf {
     if (ptr) (void)hipFree(ptr);
     ptr = nullptr;
     cap = 0;
+    clean_bytes = 0;
   }
   template <typename T>
   T* as() const {
@@ -204,6 +209,80 @@ struct RingSlot {
   void release();  // rip_ring.cpp
 };
 
+// ---- the constants a handle keeps on the device (rip_constants.cpp): each with its host copy, its device buffers and whatever says
+// whether those are current, side by side ----
+// undistortion maps (interleaved float2), built lazily
+struct MapConst {
+  std::vector<float> host;
+  DevBuf dev, ckpt;  // ckpt: scratch of the map kernels (row accumulators at every 32nd column)
+  bool dirty = true, uploaded = false;
+  bool host_valid = false;  // device-built maps are copied to the host only when something on the host asks for them
+};
+// compiled remap plan (tiled LDS gather), rebuilt when the maps or the source geometry change
+struct PlanConst {
+  rip::RemapPlan host;
+  DevBuf words, tiles, border, counters;
+  DevBuf fp;  // the device compiler's footprint (lo, hi per source row pair), read back into host.fp_lo / fp_hi
+  bool uploaded = false;
+  bool on_device = false;  // compiled by remap_plan_kernel: host.words / tiles / border stay empty
+  int n_border = 0;
+  // the fast chain kernel's items inside the plan's footprint (rip::chain_footprint_items), uploaded once per (plan, flip)
+  DevBuf items;
+  int items_flip = -1;  // -1: not built for the current plan
+  int items_n = 0;
+};
+// colour tables
+struct TableConst {
+  rip::DevTables host;
+  DevBuf dev;
+  DevBuf lds_image;  // the fused chain's LDS tables as one image (rip::launch_vig_image)
+  DevBuf ccc_accum;  // the ccc estimator's accumulator table (rip::ccc_build_scalar_tables): never changes, uploaded once
+  bool dirty = true;
+};
+// vignetting mask plane per geometry (float, rows x cols)
+struct VignetteConst {
+  std::vector<float> host;
+  DevBuf dev;
+  int rows = -1, cols = -1;
+  bool dirty = true;
+};
+// ccc: model spectra, filter state and the estimator's resize geometry
+struct CccConst {
+  rip::CccModel model;
+  DevBuf filter_fft, bias_fft, state;
+  bool uploaded = false, state_init = false, reset_pending = false, cfg_dirty = true;
+  double kf_h = 0.0, kf_r = 1.0;
+  DevBuf geom;  // CccGeomLayout, for frames of geom_rows x geom_cols
+  int geom_rows = -1, geom_cols = -1;
+};
+// The ccc estimator's cv::resize(frame, Size(360, 270)) tables (rip::fill_resize_tables) in CccConst::geom: byte offsets of the parts
+struct CccGeomLayout {
+  static constexpr int W = 360, H = 270;
+  static constexpr size_t xofs = 0;                      // int32 [W]
+  static constexpr size_t ialpha = xofs + W * 4;         // int16 [2 W]
+  static constexpr size_t yofs = ialpha + 2 * W * 2;     // int32 [2 H]
+  static constexpr size_t ibeta = yofs + 2 * H * 4;      // int16 [2 H]
+  static constexpr size_t bytes = ibeta + 2 * H * 2;
+  // cv::resize's switch to the 2 x 2 mean, which the kernel takes by value (CccParams::geom.area_fast)
+  static bool area_fast(int rows, int cols) { return rows == 2 * H && cols == 2 * W; }
+};
+// output stage (rip_set_output_format): the planar formats' 3 x 256 table, rebuilt and uploaded when the format or the normalisation changes
+struct OutputTableConst {
+  std::vector<uint8_t> host;
+  DevBuf dev;
+  bool dirty = true;
+};
+// resize stage (rip_set_output_size): the tables of rip::build_resize_tables or, under the area interpolation,
+// rip::build_resize_area_tables, rebuilt and uploaded when the (R, C, H, W, kind of table) they were built for changes
+struct ResizeTableConst {
+  std::vector<uint8_t> host;
+  DevBuf dev;
+  int key[5] = {0, 0, 0, 0, 0};
+  int area2 = 0;  // build_resize_tables' flag for that key: the 2 x 2 mean replaces the tables
+  int whole = 0;  // build_resize_area_tables' flag and scale for that key: whole factors, no table is read
+  float scale = 0.f;
+};
+
 }  // namespace rip::api
 
 struct rip_pipeline {
@@ -222,64 +301,25 @@ struct rip_pipeline {
   int fp_contract = 0;        // rip_set_fp_contraction / RIP_FP_CONTRACT: contraction model of the float stages (0 none, 1 fused)
 
   // constants on the device
-  rip::DevTables h_tabs;
-  rip::api::DevBuf d_tabs, d_vig_image;  // d_vig_image: the fused chain's LDS tables as one image (rip::launch_vig_image)
-  bool tabs_dirty = true;
-  // undistortion maps (interleaved float2), built lazily
-  std::vector<float> h_map;
-  rip::api::DevBuf d_map, d_map_ckpt;  // d_map_ckpt: scratch of the map kernels (row accumulators at every 32nd column)
-  bool map_dirty = true, map_uploaded = false;
-  bool h_map_valid = false;  // device-built maps are copied to the host only when something on the host asks for them
-  // vignetting mask plane per geometry (float, rows x cols)
-  std::vector<float> h_vig;
-  rip::api::DevBuf d_vig;
-  int vig_rows = -1, vig_cols = -1;
-  bool vig_dirty = true;
-  // ccc
-  rip::CccModel ccc;
-  rip::api::DevBuf d_filter_fft, d_bias_fft, d_accum, d_ccc_state, d_geom;
-  bool ccc_uploaded = false, ccc_state_init = false, ccc_reset_pending = false, ccc_cfg_dirty = true;
-  double kf_h = 0.0, kf_r = 1.0;
-  int geom_rows = -1, geom_cols = -1;
-  // per-batch scratch
+  rip::api::MapConst maps;
+  rip::api::PlanConst plan;
+  rip::api::TableConst tables;
+  rip::api::VignetteConst vignette;
+  rip::api::CccConst ccc;
+  rip::api::OutputTableConst out_table;
+  rip::api::ResizeTableConst rsz_tables;
+  // per-batch scratch.  d_stats.clean_bytes: the prefix known to hold zeroed FrameStats records (the grey-world / pca statistics
+  // kernels clean up after themselves).  d_hist.clean_bytes: the leading bytes known to be zero -- the ccc estimator's global-atomic
+  // histogram (small batches) hands its counters back zeroed, so a stream of single frames pays for one memset, not one per frame
   rip::api::DevBuf d_stats, d_wb, d_hist, d_work, d_rowbest, d_argmax, d_mid;
   rip::api::DevBuf d_mht;  // the Malvar-He-Cutler image of a batch when no DEBAYERED tap holds it (run_batch)
-  // output stage (rip_set_output_format): the pipeline's final image of a batch slice in front of the converter (rows padded to
-  // 16 bytes), and the planar formats' 3 x 256 table, rebuilt and uploaded when the format or the normalisation changes
-  rip::api::DevBuf d_fmt, d_out_tab;
-  std::vector<uint8_t> h_out_tab;
-  bool out_tab_dirty = true;
-  // resize stage (rip_set_output_size): the resized image of a batch slice in front of the converter (rows padded to 16 bytes; only
-  // under a format) and the tables of rip::build_resize_tables or, under the area interpolation, rip::build_resize_area_tables,
-  // rebuilt and uploaded when the (R, C, H, W, kind of table) they were built for changes
-  rip::api::DevBuf d_rsz, d_rsz_tab;
-  std::vector<uint8_t> h_rsz_tab;
-  int rsz_tab_key[5] = {0, 0, 0, 0, 0};
-  int rsz_tab_area2 = 0;  // build_resize_tables' flag for that key: the 2 x 2 mean replaces the tables
-  int rsz_tab_whole = 0;  // build_resize_area_tables' flag and scale for that key: whole factors, no table is read
-  float rsz_tab_scale = 0.f;
-  // compiled remap plan (tiled LDS gather), rebuilt when the maps or the source geometry change
-  rip::RemapPlan plan;
-  rip::api::DevBuf d_plan_words, d_plan_tiles, d_plan_border, d_plan_counters;
-  bool plan_uploaded = false;
-  bool plan_on_device = false;  // compiled by remap_plan_kernel: plan.words / tiles / border stay empty on the host
-  int plan_n_border = 0;
-  rip::api::DevBuf d_plan_fp;  // the device compiler's footprint (lo, hi per source row pair), read back into plan.fp_lo / fp_hi
-  // the fast chain kernel's items inside the plan's footprint (rip::chain_footprint_items), uploaded once per (plan, flip)
-  rip::api::DevBuf d_chain_items;
-  int chain_items_flip = -1;  // -1: not built for the current plan
-  int chain_items_n = 0;
+  // output and resize stage: the pipeline's final image of a batch slice in front of the converter, and the resized image of the slice
+  // in front of the converter (only under a format); rows of both padded to 16 bytes
+  rip::api::DevBuf d_fmt, d_rsz;
   int last_chain_walked = 0;  // items per frame the last chain launch of run_batch walked (rip_debug_chain_footprint)
   bool use_tiled_remap = true;
   int last_batch_frames = 0;
   bool work_enqueued = false;  // some frame call has put work on `stream` (rip_set_stream orders a new stream behind it)
-  // prefix of d_stats known to hold zeroed FrameStats records (the grey-world / pca statistics kernels clean up after themselves)
-  const void* stats_clean_ptr = nullptr;
-  size_t stats_clean_cap = 0, stats_clean_bytes = 0;  // (pointer, capacity) identify the allocation: rip::api::DevBuf only ever grows
-  // the leading bytes of d_hist known to be zero: the ccc estimator's global-atomic histogram (small batches) hands its
-  // counters back zeroed, so a stream of single frames pays for one memset, not one per frame
-  const void* hist_clean_ptr = nullptr;
-  size_t hist_clean_cap = 0, hist_clean_bytes = 0;
   // cross-kernel overlap inside one batch (run_batch): the remap of frame group g runs on this internal stream while the
   // statistics and the fused chain of group g + 1 run on the caller's stream
   hipStream_t aux_stream = nullptr;
@@ -304,7 +344,6 @@ struct rip_pipeline {
   bool last_valid[3] = {false, false, false};
   rip::api::DevBuf* last_buf[3] = {nullptr, nullptr, nullptr};
   const void* last_host[3] = {nullptr, nullptr, nullptr};  // pinned host copy of the image (frames that came through rip_collect), else null
-
 
   ~rip_pipeline();  // rip_api.cpp
 };
@@ -364,12 +403,35 @@ void apply_output_format(const rip::Modules& m, Plan& pl);
 FrameView tight_output_view(const Plan& pl, void* d_out);
 FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, size_t out_frame_stride);
 
-// rip_batch.cpp
+// rip_constants.cpp: the device-resident constants, each rebuilt and uploaded when what it was built from has changed
 void und_init(rip_pipeline* p);
 void ensure_host_maps(rip_pipeline* p);
 void need_host_map(rip_pipeline* p);
 void ensure_maps(rip_pipeline* p);
 void ensure_plan(rip_pipeline* p, int src_rows, int src_cols);
+int ensure_chain_items(rip_pipeline* p, int rows, int cols, int flip_angle);
+void ensure_tables(rip_pipeline* p);
+void ensure_vignette(rip_pipeline* p, int rows, int cols);
+void ensure_ccc(rip_pipeline* p, int rows, int cols);
+void ensure_output_table(rip_pipeline* p, int fmt);
+// the resize stage's tables as the kernels' parameter blocks take them (device pointers into ResizeTableConst::dev)
+struct ResizeTables {
+  const int32_t* xofs;
+  const int16_t* alpha;
+  const int32_t* yofs;
+  const int16_t* beta;
+  int area2;
+};
+struct AreaTables {
+  const int32_t *xfirst, *xcount, *xwofs, *yfirst, *ycount, *ywofs;
+  const float *xweight, *yweight;
+  int whole;
+  float scale;
+};
+ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, int W);
+AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W);
+
+// rip_batch.cpp
 size_t fmt_pitch(const Plan& pl);
 void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb = false);
 void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n);

@@ -526,6 +526,11 @@ void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alp
   for (int side : {R, C, H, W})
     if (side < 1 || side > 16384) throw std::invalid_argument("resize: every side of the source and of the target must be in 1..16384");
   if (!xofs || !alpha || !yofs || !beta) throw std::invalid_argument("resize: null table");
+  fill_resize_tables(R, C, H, W, xofs, alpha, yofs, beta);
+  if (area2) *area2 = (R == 2 * H && C == 2 * W) ? 1 : 0;
+}
+
+void fill_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta) {
   // imgproc/resize.cpp, the statements of oracle/rip_oracle.c ripo_resize_linear_8u; weights beyond 16 bits cannot occur (f in [0, 1))
   const double scale_x = (double)C / W, scale_y = (double)R / H;
   for (int dx = 0; dx < W; dx++) {
@@ -547,7 +552,6 @@ void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alp
     yofs[2 * dy] = std::min(std::max(sy, 0), R - 1);
     yofs[2 * dy + 1] = std::min(std::max(sy + 1, 0), R - 1);
   }
-  if (area2) *area2 = (R == 2 * H && C == 2 * W) ? 1 : 0;
 }
 
 void check_output_roi(int x, int y, int width, int height) {

@@ -133,6 +133,9 @@ void check_output_size(int width, int height);
 // *area2 = 1 when R == 2 H and C == 2 W (OpenCV's switch to the 2 x 2 mean; the tables are filled in all the same).
 // xofs: W, alpha: 2 W, yofs: 2 H, beta: 2 H entries.
 void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta, int* area2);
+// the same tables without the checks, for sizes of any positive int: the ccc estimator's resize to 360 x 270 of frames with a side
+// past 16384 takes them from here
+void fill_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta);
 // the names rip_set_output_interpolation accepts: 0 for "linear", 1 for "area"; throws std::invalid_argument naming both otherwise
 int output_interpolation_id(const std::string& name);
 // The sizes the area interpolation takes, from R x C to H x W: every side in 1 .. 16384, no upscale (H <= R, W <= C) and a factor of at
