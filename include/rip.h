@@ -345,8 +345,8 @@ rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, 
  * absent key means off; an invalid value fails with RIP_ERR_INVALID_ARGUMENT and leaves the parameters as they were. */
 rip_status rip_set_output_size(rip_pipeline* p, int width, int height);
 rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height); /* either pointer may be null */
-/* Extension beyond the reference: the filter of the resize stage, "linear" (the default; the text above) or "area".  Any other name,
- * or a null one: RIP_ERR_INVALID_ARGUMENT, nothing changed.  Without effect until a target size is active; it never touches the ccc
+/* Extension beyond the reference: the filter of the resize stage, "linear" (the default; the text above), "area", "linear_aa" or
+ * "cubic_aa".  Any other name, or a null one: RIP_ERR_INVALID_ARGUMENT, nothing changed.  Without effect until a target size is active; it never touches the ccc
  * estimator's own resize, which stays linear.
  * Under "area" resize(F, H, W) is cv::resize(F, Size(W, H), 0, 0, INTER_AREA) for downscales (PARITY.md "Resize: area
  * interpolation"), per channel, with R x C the size of F: a target equal to F's size launches nothing; R == 2 H and C == 2 W is the
@@ -360,7 +360,17 @@ rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height); 
  * top of the refusals above: a target wider or higher than F (area is a downscale filter), and an F more than 256 times the target
  * on an axis.  Geometry, pitches, taps, white-balance info, the ccc track, the dumps and rip_get_output_camera_info are what they are
  * under "linear": output pixel u' averages the source interval whose centre is (u' + 0.5) * C / W - 0.5.
- * Works on RIP_DEVICE_NONE handles.  Params YAML: `output: interpolation: linear | area`; an absent key means linear; an invalid
+ * Under "linear_aa" / "cubic_aa" resize(F, H, W) is, byte for byte, torch.nn.functional.interpolate(F as uint8 NCHW, size=(H, W),
+ * mode='bilinear' / 'bicubic', antialias=True, align_corners=False) -- what torchvision.transforms.v2.Resize gives on uint8 tensors --
+ * for downscales and upscales alike (PARITY.md "Resize: antialiased filters"): a separable triangle (support 1) or cubic (a = -0.5,
+ * support 2) filter, stretched by the scale factor on a downscaled axis, with int16 fixed-point weights built on the host in double;
+ * one pass is clamp((2^(prec - 1) + sum of taps) >> prec, 0, 255) in int32, and the picture is the horizontal pass over every source
+ * row, rounded to uint8, then the vertical pass over that.  An axis that keeps its size is skipped; a target equal to F's size
+ * launches nothing; there is no 2 x 2 special case (torch's taps are 1/8, 3/8, 3/8, 1/8).  Integer work only: the result does not
+ * depend on rip_set_fp_contraction.  Refused under these two names, in the same calls and at the same place in the order as the
+ * rules of "area": an F (or window) more than 64 times the target (or picture) on an axis.  Upscales are accepted up to 16384 per
+ * side.  Everything else -- geometry, window, fit modes, pad, formats, what stays on F, camera info -- is what it is under "linear".
+ * Works on RIP_DEVICE_NONE handles.  Params YAML: `output: interpolation: linear | area | linear_aa | cubic_aa`; an absent key means linear; an invalid
  * value fails with RIP_ERR_INVALID_ARGUMENT and leaves the parameters as they were. */
 rip_status rip_set_output_interpolation(rip_pipeline* p, const char* name);
 rip_status rip_get_output_interpolation(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
@@ -571,6 +581,16 @@ rip_status rip_debug_resize_tables(int src_rows, int src_cols, int dst_rows, int
  * 1.f / (ky * kx) -- else 0 and *scale = 0.  No device, no handle. */
 rip_status rip_debug_resize_area_tables(int src_rows, int src_cols, int dst_rows, int dst_cols, int32_t* xfirst, int32_t* xcount, float* xweight,
                                         int32_t* yfirst, int32_t* ycount, float* yweight, int* whole, float* scale);
+/* Test hook: the tables of the resize stage under "linear_aa" or "cubic_aa" (`name`; rip_set_output_interpolation) from a
+ * src_rows x src_cols image of `channels` (1 or 3) channels to dst_rows x dst_cols: every side in 1..16384, no factor above 64
+ * (RIP_ERR_INVALID_ARGUMENT otherwise, or for another name or a null table).  Output column x reads the xcount[x] >= 1 consecutive
+ * source columns from xfirst[x] on; their int16 weights round(w * 2^*xprec) follow each other in xweight in output order, those of
+ * column x from xwofs[x] on; xfirst / xcount / xwofs: dst_cols entries, xweight: room for 2 * S * max(src_cols, dst_cols) + dst_cols
+ * with S = 1 ("linear_aa") or 2 ("cubic_aa").  Rows alike.  *tile_rows: the kernel's tile height (8, 4, 2 or 1) for that channel
+ * count, *lds_rows: the source rows its LDS image holds.  xwofs, ywofs and the last four pointers may be null.  No device, no handle. */
+rip_status rip_debug_resize_aa_tables(const char* name, int src_rows, int src_cols, int dst_rows, int dst_cols, int channels, int32_t* xfirst,
+                                      int32_t* xcount, int32_t* xwofs, int16_t* xweight, int32_t* yfirst, int32_t* ycount, int32_t* ywofs,
+                                      int16_t* yweight, int* xprec, int* yprec, int* tile_rows, int* lds_rows);
 /* Test hook: the geometry of the resize stage with a window and a fit mode (PARITY.md "Resize: window and fit") for a final image
  * of cols x rows: roi_xywh as for rip_set_output_roi, (width, height) as for rip_set_output_size, fit as for rip_set_output_fit;
  * src_xywh / dst_xywh as rip_get_output_window gives them.  RIP_ERR_INVALID_ARGUMENT for what those setters refuse, a window outside

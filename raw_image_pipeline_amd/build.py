@@ -1,5 +1,5 @@
 """Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the table COMPANIONS below: the kernels
-of the output stage and the three libraries of the resize stage -- for gfx950 with hipcc.
+of the output stage and the four libraries of the resize stage -- for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", os.path.join("..", "..", "include", "rip.h")]
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
 # what tests/variant_cases.py closes over; each companion's table is closed by a tests/*_variant_cases.py of its own.
 # librip_hip.so -- every build of it: the default one, the sanitizer build and the A/B variants under variants/ -- links against
@@ -23,18 +23,22 @@ HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_
 #   area  the resize stage's area interpolation (rip_set_output_interpolation); tests/area_variant_cases.py
 #   fit   the resize stage's kernels that read a window of the image, and the pad kernel of the letterbox (rip_set_output_roi,
 #         rip_set_output_fit); rip_fit.hpp takes its parameter structs from the two headers before it; tests/fit_variant_cases.py
-# rip_resize_dev.hpp is the device code and the launch checks the three libraries of the resize stage share.
+#   aa    the resize stage's antialiased filters (rip_set_output_interpolation "linear_aa" / "cubic_aa"), whole frame and window;
+#         its device code is rip_aa_dev.hpp; tests/aa_variant_cases.py
+# rip_resize_dev.hpp is the device code and the launch checks the libraries of the resize stage share.
 RESIZE_SHARED = ["rip_resize_dev.hpp", "rip_resize.hpp", "rip_area.hpp"]
 COMPANIONS = {
     "out": (os.path.join(HERE, "librip_out_hip.so"), ["rip_output.hip"], ["rip_output.hpp"], "build_out"),
     "rsz": (os.path.join(HERE, "librip_rsz_hip.so"), ["rip_resize.hip"], RESIZE_SHARED, "build_rsz"),
     "area": (os.path.join(HERE, "librip_area_hip.so"), ["rip_area.hip"], RESIZE_SHARED, "build_area"),
     "fit": (os.path.join(HERE, "librip_fit_hip.so"), ["rip_fit.hip"], ["rip_fit.hpp"] + RESIZE_SHARED, "build_fit"),
+    "aa": (os.path.join(HERE, "librip_aa_hip.so"), ["rip_aa.hip"], ["rip_aa.hpp", "rip_aa_dev.hpp"] + RESIZE_SHARED, "build_aa"),
 }
 OUT_COMPANION, COMPANION_SOURCES, COMPANION_HEADERS = COMPANIONS["out"][:3]
 OUT_RSZ, RSZ_SOURCES, RSZ_HEADERS = COMPANIONS["rsz"][:3]
 OUT_AREA, AREA_SOURCES, AREA_HEADERS = COMPANIONS["area"][:3]
 OUT_FIT, FIT_SOURCES, FIT_HEADERS = COMPANIONS["fit"][:3]
+OUT_AA, AA_SOURCES, AA_HEADERS = COMPANIONS["aa"][:3]
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -105,6 +109,7 @@ companion_up_to_date, build_companion = functools.partial(_companion_up_to_date,
 rsz_up_to_date, build_rsz = functools.partial(_companion_up_to_date, "rsz"), functools.partial(_build_companion, "rsz")
 area_up_to_date, build_area = functools.partial(_companion_up_to_date, "area"), functools.partial(_build_companion, "area")
 fit_up_to_date, build_fit = functools.partial(_companion_up_to_date, "fit"), functools.partial(_build_companion, "fit")
+aa_up_to_date, build_aa = functools.partial(_companion_up_to_date, "aa"), functools.partial(_build_companion, "aa")
 
 
 # --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under

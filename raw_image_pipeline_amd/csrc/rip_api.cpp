@@ -588,6 +588,22 @@ rip_status rip_debug_resize_area_tables(int src_rows, int src_cols, int dst_rows
   });
 }
 
+rip_status rip_debug_resize_aa_tables(const char* name, int src_rows, int src_cols, int dst_rows, int dst_cols, int channels, int32_t* xfirst,
+                                      int32_t* xcount, int32_t* xwofs, int16_t* xweight, int32_t* yfirst, int32_t* ycount, int32_t* ywofs, int16_t* yweight,
+                                      int* xprec, int* yprec, int* tile_rows, int* lds_rows) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    if (!name) throw InvalidArgument("rip_debug_resize_aa_tables: null name");
+    const int filter = rip::output_interpolation_id(name);
+    if (filter < 2) throw InvalidArgument("rip_debug_resize_aa_tables: \"linear_aa\" or \"cubic_aa\"");
+    if (channels != 1 && channels != 3) throw InvalidArgument("rip_debug_resize_aa_tables: 1 or 3 channels");
+    int th[2] = {0, 0}, lr[2] = {0, 0};
+    rip::build_resize_aa_tables(filter, src_rows, src_cols, dst_rows, dst_cols, xfirst, xcount, xwofs, xweight, xprec, yfirst, ycount, ywofs, yweight, yprec,
+                                th, lr);
+    if (tile_rows) *tile_rows = th[channels == 3];
+    if (lds_rows) *lds_rows = lr[channels == 3];
+  });
+}
+
 rip_status rip_debug_output_table(const char* name, double divisor, const double* mean, const double* sd, void* out) {
   return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
     if (!name || !mean || !sd || !out) throw InvalidArgument("rip_debug_output_table: null argument");

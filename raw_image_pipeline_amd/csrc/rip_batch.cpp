@@ -468,7 +468,7 @@ void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView ds
 // pitch of the staging image in front of the resize and the converter: every source row starts 16-byte aligned
 size_t fmt_pitch(const Plan& pl) { return ((size_t)pl.out_cols * pl.channels + 15) & ~(size_t)15; }
 
-// The fields ResizeParams and AreaParams (P) have in common: the window of F in `staged` that is read -- its size; its origin goes to
+// The fields ResizeParams, AreaParams and AaParams (P) have in common: the window of F in `staged` that is read -- its size; its origin goes to
 // the launch -- and the picture's rectangle `to` of F' that is written, for n frames.
 template <typename P>
 P resize_params(const FrameView& staged, const FrameView& to, const Plan& pl, int n) {
@@ -490,7 +490,8 @@ P resize_params(const FrameView& staged, const FrameView& to, const Plan& pl, in
 
 // run_batch with the resize and the output stage behind it.  With a target size other than F's, or under a format, the chain's
 // last kernel writes the pipeline's image F into the handle's staging buffer; then one launch of the resize (librip_rsz_hip.so, or
-// librip_area_hip.so under the area interpolation; librip_fit_hip.so when it reads a window of F, rip_set_output_roi) writes F' --
+// librip_area_hip.so under the area interpolation; librip_fit_hip.so when it reads a window of F, rip_set_output_roi; librip_aa_hip.so
+// under an antialiased filter, window or not) writes F' --
 // into the caller's buffer under "native", else into a second staging image; under a letterbox it writes the picture's rectangle of
 // F' and one launch of the pad kernel fills the rest -- and one launch of the converter (librip_out_hip.so) writes the caller's buffer from F' (or from F without a target).  Neither: this is run_batch.
 // dst: the DELIVERED frames.
@@ -507,9 +508,11 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   FrameView converted_from = staged;  // what the converter reads: F, or F' behind a resize
   ResizeTables rt = {};
   AreaTables at = {};
+  AaTables aat = {};
   if (pl.rsz_active) {
     // from the window that is read to the picture that is written: all of F and all of F' unless a window or a fit mode is set
-    if (pl.rsz_area) at = ensure_area_tables(p, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
+    if (pl.rsz_kind >= 2) aat = ensure_aa_tables(p, pl.rsz_kind, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
+    else if (pl.rsz_kind == 1) at = ensure_area_tables(p, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
     else rt = ensure_resize_tables(p, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
     if (pl.out_fmt != rip::OUT_NATIVE) {  // the converter's source alignment
       const size_t pitch = ((size_t)pl.dl_cols * pl.channels + 15) & ~(size_t)15;
@@ -534,7 +537,22 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
     RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
   };
   rip::ResizeLaunchInfo info = {};
-  if (pl.rsz_active && pl.rsz_area) {
+  if (pl.rsz_active && pl.rsz_kind >= 2) {  // an antialiased filter: one launch function for all of F and for a window
+    rip::AaParams r = resize_params<rip::AaParams>(staged, to, pl, n);
+    r.tile_rows = aat.tile_rows[pl.channels == 3];
+    r.lds_rows = aat.lds_rows[pl.channels == 3];
+    r.xprec = aat.xprec;
+    r.yprec = aat.yprec;
+    r.xfirst = aat.xfirst;
+    r.xcount = aat.xcount;
+    r.xwofs = aat.xwofs;
+    r.xweight = aat.xweight;
+    r.yfirst = aat.yfirst;
+    r.ycount = aat.ycount;
+    r.ywofs = aat.ywofs;
+    r.yweight = aat.yweight;
+    launched(rip::launch_aa(r, win, p->stream, &info), info, "the antialiased resize");
+  } else if (pl.rsz_active && pl.rsz_kind == 1) {
     rip::AreaParams r = resize_params<rip::AreaParams>(staged, to, pl, n);
     r.whole = at.whole;
     r.scale = at.scale;

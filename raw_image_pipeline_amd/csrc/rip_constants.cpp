@@ -398,4 +398,24 @@ AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W) {
           reinterpret_cast<const float*>(d + o_yw), p->rsz_tables.whole, p->rsz_tables.scale};
 }
 
+// The tables of an antialiased filter (rip::build_resize_aa_tables) in the same buffer and under the same key, whose last entry is
+// the filter.  Parts: xfirst, xcount, xwofs [W], yfirst, ycount, ywofs [H] of 4-byte entries, then the int16 weights of the columns
+// and of the rows, each part of its capacity rounded up to an even count.
+AaTables ensure_aa_tables(rip_pipeline* p, int filter, int R, int C, int H, int W) {
+  const size_t o_y = (size_t)W * 3, o_xw = o_y + (size_t)H * 3;  // in 4-byte entries
+  const size_t cap_x = (rip::resize_aa_weight_capacity(filter, C, W) + 1) & ~(size_t)1, cap_y = (rip::resize_aa_weight_capacity(filter, R, H) + 1) & ~(size_t)1;
+  const size_t bytes = o_xw * 4 + (cap_x + cap_y) * 2;
+  ResizeTableConst& t = p->rsz_tables;
+  ensure_keyed_tables(p, {R, C, H, W, filter}, bytes, [&](uint8_t* raw) {
+    int32_t* h = reinterpret_cast<int32_t*>(raw);
+    int16_t* wts = reinterpret_cast<int16_t*>(raw + o_xw * 4);
+    rip::build_resize_aa_tables(filter, R, C, H, W, h, h + W, h + 2 * (size_t)W, wts, &t.aa_xprec, h + o_y, h + o_y + H, h + o_y + 2 * (size_t)H, wts + cap_x,
+                                &t.aa_yprec, t.aa_tile_rows, t.aa_lds_rows);
+  });
+  const int32_t* d = t.dev.as<int32_t>();
+  const int16_t* dw = reinterpret_cast<const int16_t*>(d + o_xw);
+  return {d, d + W, d + 2 * (size_t)W, d + o_y, d + o_y + H, d + o_y + 2 * (size_t)H, dw, dw + cap_x, t.aa_xprec, t.aa_yprec,
+          {t.aa_tile_rows[0], t.aa_tile_rows[1]}, {t.aa_lds_rows[0], t.aa_lds_rows[1]}};
+}
+
 }  // namespace rip::api

@@ -17,6 +17,7 @@
 #include "rip_host.hpp"
 #include "rip_kernels.hpp"
 #include "rip_output.hpp"
+#include "rip_aa.hpp"
 #include "rip_area.hpp"
 #include "rip_fit.hpp"
 #include "rip_resize.hpp"
@@ -134,9 +135,10 @@ struct Plan {
   // stay the pipeline's own image F -- and whether a resize kernel runs between F and the converter (a target other than F's size)
   int dl_rows = 0, dl_cols = 0;
   bool rsz_active = false;
-  // that kernel is the area interpolation's (rip_set_output_interpolation "area"; rip_area.hpp): false for the exact 2 x 2 case,
-  // which is the mean kernel of the linear path under either name
-  bool rsz_area = false;
+  // which filter's kernel that is, as rip::output_interpolation_id numbers them: 0 the linear path's (also the exact 2 x 2 case under
+  // "area", which is its mean kernel, and a copy under any name), 1 the area interpolation's (rip_area.hpp), 2 / 3 the antialiased
+  // linear / cubic filter's (rip_aa.hpp)
+  int rsz_kind = 0;
   // the window and the fit mode (rip_set_output_roi, rip_set_output_fit; rip::output_window_geometry): win_* is the rectangle of F
   // the resize reads, pic_* the rectangle of the delivered dl_rows x dl_cols image it writes; every other delivered pixel gets `pad`
   // (channels bytes).  fit_geometry: a window or a fit mode other than "stretch" is set, so these fields decide (without either
@@ -273,7 +275,8 @@ struct OutputTableConst {
   bool dirty = true;
 };
 // resize stage (rip_set_output_size): the tables of rip::build_resize_tables or, under the area interpolation,
-// rip::build_resize_area_tables, rebuilt and uploaded when the (R, C, H, W, kind of table) they were built for changes
+// rip::build_resize_area_tables, or, under an antialiased filter, rip::build_resize_aa_tables, rebuilt and uploaded when the
+// (R, C, H, W, kind of table: the filter, one of four) they were built for changes
 struct ResizeTableConst {
   std::vector<uint8_t> host;
   DevBuf dev;
@@ -281,6 +284,8 @@ struct ResizeTableConst {
   int area2 = 0;  // build_resize_tables' flag for that key: the 2 x 2 mean replaces the tables
   int whole = 0;  // build_resize_area_tables' flag and scale for that key: whole factors, no table is read
   float scale = 0.f;
+  // build_resize_aa_tables' precisions for that key, and its tile height and LDS rows for 1 ([0]) and 3 ([1]) channels
+  int aa_xprec = 0, aa_yprec = 0, aa_tile_rows[2] = {0, 0}, aa_lds_rows[2] = {0, 0};
 };
 
 }  // namespace rip::api
@@ -430,6 +435,14 @@ struct AreaTables {
 };
 ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, int W);
 AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W);
+struct AaTables {
+  const int32_t *xfirst, *xcount, *xwofs, *yfirst, *ycount, *ywofs;
+  const int16_t *xweight, *yweight;
+  int xprec, yprec;
+  int tile_rows[2], lds_rows[2];  // for 1 and for 3 channels
+};
+// filter: 2 (linear_aa) or 3 (cubic_aa), rip::output_interpolation_id's numbers
+AaTables ensure_aa_tables(rip_pipeline* p, int filter, int R, int C, int H, int W);
 
 // rip_batch.cpp
 size_t fmt_pitch(const Plan& pl);

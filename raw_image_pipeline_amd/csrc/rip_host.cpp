@@ -321,11 +321,11 @@ void params_from_node(Modules& m, const YamlNode& node) {
     out_h = (int)v[1];
     check_output_size(out_w, out_h);
   }
-  // extension key output: interpolation: linear | area (rip_set_output_interpolation); absent means linear
+  // extension key output: interpolation: linear | area | linear_aa | cubic_aa (rip_set_output_interpolation); absent means linear
   const std::string out_interp = o.get("interpolation", std::string("linear"));
   (void)output_interpolation_id(out_interp);
   if (o["interpolation"].defined() && o["interpolation"].kind != YamlNode::Scalar)
-    throw std::invalid_argument("output: interpolation: one word is expected, \"linear\" or \"area\"");
+    throw std::invalid_argument("output: interpolation: one word is expected, \"linear\" or \"area\", \"linear_aa\" or \"cubic_aa\"");
   // extension keys output: roi: [x, y, w, h] / fit: stretch | letterbox | crop / pad: [b, g, r] (rip_set_output_roi,
   // rip_set_output_fit, rip_set_output_pad); absent keys mean the defaults
   int roi[4] = {0, 0, 0, 0}, pad[3] = {114, 114, 114};
@@ -609,7 +609,9 @@ void output_window_geometry(int C, int R, const int roi[4], int W, int H, int fi
 int output_interpolation_id(const std::string& name) {
   if (name == "linear") return 0;
   if (name == "area") return 1;
-  throw std::invalid_argument("output interpolation \"" + name + "\" not supported: \"linear\" or \"area\"");
+  if (name == "linear_aa") return 2;
+  if (name == "cubic_aa") return 3;
+  throw std::invalid_argument("output interpolation \"" + name + "\" not supported: \"linear\" or \"area\", \"linear_aa\" or \"cubic_aa\"");
 }
 
 void check_resize_area_sizes(int R, int C, int H, int W) {
@@ -654,6 +656,105 @@ void build_resize_area_tables(int R, int C, int H, int W, int32_t* xfirst, int32
   const bool is_whole = R % H == 0 && C % W == 0 && !(R == H && C == W) && !(R == 2 * H && C == 2 * W);
   if (whole) *whole = is_whole ? 1 : 0;
   if (scale) *scale = is_whole ? 1.f / (float)((R / H) * (C / W)) : 0.f;
+}
+
+void check_resize_aa_sizes(int R, int C, int H, int W) {
+  for (int side : {R, C, H, W})
+    if (side < 1 || side > 16384) throw std::invalid_argument("resize: every side of the source and of the target must be in 1..16384");
+  if (C > 64 * W || R > 64 * H)
+    throw std::invalid_argument("output interpolations \"linear_aa\" and \"cubic_aa\" take factors up to 64 per axis: from " + std::to_string(C) + " x " +
+                                std::to_string(R) + " to " + std::to_string(W) + " x " + std::to_string(H) + " is beyond that");
+}
+
+namespace {
+// the filters of PARITY.md "Resize: antialiased filters", in double
+double aa_linear(double t) {
+  t = std::fabs(t);
+  return t < 1.0 ? 1.0 - t : 0.0;
+}
+double aa_cubic(double t) {
+  const double a = -0.5;
+  t = std::fabs(t);
+  if (t < 1.0) return ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0;
+  if (t < 2.0) return (((t - 5.0) * t + 8.0) * t - 4.0) * a;
+  return 0.0;
+}
+int aa_support(int filter) {
+  if (filter != 2 && filter != 3) throw std::invalid_argument("resize: the antialiased filters are 2 (linear_aa) and 3 (cubic_aa)");
+  return filter == 3 ? 2 : 1;
+}
+}  // namespace
+
+size_t resize_aa_weight_capacity(int filter, int s, int d) { return 2 * (size_t)aa_support(filter) * (size_t)std::max(s, d) + (size_t)d; }
+
+size_t build_aa_axis(int filter, int s, int d, int32_t* first, int32_t* count, int32_t* wofs, int16_t* weights, int* prec) {
+  const int S = aa_support(filter);
+  const double scale = (double)s / d;
+  const double support = scale >= 1.0 ? S * scale : (double)S;
+  const double inv = scale >= 1.0 ? 1.0 / scale : 1.0;
+  std::vector<double> w;
+  w.reserve(resize_aa_weight_capacity(filter, s, d));
+  double wmax = 0.0;
+  for (int i = 0; i < d; i++) {
+    const double c = scale * (i + 0.5);
+    const int lo = std::max((int)(c - support + 0.5), 0);
+    const int n = std::min((int)(c + support + 0.5), s) - lo;
+    const size_t at = w.size();
+    double t = 0.0;
+    for (int j = 0; j < n; j++) {
+      const double v = filter == 3 ? aa_cubic((j + lo - c + 0.5) * inv) : aa_linear((j + lo - c + 0.5) * inv);
+      w.push_back(v);
+      t += v;
+    }
+    for (size_t k = at; k < w.size(); k++) {
+      if (t != 0.0) w[k] = w[k] / t;
+      wmax = std::max(wmax, w[k]);
+    }
+    first[i] = lo;
+    count[i] = n;
+    if (wofs) wofs[i] = (int32_t)at;
+  }
+  int pr = 0;
+  while (pr < 22 && (int)(0.5 + wmax * (double)(1 << (pr + 1))) < (1 << 15)) pr++;
+  for (size_t k = 0; k < w.size(); k++)
+    weights[k] = (int16_t)(w[k] >= 0.0 ? (int)(0.5 + w[k] * (double)(1 << pr)) : (int)(-0.5 + w[k] * (double)(1 << pr)));
+  if (prec) *prec = pr;
+  return w.size();
+}
+
+int aa_lds_rows(int s, int d, const int32_t* first, const int32_t* count, int th) {
+  int span = 0;
+  for (int y0 = 0; y0 < d; y0 += th) {
+    const int y1 = std::min(d, y0 + th) - 1;
+    span = std::max(span, s == d ? y1 - y0 + 1 : first[y1] + count[y1] - first[y0]);
+  }
+  return span;
+}
+
+int aa_tile_rows(int s, int d, const int32_t* first, const int32_t* count, int channels, int* lds_rows) {
+  for (int th = 8; th >= 1; th /= 2) {
+    const int span = aa_lds_rows(s, d, first, count, th);
+    if ((size_t)span * 64 * (size_t)channels <= 65536 || th == 1) {
+      if (lds_rows) *lds_rows = span;
+      return th;
+    }
+  }
+  return 1;
+}
+
+void build_resize_aa_tables(int filter, int R, int C, int H, int W, int32_t* xfirst, int32_t* xcount, int32_t* xwofs, int16_t* xweight, int* xprec,
+                            int32_t* yfirst, int32_t* ycount, int32_t* ywofs, int16_t* yweight, int* yprec, int tile_rows[2], int lds_rows[2]) {
+  (void)aa_support(filter);
+  check_resize_aa_sizes(R, C, H, W);
+  if (!xfirst || !xcount || !xweight || !yfirst || !ycount || !yweight) throw std::invalid_argument("resize: null table");
+  build_aa_axis(filter, C, W, xfirst, xcount, xwofs, xweight, xprec);
+  build_aa_axis(filter, R, H, yfirst, ycount, ywofs, yweight, yprec);
+  for (int k = 0; k < 2; k++) {
+    int rows = 0;
+    const int th = aa_tile_rows(R, H, yfirst, ycount, k ? 3 : 1, &rows);
+    if (tile_rows) tile_rows[k] = th;
+    if (lds_rows) lds_rows[k] = rows;
+  }
 }
 
 void check_debayer_16bit_range(int black, int white) {

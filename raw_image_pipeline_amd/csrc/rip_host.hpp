@@ -64,7 +64,7 @@ struct Modules {
   double out_divisor = 255.0, out_mean[3] = {0, 0, 0}, out_std[3] = {1, 1, 1};
   // extension (rip_set_output_size): the size the delivered frames are resized to, in front of the output format; (0, 0) = off
   int out_w = 0, out_h = 0;
-  // extension (rip_set_output_interpolation): the filter of that resize, "linear" or "area"; without effect while no target is active
+  // extension (rip_set_output_interpolation): the filter of that resize, "linear", "area", "linear_aa" or "cubic_aa"; without effect while no target is active
   std::string out_interp = "linear";
   // extension (rip_set_output_roi, rip_set_output_fit, rip_set_output_pad; PARITY.md "Resize: window and fit"): the window of the
   // final image the resize stage reads ((0, 0, 0, 0) = all of it), how the window is placed in the target ("stretch", "letterbox",
@@ -136,11 +136,32 @@ void build_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alp
 // the same tables without the checks, for sizes of any positive int: the ccc estimator's resize to 360 x 270 of frames with a side
 // past 16384 takes them from here
 void fill_resize_tables(int R, int C, int H, int W, int32_t* xofs, int16_t* alpha, int32_t* yofs, int16_t* beta);
-// the names rip_set_output_interpolation accepts: 0 for "linear", 1 for "area"; throws std::invalid_argument naming both otherwise
+// the names rip_set_output_interpolation accepts: 0 for "linear", 1 for "area", 2 for "linear_aa", 3 for "cubic_aa"; throws
+// std::invalid_argument naming them otherwise
 int output_interpolation_id(const std::string& name);
 // The sizes the area interpolation takes, from R x C to H x W: every side in 1 .. 16384, no upscale (H <= R, W <= C) and a factor of at
 // most 256 per axis (R <= 256 H, C <= 256 W: a block sum stays below 2^24).  Throws std::invalid_argument naming the rule.
 void check_resize_area_sizes(int R, int C, int H, int W);
+// The sizes the antialiased filters take, from R x C to H x W: every side in 1 .. 16384 and a factor of at most 64 per axis (R <= 64 H,
+// C <= 64 W: the source rows one output row reads fit the kernel's LDS); upscales are accepted.  Throws std::invalid_argument.
+void check_resize_aa_sizes(int R, int C, int H, int W);
+// The tap list of one axis of an antialiased filter (`filter`: 2 = linear_aa, 3 = cubic_aa as output_interpolation_id numbers them;
+// PARITY.md "Resize: antialiased filters", every step in double) from s source to d target samples: output i reads the count[i] >= 1
+// consecutive source samples from first[i] on, all inside [0, s), with the int16 weights round(w * 2^*prec) that follow each other
+// in `weights` in output order; wofs[i] (optional) is where those of output i start.  Returns the number of weights, at most
+// resize_aa_weight_capacity(filter, s, d) = 2 S max(s, d) + d with S the filter's support (1 or 2).
+size_t resize_aa_weight_capacity(int filter, int s, int d);
+size_t build_aa_axis(int filter, int s, int d, int32_t* first, int32_t* count, int32_t* wofs, int16_t* weights, int* prec);
+// The tile height of the kernel (rip_aa.hpp) for the vertical axis from s to d rows: the largest of 8, 4, 2, 1 at which the source
+// rows any tile's output rows read -- *lds_rows, the largest such span -- times 64 columns times `channels` bytes fit 64 KiB.  A
+// height of 1 always fits under the factor cap.  s == d: the pass is skipped and a tile reads its own rows.
+int aa_tile_rows(int s, int d, const int32_t* first, const int32_t* count, int channels, int* lds_rows);
+// the largest span of source rows a tile of `th` output rows reads
+int aa_lds_rows(int s, int d, const int32_t* first, const int32_t* count, int th);
+// Both axes from R x C to H x W (check_resize_aa_sizes; std::invalid_argument for a null table or another filter); tile_rows[k] /
+// lds_rows[k]: aa_tile_rows for 1 (k = 0) and 3 (k = 1) channels.  xwofs, ywofs, the precisions and the last two may be null.
+void build_resize_aa_tables(int filter, int R, int C, int H, int W, int32_t* xfirst, int32_t* xcount, int32_t* xwofs, int16_t* xweight, int* xprec,
+                            int32_t* yfirst, int32_t* ycount, int32_t* ywofs, int16_t* yweight, int* yprec, int tile_rows[2], int lds_rows[2]);
 // the windows rip_set_output_roi accepts: (0, 0, 0, 0), or x, y >= 0 with width and height in 1 .. 16384; throws std::invalid_argument
 void check_output_roi(int x, int y, int width, int height);
 // the names rip_set_output_fit accepts: 0 for "stretch", 1 for "letterbox", 2 for "crop"; throws std::invalid_argument naming them otherwise

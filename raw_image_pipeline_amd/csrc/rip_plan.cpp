@@ -157,7 +157,7 @@ void apply_output_format(const rip::Modules& m, Plan& pl) {
   pl.fit_geometry = m.roi_w > 0 || (m.out_w > 0 && fit != 0);
   if (pl.fit_geometry) {
     // a window, or a fit mode that changes what a target means (PARITY.md "Resize: window and fit").  The refusals in their order:
-    // a bgr16 result, a window outside F, an F beyond the resize's sides, the area interpolation's rules on window -> picture.
+    // a bgr16 result, a window outside F, an F beyond the resize's sides, the filter's own rules on window -> picture.
     if (pl.out_elem_bytes != 1)
       throw InvalidArgument("output roi / fit need an 8-bit pipeline result; this frame gives bgr16 (set a 16-bit range, or the roi (0, 0, 0, 0) and the fit 'stretch')");
     const int roi[4] = {m.roi_x, m.roi_y, m.roi_w, m.roi_h};
@@ -175,9 +175,14 @@ void apply_output_format(const rip::Modules& m, Plan& pl) {
         throw InvalidArgument("output size: the pipeline's image of " + std::to_string(pl.out_cols) + " x " + std::to_string(pl.out_rows) +
                               " is larger than the " + std::to_string(rip::kRszMaxSide) + " pixels per side the resize takes");
       // a picture of the window's own size is a copy, which the linear tables are (weights 2048 and 0) under either interpolation
-      if (rip::output_interpolation_id(m.out_interp) == 1 && !(pl.win_w == pl.pic_w && pl.win_h == pl.pic_h)) {
+      const int filter = rip::output_interpolation_id(m.out_interp);
+      if (filter == 1 && !(pl.win_w == pl.pic_w && pl.win_h == pl.pic_h)) {
         rip::check_resize_area_sizes(pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
-        pl.rsz_area = !(pl.win_h == 2 * pl.pic_h && pl.win_w == 2 * pl.pic_w);
+        pl.rsz_kind = pl.win_h == 2 * pl.pic_h && pl.win_w == 2 * pl.pic_w ? 0 : 1;
+      } else if (filter >= 2 && !(pl.win_w == pl.pic_w && pl.win_h == pl.pic_h)) {
+        // the antialiased filters' own refusal (a factor beyond 64); no 2 x 2 special case under these names
+        rip::check_resize_aa_sizes(pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
+        pl.rsz_kind = filter;
       }
       pl.rsz_active = true;
     }
@@ -189,10 +194,14 @@ void apply_output_format(const rip::Modules& m, Plan& pl) {
       if (pl.out_rows > rip::kRszMaxSide || pl.out_cols > rip::kRszMaxSide)
         throw InvalidArgument("output size: the pipeline's image of " + std::to_string(pl.out_cols) + " x " + std::to_string(pl.out_rows) +
                               " is larger than the " + std::to_string(rip::kRszMaxSide) + " pixels per side the resize takes");
-      if (rip::output_interpolation_id(m.out_interp) == 1) {
+      const int filter = rip::output_interpolation_id(m.out_interp);
+      if (filter == 1) {
         // the area interpolation's own refusals (an upscale, a factor beyond 256); the exact 2 x 2 case is the linear path's mean
         rip::check_resize_area_sizes(pl.out_rows, pl.out_cols, m.out_h, m.out_w);
-        pl.rsz_area = !(pl.out_rows == 2 * m.out_h && pl.out_cols == 2 * m.out_w);
+        pl.rsz_kind = pl.out_rows == 2 * m.out_h && pl.out_cols == 2 * m.out_w ? 0 : 1;
+      } else if (filter >= 2) {
+        rip::check_resize_aa_sizes(pl.out_rows, pl.out_cols, m.out_h, m.out_w);  // a factor beyond 64
+        pl.rsz_kind = filter;
       }
       pl.rsz_active = true;
       pl.dl_rows = m.out_h;

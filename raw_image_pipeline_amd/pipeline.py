@@ -677,10 +677,13 @@ class RawImagePipeline:
         return w.value, h.value
 
     def set_output_interpolation(self, name):
-        """Extension: the filter of the resize stage, ``"linear"`` (default) or ``"area"`` -- cv::resize's INTER_AREA for
-        downscales, which averages every source pixel an output pixel covers.  Without effect until ``set_output_size`` has set a
-        target; under ``"area"`` a target larger than the image, or more than 256 times smaller, on an axis is refused by the
-        frame calls (ValueError).  include/rip.h rip_set_output_interpolation."""
+        """Extension: the filter of the resize stage, ``"linear"`` (default), ``"area"`` -- cv::resize's INTER_AREA for
+        downscales, which averages every source pixel an output pixel covers -- or ``"linear_aa"`` / ``"cubic_aa"``: byte for byte
+        ``torch.nn.functional.interpolate(uint8, mode='bilinear' / 'bicubic', antialias=True)``, which is what
+        ``torchvision.transforms.v2.Resize`` computes on uint8 tensors, for downscales and upscales.  Without effect until
+        ``set_output_size`` has set a target; under ``"area"`` a target larger than the image, or more than 256 times smaller, on an
+        axis is refused by the frame calls (ValueError), under the two antialiased names a target more than 64 times smaller.
+        include/rip.h rip_set_output_interpolation."""
         self._call("rip_set_output_interpolation", name.encode())
 
     def get_output_interpolation(self):
