@@ -260,6 +260,52 @@ class RawImagePipeline {
     P = detail::make_f64(3, 4);
     check(rip_get_output_camera_info(h_, rows, cols, channels, encoding.c_str(), &height, &width, detail::doubles(K), detail::doubles(P)));
   }
+  // Not in the reference: output heads (rip.h rip_set_output_heads) -- up to 8 complete sets of the output settings above, delivered
+  // together from one run of the chain.  selectOutputHead says which set every setOutput* / getOutput* call, apply, process and submit
+  // address; with one head and head 0 selected (the defaults) nothing changes.
+  void setOutputHeads(int n) { check(rip_set_output_heads(h_, n)); }
+  int getOutputHeads() const {
+    int n = 0;
+    check(rip_get_output_heads(h_, &n));
+    return n;
+  }
+  void selectOutputHead(int head) { check(rip_select_output_head(h_, head)); }
+  int getSelectedOutputHead() const {
+    int head = 0;
+    check(rip_get_selected_output_head(h_, &head));
+    return head;
+  }
+  // process() for every head at once: one upload, one run of the chain (rip_apply_heads).  outs[k] is head k's image with the Mat type
+  // process() gives under that head's format (CV_8UC3 / CV_8UC1; a planar float format on any head throws like process());
+  // `encoding` is rewritten to what head 0 delivers.  The selection is left as it was.
+  void processHeads(const Mat& image, std::string& encoding, std::vector<Mat>& outs) {
+    const int n = getOutputHeads(), was = getSelectedOutputHead();
+    const int in_cols = pixel_cols(image, encoding);
+    std::vector<int> rows(n), cols(n), cn(n);
+    std::vector<uint8_t*> ptrs(n);
+    std::vector<size_t> caps(n);
+    std::vector<Mat> made(n);
+    std::string enc0;
+    struct Reselect {
+      rip_pipeline* h;
+      int head;
+      ~Reselect() { (void)rip_select_output_head(h, head); }
+    } reselect{h_, was};
+    for (int k = 0; k < n; k++) {
+      char enc[32] = {0};
+      check(rip_select_output_head(h_, k));
+      need_u8_output();
+      check(rip_query_output(h_, image.rows, in_cols, image.channels(), encoding.c_str(), &rows[k], &cols[k], &cn[k], enc));
+      if (k == 0) enc0 = enc;
+      made[k] = detail::make_u8(rows[k], cols[k], cn[k]);
+      ptrs[k] = detail::bytes(made[k]);
+      caps[k] = (size_t)rows[k] * cols[k] * cn[k];
+    }
+    check(rip_apply_heads(h_, detail::bytes(image), image.rows, in_cols, image.channels(), detail::step_of(image), encoding.c_str(), ptrs.data(),
+                          caps.data(), n, rows.data(), cols.data(), cn.data()));
+    encoding = enc0;
+    outs.swap(made);
+  }
 
   void setFlip(bool enabled) { check(rip_set_flip(h_, enabled)); }
   void setFlipAngle(int angle) { check(rip_set_flip_angle(h_, angle)); }

@@ -425,6 +425,66 @@ rip_status rip_get_output_window(rip_pipeline* p, int rows, int cols, int channe
  * fails.  Works on RIP_DEVICE_NONE handles. */
 rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* height, int* width,
                                       double K[9], double P[12]);
+/* Extension beyond the reference: output heads -- several delivered images per frame from one run of the chain (PARITY.md "Output
+ * heads").  An output head is one complete set of the output stage's settings: format and normalisation, target size, interpolation,
+ * window, fit mode and pad colour.  A handle has n heads, 1 <= n <= RIP_MAX_OUTPUT_HEADS; head 0 is the output of a handle that
+ * never asked for more, further heads start at the defaults ("native", no target, no window, "stretch", "linear", pad 114).
+ * rip_set_output_heads: sets n.  Heads at and beyond n are reset to the defaults; a selection at or beyond n becomes 0.  Refused
+ * with RIP_ERR_INVALID_ARGUMENT outside 1..8 and while ring frames are in flight (as rip_set_ring_depth is).
+ * rip_select_output_head: which head every single-output entry addresses from now on -- the setters and getters rip_set / get_
+ * output_format, _normalization, _size, _interpolation, _roi, _fit, _pad; the queries rip_query_output, rip_query_output_bytes,
+ * rip_get_output_camera_info, rip_get_output_window; and the frame calls rip_apply, rip_apply_device, rip_submit, rip_submit_to
+ * (the frame of a ring slot is delivered under the head selected when it was submitted).  An index outside 0..n-1:
+ * RIP_ERR_INVALID_ARGUMENT, nothing changed.  With n = 1 and head 0 selected -- the defaults -- every call behaves bit for bit as
+ * it did before there were heads.
+ * Work on RIP_DEVICE_NONE handles.  Params YAML: the sections `output_1:` .. `output_7:` take exactly the keys of `output:`; after
+ * a load n = 1 + the largest k present, sections absent in between hold the defaults and head 0 is selected; a file without such
+ * a section gives n = 1.  `output_8:` and above, or an invalid value inside a section: RIP_ERR_INVALID_ARGUMENT, parameters as
+ * they were. */
+#define RIP_MAX_OUTPUT_HEADS 8
+rip_status rip_set_output_heads(rip_pipeline* p, int n);
+rip_status rip_get_output_heads(rip_pipeline* p, int* n); /* the pointer may be null */
+rip_status rip_select_output_head(rip_pipeline* p, int head);
+rip_status rip_get_selected_output_head(rip_pipeline* p, int* head); /* the pointer may be null */
+/* One head's buffer of rip_apply_device_heads: d_out, out_step and out_frame_stride as rip_apply_device takes them for that head's
+ * settings (0 = tightly packed); d_out NULL: the head is not requested -- it is neither planned nor validated and nothing runs for it. */
+typedef struct {
+  void* d_out;
+  size_t out_step;
+  size_t out_frame_stride;
+} rip_head_buffer;
+/* rip_apply_device with one delivered image per requested head.  The chain, the white-balance statistics, the ccc estimator and the
+ * undistortion run ONCE per batch (slice); the ccc Kalman state advances once per frame; the taps, rip_get_white_balance_info and
+ * rip_get_ccc_track are those of that one run.  The bytes written into head k's buffer are exactly the bytes rip_apply_device writes
+ * into a buffer of the same layout on a handle with the same pipeline settings whose only output has head k's settings, float formats
+ * as bit patterns; bytes that call leaves untouched (row padding, plane remainders, gaps between frames) stay untouched here.
+ * heads: n_heads entries, n_heads equal to rip_get_output_heads.  Overlapping head buffers are the caller's responsibility.
+ * Checked in this order, all before anything is enqueued (the ccc filter does not advance): a null d_in, heads or encoding;
+ * n_heads other than the handle's n; no requested head; the frame's own refusals (as rip_apply_device); for each requested head in
+ * index order the refusals of its settings in their usual order, then the layout rules of rip_apply_device for its buffer -- the
+ * message prefixed "output head <k>: "; more than one requested head on a bgr16 result; taps on a bgr16 result.  n_frames == 0
+ * returns RIP_OK.  One requested head takes exactly the launches of rip_apply_device.  With several, among the requested heads that
+ * deliver F as it is ("native", no active resize, no window smaller than F), in index order, the first whose buffer address, row
+ * pitch and frame stride are all multiples of 16 bytes is written by the chain's last kernel directly and read by the other heads
+ * (tight bgr8 rows of 2448, 1920 or 1440 pixels qualify); every other such head costs one copy launch (head_copy_kernel of
+ * librip_heads_hip.so); every other head runs its resize / pad / converter launches in index order.  The launch record
+ * (rip_debug_launch_log) of a call is the chain's launches of a single run followed per head by that head's. */
+rip_status rip_apply_device_heads(rip_pipeline* p, const void* d_in, size_t in_step, size_t in_frame_stride, int n_frames, int rows, int cols,
+                                  int channels, const char* encoding, const rip_head_buffer* heads, int n_heads, void* d_tap_debayered,
+                                  void* d_tap_color);
+/* rip_apply with one delivered image per requested head: uploads the frame once, runs as rip_apply_device_heads does and downloads
+ * every requested head tightly packed into outs[k] (NULL: not requested) of out_capacities[k] bytes -- RIP_ERR_CAPACITY, message
+ * prefixed "output head <k>: ", where rip_apply gives it.  out_rows / out_cols / out_channels: n_heads entries each with the delivered
+ * geometry of the requested heads (0 for the others); each array may be null.  RIP_IMAGE_PROCESSED is empty afterwards -- the
+ * delivered buffers are the results -- while the DEBAYERED and COLOR taps are kept as rip_apply keeps them.  Writes no debug dumps
+ * whatever rip_set_debug says. */
+rip_status rip_apply_heads(rip_pipeline* p, const uint8_t* image, int rows, int cols, int channels, size_t step, const char* encoding,
+                           uint8_t* const* outs, const size_t* out_capacities, int n_heads, int* out_rows, int* out_cols, int* out_channels);
+/* Test hook: for head `head` (0..n-1, else RIP_ERR_INVALID_ARGUMENT), *table_builds: how often its device tables (the planar formats'
+ * table, the resize tables) were built and uploaded since the handle was created -- a steady sequence of identical calls builds each
+ * head's tables once; *direct_write / *copied: whether the last frame call that delivered the head had the chain write its buffer
+ * directly (also true of a head that delivers F in a single-output call) or copied it from the staging image.  Any pointer may be null. */
+rip_status rip_debug_output_head_info(rip_pipeline* p, int head, int* table_builds, int* direct_write, int* copied);
 rip_status rip_set_flip(rip_pipeline* p, int enabled);                            /* hpp:69 */
 rip_status rip_set_flip_angle(rip_pipeline* p, int angle);                        /* hpp:70 */
 rip_status rip_set_white_balance(rip_pipeline* p, int enabled);                   /* hpp:72 */

@@ -1,5 +1,5 @@
-"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the table COMPANIONS below: the kernels
-of the output stage and the four libraries of the resize stage -- for gfx950 with hipcc.
+"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the tables COMPANIONS and HEAD_LIBRARIES below: the kernels
+of the output stage, the four libraries of the resize stage and the output heads' copy -- for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", os.path.join("..", "..", "include", "rip.h")]
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
 # what tests/variant_cases.py closes over; each companion's table is closed by a tests/*_variant_cases.py of its own.
 # librip_hip.so -- every build of it: the default one, the sanitizer build and the A/B variants under variants/ -- links against
@@ -39,6 +39,14 @@ OUT_RSZ, RSZ_SOURCES, RSZ_HEADERS = COMPANIONS["rsz"][:3]
 OUT_AREA, AREA_SOURCES, AREA_HEADERS = COMPANIONS["area"][:3]
 OUT_FIT, FIT_SOURCES, FIT_HEADERS = COMPANIONS["fit"][:3]
 OUT_AA, AA_SOURCES, AA_HEADERS = COMPANIONS["aa"][:3]
+# A second table of the same rows beside COMPANIONS (which tests/test_aa_variants.py closes at five): the libraries behind the output
+# heads.  Built, dated, linked and found through $ORIGIN exactly like the companions, in every build.
+#   heads  head_copy_kernel, the copy that delivers F to a further head that asks for it as it is (rip_apply_device_heads);
+#          tests/heads_variant_cases.py
+HEAD_LIBRARIES = {
+    "heads": (os.path.join(HERE, "librip_heads_hip.so"), ["rip_heads.hip"], ["rip_heads.hpp"], "build_heads"),
+}
+OUT_HEADS, HEADS_SOURCES, HEADS_HEADERS = HEAD_LIBRARIES["heads"][:3]
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -57,8 +65,16 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
+def _row(key):
+    return COMPANIONS[key] if key in COMPANIONS else HEAD_LIBRARIES[key]
+
+
+def _all_keys():
+    return list(COMPANIONS) + list(HEAD_LIBRARIES)
+
+
 def _companion_up_to_date(key):
-    out, sources, headers, _ = COMPANIONS[key]
+    out, sources, headers, _ = _row(key)
     if not os.path.exists(out):
         return False
     t = os.path.getmtime(out)
@@ -67,7 +83,7 @@ def _companion_up_to_date(key):
 
 
 def companions_up_to_date():
-    return all(_companion_up_to_date(key) for key in COMPANIONS)
+    return all(_companion_up_to_date(key) for key in _all_keys())
 
 
 def up_to_date():
@@ -80,7 +96,7 @@ def up_to_date():
 
 def _build_companion(key, force=False, verbose=False):
     """One companion library, next to librip_hip.so."""
-    out, sources, _, bdir_name = COMPANIONS[key]
+    out, sources, _, bdir_name = _row(key)
     if not force and _companion_up_to_date(key):
         return out
     bdir = os.path.join(HERE, bdir_name)
@@ -110,6 +126,7 @@ rsz_up_to_date, build_rsz = functools.partial(_companion_up_to_date, "rsz"), fun
 area_up_to_date, build_area = functools.partial(_companion_up_to_date, "area"), functools.partial(_build_companion, "area")
 fit_up_to_date, build_fit = functools.partial(_companion_up_to_date, "fit"), functools.partial(_build_companion, "fit")
 aa_up_to_date, build_aa = functools.partial(_companion_up_to_date, "aa"), functools.partial(_build_companion, "aa")
+heads_up_to_date, build_heads = functools.partial(_companion_up_to_date, "heads"), functools.partial(_build_companion, "heads")
 
 
 # --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under
@@ -143,7 +160,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
             return out
     if out is None and not force and up_to_date():
         return OUT
-    for key in COMPANIONS:  # every build of librip_hip.so links against all of them; `force` is about the library asked for
+    for key in _all_keys():  # every build of librip_hip.so links against all of them; `force` is about the library asked for
         _build_companion(key, verbose=verbose)
     out = out or OUT
     objs = []
@@ -167,7 +184,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
         if verbose and log.strip():
             print(log)
     # the companions are found next to the library ($ORIGIN) or one directory up (variants/*.so)
-    companion = ["-L" + HERE] + ["-l:" + os.path.basename(c[0]) for c in COMPANIONS.values()] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    companion = ["-L" + HERE] + ["-l:" + os.path.basename(c[0]) for c in list(COMPANIONS.values()) + list(HEAD_LIBRARIES.values())] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
     cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -216,7 +216,7 @@ rip_status rip_query_output(rip_pipeline* p, int rows, int cols, int channels, c
     need(p);
     if (!encoding) throw InvalidArgument("encoding is null");
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, pl);
+    apply_output_format(p->m, p->m.selected, pl);
     if (out_rows) *out_rows = pl.dl_rows;
     if (out_cols) *out_cols = pl.dl_cols;
     if (out_channels) *out_channels = pl.dl_channels;
@@ -230,7 +230,7 @@ rip_status rip_query_output_bytes(rip_pipeline* p, int rows, int cols, int chann
     need(p);
     if (!encoding) throw InvalidArgument("encoding is null");
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, pl);
+    apply_output_format(p->m, p->m.selected, pl);
     if (bytes) *bytes = delivered_bytes(pl);
     if (elem_bytes) *elem_bytes = pl.dl_elem_bytes;
     if (planar) *planar = pl.dl_planar ? 1 : 0;
@@ -258,7 +258,7 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     if (n_frames < 0) throw InvalidArgument("negative frame count");
     if (n_frames == 0) return;
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, pl);
+    apply_output_format(p->m, p->m.selected, pl);
     const size_t in_row = row_bytes(pl, cols, channels);
     if (in_step == 0) in_step = in_row;
     if (in_frame_stride == 0) in_frame_stride = in_step * rows;
@@ -283,6 +283,97 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
   });
 }
 
+// ---- output heads --------------------------------------------------------------------------------
+rip_status rip_set_output_heads(rip_pipeline* p, int n) {
+  return guarded(p, [&] {
+    need(p);
+    if (n < 1 || n > RIP_MAX_OUTPUT_HEADS) throw InvalidArgument("output heads: 1.." + std::to_string(RIP_MAX_OUTPUT_HEADS) + " expected, got " + std::to_string(n));
+    for (auto& s : p->ring)
+      if (s->busy) throw InvalidArgument("rip_set_output_heads: frames are in flight");
+    for (int k = n; k < RIP_MAX_OUTPUT_HEADS; k++) {
+      p->m.heads[k] = rip::OutputHead();
+      p->out_table[k].dirty = true;
+      p->head_record[k] = {};
+    }
+    p->m.n_heads = n;
+    if (p->m.selected >= n) p->m.selected = 0;
+  });
+}
+
+rip_status rip_get_output_heads(rip_pipeline* p, int* n) {
+  return guarded(p, [&] {
+    need(p);
+    if (n) *n = p->m.n_heads;
+  });
+}
+
+rip_status rip_select_output_head(rip_pipeline* p, int head) {
+  return guarded(p, [&] {
+    need(p);
+    if (head < 0 || head >= p->m.n_heads)
+      throw InvalidArgument("output head " + std::to_string(head) + " does not exist: the handle has heads 0.." + std::to_string(p->m.n_heads - 1));
+    p->m.selected = head;
+  });
+}
+
+rip_status rip_get_selected_output_head(rip_pipeline* p, int* head) {
+  return guarded(p, [&] {
+    need(p);
+    if (head) *head = p->m.selected;
+  });
+}
+
+rip_status rip_debug_output_head_info(rip_pipeline* p, int head, int* table_builds, int* direct_write, int* copied) {
+  return guarded(p, [&] {
+    need(p);
+    if (head < 0 || head >= p->m.n_heads)
+      throw InvalidArgument("output head " + std::to_string(head) + " does not exist: the handle has heads 0.." + std::to_string(p->m.n_heads - 1));
+    if (table_builds) *table_builds = p->out_table[head].builds + p->rsz_tables[head].builds;
+    if (direct_write) *direct_write = p->head_record[head].direct_write;
+    if (copied) *copied = p->head_record[head].copied;
+  });
+}
+
+rip_status rip_apply_device_heads(rip_pipeline* p, const void* d_in, size_t in_step, size_t in_frame_stride, int n_frames, int rows, int cols,
+                                  int channels, const char* encoding, const rip_head_buffer* heads, int n_heads, void* d_tap_debayered,
+                                  void* d_tap_color) {
+  return guarded(p, [&] {
+    need_device(p);
+    if (!d_in || !heads || !encoding) throw InvalidArgument("null buffer, heads or encoding");
+    if (n_heads != p->m.n_heads)
+      throw InvalidArgument("rip_apply_device_heads: " + std::to_string(n_heads) + " head buffers for a handle with " + std::to_string(p->m.n_heads) + " output heads");
+    bool requested[RIP_MAX_OUTPUT_HEADS] = {};
+    bool any = false;
+    for (int k = 0; k < n_heads; k++) any |= requested[k] = heads[k].d_out != nullptr;
+    if (!any) throw InvalidArgument("rip_apply_device_heads: no head is requested (every d_out is null)");
+    if (n_frames < 0) throw InvalidArgument("negative frame count");
+    if (n_frames == 0) return;
+    const Plan pl = make_plan(p->m, rows, cols, channels, encoding);
+    Plan plans[RIP_MAX_OUTPUT_HEADS];
+    FrameView dsts[RIP_MAX_OUTPUT_HEADS];
+    plan_heads(p->m, pl, n_heads, requested, d_tap_debayered || d_tap_color, plans, dsts,
+               [&](int k, const Plan& hp) { return resolve_output_layout(hp, heads[k].d_out, heads[k].out_step, heads[k].out_frame_stride); });
+    // the input: rip_apply_device's rules
+    const size_t in_row = row_bytes(pl, cols, channels);
+    if (in_step == 0) in_step = in_row;
+    if (in_frame_stride == 0) in_frame_stride = in_step * rows;
+    if (in_step < in_row) throw InvalidArgument("input row pitch smaller than a row");
+    if (in_frame_stride < in_step * (size_t)(rows - 1) + in_row) throw InvalidArgument("input frame stride smaller than a frame");
+    if (in_step >= (1u << 24) || (unsigned long long)in_step * rows >= (1ull << 32))
+      throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
+    const ConstFrameView src = {static_cast<const uint8_t*>(d_in), in_step, in_frame_stride, rows, cols};
+    const size_t tap_frame = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
+    constexpr int kMaxFramesPerLaunch = 16384;  // rip_apply_device's slices: per slice the chain runs once, then the heads
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
+      const Taps taps = {d_tap_debayered ? static_cast<uint8_t*>(d_tap_debayered) + (size_t)f0 * tap_frame : nullptr,
+                         d_tap_color ? static_cast<uint8_t*>(d_tap_color) + (size_t)f0 * tap_frame : nullptr};
+      FrameView slice[RIP_MAX_OUTPUT_HEADS];
+      for (int k = 0; k < n_heads; k++) slice[k] = requested[k] ? frames_from(dsts[k], f0) : dsts[k];
+      run_batch_heads(p, pl, plans, slice, n_heads, frames_from(src, f0), taps, std::min(kMaxFramesPerLaunch, n_frames - f0));
+    }
+  });
+}
+
 // ---- loaders -----------------------------------------------------------------------------------
 rip_status rip_load_params(rip_pipeline* p, const char* path) {
   return guarded(p, [&] {
@@ -303,7 +394,8 @@ rip_status rip_load_params(rip_pipeline* p, const char* path) {
       p->m.und_available = false;
       p->ccc.state_init = false;
     }
-    p->tables.dirty = p->vignette.dirty = p->ccc.cfg_dirty = p->out_table.dirty = true;
+    p->tables.dirty = p->vignette.dirty = p->ccc.cfg_dirty = true;
+    for (auto& t : p->out_table) t.dirty = true;
     und_init(p);  // setBalance / setFovScale re-run init()
   });
 }
@@ -374,20 +466,20 @@ RIP_SETTER(rip_set_debayer_encoding, (rip_pipeline * p, const char* s), if (!s) 
 RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            rip::check_debayer_method(s); p->m.debayer_method = s)
 RIP_SETTER(rip_set_output_format, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
-           (void)rip::output_format_id(s); if (p->m.out_format != s) p->out_table.dirty = true; p->m.out_format = s)
+           (void)rip::output_format_id(s); if (p->m.out().out_format != s) p->out_table[p->m.selected].dirty = true; p->m.out().out_format = s)
 RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, const double* mean, const double* sd),
            if (!mean || !sd) throw InvalidArgument("null mean or std");
-           rip::check_output_normalization(divisor, mean, sd); p->m.out_divisor = divisor;
-           for (int i = 0; i < 3; i++) { p->m.out_mean[i] = mean[i]; p->m.out_std[i] = sd[i]; } p->out_table.dirty = true)
-RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), rip::check_output_size(width, height); p->m.out_w = width; p->m.out_h = height)
+           rip::check_output_normalization(divisor, mean, sd); p->m.out().out_divisor = divisor;
+           for (int i = 0; i < 3; i++) { p->m.out().out_mean[i] = mean[i]; p->m.out().out_std[i] = sd[i]; } p->out_table[p->m.selected].dirty = true)
+RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), rip::check_output_size(width, height); p->m.out().out_w = width; p->m.out().out_h = height)
 RIP_SETTER(rip_set_output_interpolation, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
-           (void)rip::output_interpolation_id(s); p->m.out_interp = s)
+           (void)rip::output_interpolation_id(s); p->m.out().out_interp = s)
 RIP_SETTER(rip_set_output_roi, (rip_pipeline * p, int x, int y, int width, int height), rip::check_output_roi(x, y, width, height);
-           p->m.roi_x = x; p->m.roi_y = y; p->m.roi_w = width; p->m.roi_h = height)
+           p->m.out().roi_x = x; p->m.out().roi_y = y; p->m.out().roi_w = width; p->m.out().roi_h = height)
 RIP_SETTER(rip_set_output_fit, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
-           (void)rip::output_fit_id(s); p->m.out_fit = s)
+           (void)rip::output_fit_id(s); p->m.out().out_fit = s)
 RIP_SETTER(rip_set_output_pad, (rip_pipeline * p, int b, int g, int r), rip::check_output_pad(b, g, r);
-           p->m.out_pad[0] = b; p->m.out_pad[1] = g; p->m.out_pad[2] = r)
+           p->m.out().out_pad[0] = b; p->m.out().out_pad[1] = g; p->m.out().out_pad[2] = r)
 RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
 RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)
 RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v != 0)
@@ -459,17 +551,17 @@ int rip_get_rect_image_width(const rip_pipeline* p) { return p ? p->m.rect_w : 0
     });                                                            \
   }
 RIP_GET_STRING(rip_get_debayer_method, p->m.debayer_method)
-RIP_GET_STRING(rip_get_output_format, p->m.out_format)
-RIP_GET_STRING(rip_get_output_interpolation, p->m.out_interp)
-RIP_GET_STRING(rip_get_output_fit, p->m.out_fit)
+RIP_GET_STRING(rip_get_output_format, p->m.out().out_format)
+RIP_GET_STRING(rip_get_output_interpolation, p->m.out().out_interp)
+RIP_GET_STRING(rip_get_output_fit, p->m.out().out_fit)
 
 rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, double* mean, double* sd) {
   return guarded(p, [&] {
     need(p);
-    if (divisor) *divisor = p->m.out_divisor;
+    if (divisor) *divisor = p->m.out().out_divisor;
     for (int i = 0; i < 3; i++) {
-      if (mean) mean[i] = p->m.out_mean[i];
-      if (sd) sd[i] = p->m.out_std[i];
+      if (mean) mean[i] = p->m.out().out_mean[i];
+      if (sd) sd[i] = p->m.out().out_std[i];
     }
   });
 }
@@ -477,27 +569,27 @@ rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, 
 rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height) {
   return guarded(p, [&] {
     need(p);
-    if (width) *width = p->m.out_w;
-    if (height) *height = p->m.out_h;
+    if (width) *width = p->m.out().out_w;
+    if (height) *height = p->m.out().out_h;
   });
 }
 
 rip_status rip_get_output_roi(const rip_pipeline* p, int* x, int* y, int* width, int* height) {
   return guarded(p, [&] {
     need(p);
-    if (x) *x = p->m.roi_x;
-    if (y) *y = p->m.roi_y;
-    if (width) *width = p->m.roi_w;
-    if (height) *height = p->m.roi_h;
+    if (x) *x = p->m.out().roi_x;
+    if (y) *y = p->m.out().roi_y;
+    if (width) *width = p->m.out().roi_w;
+    if (height) *height = p->m.out().roi_h;
   });
 }
 
 rip_status rip_get_output_pad(const rip_pipeline* p, int* b, int* g, int* r) {
   return guarded(p, [&] {
     need(p);
-    if (b) *b = p->m.out_pad[0];
-    if (g) *g = p->m.out_pad[1];
-    if (r) *r = p->m.out_pad[2];
+    if (b) *b = p->m.out().out_pad[0];
+    if (g) *g = p->m.out().out_pad[1];
+    if (r) *r = p->m.out().out_pad[2];
   });
 }
 
@@ -506,7 +598,7 @@ rip_status rip_get_output_window(rip_pipeline* p, int rows, int cols, int channe
     need(p);
     if (!encoding) throw InvalidArgument("encoding is null");
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, pl);
+    apply_output_format(p->m, p->m.selected, pl);
     const int src[4] = {pl.win_x, pl.win_y, pl.win_w, pl.win_h}, dst[4] = {pl.pic_x, pl.pic_y, pl.pic_w, pl.pic_h};
     if (src_xywh) std::memcpy(src_xywh, src, sizeof(src));
     if (dst_xywh) std::memcpy(dst_xywh, dst, sizeof(dst));
@@ -529,7 +621,7 @@ rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int c
     need(p);
     if (!encoding) throw InvalidArgument("encoding is null");
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, pl);
+    apply_output_format(p->m, p->m.selected, pl);
     const rip::Modules& m = p->m;
     double k[9], pr[12];
     for (int i = 0; i < 9; i++) k[i] = pl.remap ? m.rect_K[i] : m.dist_K[i];

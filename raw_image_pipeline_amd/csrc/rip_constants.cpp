@@ -334,24 +334,27 @@ void ensure_ccc(rip_pipeline* p, int rows, int cols) {
 
 // The planar formats' table on the device, rebuilt on the host (rip::build_output_table) when the format or the normalisation
 // has changed since the last frame
-void ensure_output_table(rip_pipeline* p, int fmt) {
-  OutputTableConst& t = p->out_table;
+void ensure_output_table(rip_pipeline* p, int head, int fmt) {
+  OutputTableConst& t = p->out_table[head];
   if (!t.dirty) return;
+  const rip::OutputHead& h = p->m.heads[head];
+  t.builds++;
   t.host.resize(768 * (size_t)rip::output_format_elem_bytes(fmt));
-  rip::build_output_table(fmt, p->m.out_divisor, p->m.out_mean, p->m.out_std, t.host.data());
+  rip::build_output_table(fmt, h.out_divisor, h.out_mean, h.out_std, t.host.data());
   upload(p, t.dev, t.host.data(), t.host.size(), 768 * 4);
   HIP_CHECK(hipStreamSynchronize(p->stream));
   t.dirty = false;
 }
 
-// One table set of the resize stage is kept per handle, whichever filter built it: rebuilt by fill(host copy of `bytes` zeroed bytes)
+// One table set of the resize stage is kept per output head, whichever filter built it: rebuilt by fill(host copy of `bytes` zeroed bytes)
 // and uploaded when the key -- (R, C, H, W, kind of table) -- is not the one it was built for.  The upload goes through the handle's
 // pageable copy and waits for the stream, like the other ensure_* functions: a handle that alternates between targets pays that
 // wait on every change.
 template <typename Fill>
-static void ensure_keyed_tables(rip_pipeline* p, const int (&key)[5], size_t bytes, Fill&& fill) {
-  ResizeTableConst& t = p->rsz_tables;
+static void ensure_keyed_tables(rip_pipeline* p, int head, const int (&key)[5], size_t bytes, Fill&& fill) {
+  ResizeTableConst& t = p->rsz_tables[head];
   if (std::memcmp(key, t.key, sizeof(key)) == 0 && t.dev.ptr) return;
+  t.builds++;
   t.host.assign(bytes, 0);
   fill(t.host.data());
   upload(p, t.dev, t.host.data(), bytes);
@@ -361,27 +364,27 @@ static void ensure_keyed_tables(rip_pipeline* p, const int (&key)[5], size_t byt
 
 // The linear tables (rip::build_resize_tables).  One buffer: xofs, alpha (both padded to whole lanes), yofs, beta -- every part starts
 // 16-byte aligned.
-ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, int W) {
+ResizeTables ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W) {
   const size_t wp = rip::resize_table_cols(W), hp = ((size_t)H + 3) & ~(size_t)3;
   const size_t o_alpha = wp * 4, o_yofs = o_alpha + wp * 4, o_beta = o_yofs + hp * 8, bytes = o_beta + hp * 4;
-  ensure_keyed_tables(p, {R, C, H, W, 0}, bytes, [&](uint8_t* h) {
+  ensure_keyed_tables(p, head, {R, C, H, W, 0}, bytes, [&](uint8_t* h) {
     rip::build_resize_tables(R, C, H, W, reinterpret_cast<int32_t*>(h), reinterpret_cast<int16_t*>(h + o_alpha), reinterpret_cast<int32_t*>(h + o_yofs),
-                             reinterpret_cast<int16_t*>(h + o_beta), &p->rsz_tables.area2);
+                             reinterpret_cast<int16_t*>(h + o_beta), &p->rsz_tables[head].area2);
   });
-  const uint8_t* d = p->rsz_tables.dev.as<uint8_t>();
+  const uint8_t* d = p->rsz_tables[head].dev.as<uint8_t>();
   return {reinterpret_cast<const int32_t*>(d), reinterpret_cast<const int16_t*>(d + o_alpha), reinterpret_cast<const int32_t*>(d + o_yofs),
-          reinterpret_cast<const int16_t*>(d + o_beta), p->rsz_tables.area2};
+          reinterpret_cast<const int16_t*>(d + o_beta), p->rsz_tables[head].area2};
 }
 
 // The tables of the area interpolation (rip::build_resize_area_tables) in the same buffer and under the same key, told apart by the
 // key's last entry.  Parts, all of 4-byte entries: xfirst, xcount, xwofs [W], yfirst, ycount, ywofs [H], xweight [C + 2 W],
 // yweight [R + 2 H]; wofs is the running sum of count.
-AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W) {
+AreaTables ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, int W) {
   const size_t o_y = (size_t)W * 3, o_xw = o_y + (size_t)H * 3, o_yw = o_xw + (size_t)C + 2 * (size_t)W, words = o_yw + (size_t)R + 2 * (size_t)H;
-  ensure_keyed_tables(p, {R, C, H, W, 1}, words * 4, [&](uint8_t* bytes) {
+  ensure_keyed_tables(p, head, {R, C, H, W, 1}, words * 4, [&](uint8_t* bytes) {
     int32_t* h = reinterpret_cast<int32_t*>(bytes);
     rip::build_resize_area_tables(R, C, H, W, h, h + W, reinterpret_cast<float*>(h + o_xw), h + o_y, h + o_y + H, reinterpret_cast<float*>(h + o_yw),
-                                  &p->rsz_tables.whole, &p->rsz_tables.scale);
+                                  &p->rsz_tables[head].whole, &p->rsz_tables[head].scale);
     for (int axis = 0; axis < 2; axis++) {
       const int d = axis ? H : W;
       const int32_t* count = h + (axis ? o_y : 0) + d;
@@ -393,20 +396,20 @@ AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W) {
       }
     }
   });
-  const int32_t* d = p->rsz_tables.dev.as<int32_t>();
+  const int32_t* d = p->rsz_tables[head].dev.as<int32_t>();
   return {d, d + W, d + 2 * (size_t)W, d + o_y, d + o_y + H, d + o_y + 2 * (size_t)H, reinterpret_cast<const float*>(d + o_xw),
-          reinterpret_cast<const float*>(d + o_yw), p->rsz_tables.whole, p->rsz_tables.scale};
+          reinterpret_cast<const float*>(d + o_yw), p->rsz_tables[head].whole, p->rsz_tables[head].scale};
 }
 
 // The tables of an antialiased filter (rip::build_resize_aa_tables) in the same buffer and under the same key, whose last entry is
 // the filter.  Parts: xfirst, xcount, xwofs [W], yfirst, ycount, ywofs [H] of 4-byte entries, then the int16 weights of the columns
 // and of the rows, each part of its capacity rounded up to an even count.
-AaTables ensure_aa_tables(rip_pipeline* p, int filter, int R, int C, int H, int W) {
+AaTables ensure_aa_tables(rip_pipeline* p, int head, int filter, int R, int C, int H, int W) {
   const size_t o_y = (size_t)W * 3, o_xw = o_y + (size_t)H * 3;  // in 4-byte entries
   const size_t cap_x = (rip::resize_aa_weight_capacity(filter, C, W) + 1) & ~(size_t)1, cap_y = (rip::resize_aa_weight_capacity(filter, R, H) + 1) & ~(size_t)1;
   const size_t bytes = o_xw * 4 + (cap_x + cap_y) * 2;
-  ResizeTableConst& t = p->rsz_tables;
-  ensure_keyed_tables(p, {R, C, H, W, filter}, bytes, [&](uint8_t* raw) {
+  ResizeTableConst& t = p->rsz_tables[head];
+  ensure_keyed_tables(p, head, {R, C, H, W, filter}, bytes, [&](uint8_t* raw) {
     int32_t* h = reinterpret_cast<int32_t*>(raw);
     int16_t* wts = reinterpret_cast<int16_t*>(raw + o_xw * 4);
     rip::build_resize_aa_tables(filter, R, C, H, W, h, h + W, h + 2 * (size_t)W, wts, &t.aa_xprec, h + o_y, h + o_y + H, h + o_y + 2 * (size_t)H, wts + cap_x,

@@ -20,6 +20,7 @@
 #include "rip_aa.hpp"
 #include "rip_area.hpp"
 #include "rip_fit.hpp"
+#include "rip_heads.hpp"
 #include "rip_resize.hpp"
 
 namespace rip {
@@ -126,7 +127,8 @@ struct Plan {
   int stage_bits = 0;
   std::string encoding_out;
   // the output stage (rip_set_output_format; filled in by apply_output_format, everything above describes the pipeline's own image)
-  bool fmt_active = false;        // a format other than "native" is set
+  int head = 0;                   // the output head whose settings these are (rip_select_output_head): its tables are the ones the launches read
+  bool fmt_active = false;      // a format other than "native" is set
   int out_fmt = rip::OUT_NATIVE;  // the conversion that runs behind the last kernel; OUT_NATIVE: none (mono8 of a one-channel image included)
   int dl_channels = 3;            // what the frame calls deliver: channels (planes), bytes per element, planar or interleaved
   int dl_elem_bytes = 1;
@@ -269,15 +271,18 @@ struct CccGeomLayout {
   static bool area_fast(int rows, int cols) { return rows == 2 * H && cols == 2 * W; }
 };
 // output stage (rip_set_output_format): the planar formats' 3 x 256 table, rebuilt and uploaded when the format or the normalisation changes
+// -- one per output head (rip_set_output_heads), so that alternating heads do not rebuild each other's table
 struct OutputTableConst {
   std::vector<uint8_t> host;
   DevBuf dev;
   bool dirty = true;
+  int builds = 0;  // how often the table was rebuilt and uploaded (rip_debug_output_head_info)
 };
 // resize stage (rip_set_output_size): the tables of rip::build_resize_tables or, under the area interpolation,
 // rip::build_resize_area_tables, or, under an antialiased filter, rip::build_resize_aa_tables, rebuilt and uploaded when the
-// (R, C, H, W, kind of table: the filter, one of four) they were built for changes
+// (R, C, H, W, kind of table: the filter, one of four) they were built for changes -- one set per output head
 struct ResizeTableConst {
+  int builds = 0;  // how often a table set was built and uploaded (rip_debug_output_head_info)
   std::vector<uint8_t> host;
   DevBuf dev;
   int key[5] = {0, 0, 0, 0, 0};
@@ -311,8 +316,13 @@ struct rip_pipeline {
   rip::api::TableConst tables;
   rip::api::VignetteConst vignette;
   rip::api::CccConst ccc;
-  rip::api::OutputTableConst out_table;
-  rip::api::ResizeTableConst rsz_tables;
+  rip::api::OutputTableConst out_table[rip::kMaxOutputHeads];   // indexed by output head
+  rip::api::ResizeTableConst rsz_tables[rip::kMaxOutputHeads];
+  // what the last frame call that delivered head k did for it (rip_debug_output_head_info): the chain wrote it directly -- also
+  // true of an identity head of a single-output call -- or head_copy_kernel copied it from the staging image
+  struct HeadRecord {
+    int direct_write = 0, copied = 0;
+  } head_record[rip::kMaxOutputHeads];
   // per-batch scratch.  d_stats.clean_bytes: the prefix known to hold zeroed FrameStats records (the grey-world / pca statistics
   // kernels clean up after themselves).  d_hist.clean_bytes: the leading bytes known to be zero -- the ccc estimator's global-atomic
   // histogram (small batches) hands its counters back zeroed, so a stream of single frames pays for one memset, not one per frame
@@ -345,6 +355,7 @@ struct rip_pipeline {
   rip::LaunchLog launch_log;
   // host-apply staging and last-frame taps
   rip::api::DevBuf d_in, d_out, d_tap_deb, d_tap_col, d_dbg;
+  rip::api::DevBuf d_head_out[rip::kMaxOutputHeads];  // rip_apply_heads: the delivered frame of every requested head, tightly packed
   int last_rows[3] = {0, 0, 0}, last_cols[3] = {0, 0, 0}, last_cn[3] = {0, 0, 0};
   bool last_valid[3] = {false, false, false};
   rip::api::DevBuf* last_buf[3] = {nullptr, nullptr, nullptr};
@@ -404,7 +415,7 @@ int parse_packed(const std::string& e, int& ry, int& rx);
 size_t row_bytes(const Plan& pl, int cols, int channels);
 size_t delivered_bytes(const Plan& pl);
 Plan make_plan(const rip::Modules& m, int rows, int cols, int channels, const std::string& encoding);
-void apply_output_format(const rip::Modules& m, Plan& pl);
+void apply_output_format(const rip::Modules& m, int head, Plan& pl);
 FrameView tight_output_view(const Plan& pl, void* d_out);
 FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, size_t out_frame_stride);
 
@@ -418,7 +429,7 @@ int ensure_chain_items(rip_pipeline* p, int rows, int cols, int flip_angle);
 void ensure_tables(rip_pipeline* p);
 void ensure_vignette(rip_pipeline* p, int rows, int cols);
 void ensure_ccc(rip_pipeline* p, int rows, int cols);
-void ensure_output_table(rip_pipeline* p, int fmt);
+void ensure_output_table(rip_pipeline* p, int head, int fmt);
 // the resize stage's tables as the kernels' parameter blocks take them (device pointers into ResizeTableConst::dev)
 struct ResizeTables {
   const int32_t* xofs;
@@ -433,8 +444,8 @@ struct AreaTables {
   int whole;
   float scale;
 };
-ResizeTables ensure_resize_tables(rip_pipeline* p, int R, int C, int H, int W);
-AreaTables ensure_area_tables(rip_pipeline* p, int R, int C, int H, int W);
+ResizeTables ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W);
+AreaTables ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, int W);
 struct AaTables {
   const int32_t *xfirst, *xcount, *xwofs, *yfirst, *ycount, *ywofs;
   const int16_t *xweight, *yweight;
@@ -442,12 +453,42 @@ struct AaTables {
   int tile_rows[2], lds_rows[2];  // for 1 and for 3 channels
 };
 // filter: 2 (linear_aa) or 3 (cubic_aa), rip::output_interpolation_id's numbers
-AaTables ensure_aa_tables(rip_pipeline* p, int filter, int R, int C, int H, int W);
+AaTables ensure_aa_tables(rip_pipeline* p, int head, int filter, int R, int C, int H, int W);
 
 // rip_batch.cpp
 size_t fmt_pitch(const Plan& pl);
 void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb = false);
 void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n);
+// Several delivered images from one run of the chain (rip_apply_device_heads): plans[k] / dsts[k] for every head k < n_heads, with
+// dsts[k].ptr null for a head that is not requested (its plan is not looked at).  pl: make_plan's, the pipeline's own image.
+void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const FrameView* dsts, int n_heads, ConstFrameView src, Taps taps, int n);
+// the heads calls' checks behind make_plan (rip.h rip_apply_device_heads, steps 5 to 7): fills plans[k] and views[k] of every
+// requested head (requested[k]; the others are neither planned nor validated); view_of(k, plan) resolves head k's buffer with its
+// own refusals.  The messages of step 5 are prefixed "output head <k>: " and keep their status.  Nothing is enqueued here.
+template <typename ViewOf>
+void plan_heads(const rip::Modules& m, const Plan& pl, int n_heads, const bool* requested, bool any_tap, Plan* plans, FrameView* views, ViewOf&& view_of) {
+  int n_requested = 0;
+  for (int k = 0; k < n_heads; k++) {
+    views[k] = FrameView{nullptr, 0, 0, 0, 0};
+    if (!requested[k]) continue;
+    n_requested++;
+    const std::string prefix = "output head " + std::to_string(k) + ": ";
+    try {
+      plans[k] = pl;
+      apply_output_format(m, k, plans[k]);
+      views[k] = view_of(k, plans[k]);
+    } catch (const AssertError& e) {
+      throw AssertError(prefix + e.what());
+    } catch (const CapacityError& e) {
+      throw CapacityError(prefix + e.what());
+    } catch (const std::invalid_argument& e) {
+      throw InvalidArgument(prefix + e.what());
+    }
+  }
+  if (pl.out_elem_bytes == 2 && n_requested > 1)
+    throw InvalidArgument("16-bit Bayer frames without a 16-bit range give bgr16, which one output head at a time can deliver; " + std::to_string(n_requested) + " were requested");
+  if (pl.out_elem_bytes == 2 && any_tap) throw InvalidArgument("16-bit Bayer frames have no taps");
+}
 void write_debug_dumps(rip_pipeline* p, const Plan& pl, ConstFrameView src, const uint8_t* final_image);
 
 }  // namespace rip::api

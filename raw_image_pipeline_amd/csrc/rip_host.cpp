@@ -287,18 +287,11 @@ void set_enhancer_gains_from_config(Modules& m, double hue, double sat, double v
   m.ce_hue_gain = val;
 }
 
-void params_from_node(Modules& m, const YamlNode& node) {
-  // extension key debayer: method: (not in the reference's files).  Checked before anything is assigned: an unknown method
-  // fails the load and leaves every parameter as it was.
-  const std::string debayer_method = node["debayer"].get("method", std::string("bilinear"));
-  check_debayer_method(debayer_method);
-  // extension keys debayer: accept_16bit: / black_level: / white_level: (rip_set_debayer_16bit, rip_set_debayer_16bit_range);
-  // loadParams re-creates the modules, so absent keys mean off.  An invalid range fails the load like an unknown method.
-  const int black_level = node["debayer"].get("black_level", 0), white_level = node["debayer"].get("white_level", 0);
-  check_debayer_16bit_range(black_level, white_level);
+// One section of output settings (output:, output_1: .. output_7:; `sec` names it in the messages): every key checked before anything
+// is handed back, so an invalid value fails the load and leaves every parameter as it was.
+OutputHead output_head_from_node(const YamlNode& o, const std::string& sec) {
   // extension keys output: format: / divisor: / mean: [3] / std: [3] (rip_set_output_format, rip_set_output_normalization);
   // absent keys mean the defaults, an invalid value fails the load like an unknown debayer method
-  const YamlNode& o = node["output"];
   const std::string out_format = o.get("format", std::string("native"));
   (void)output_format_id(out_format);
   const double out_divisor = o.get("divisor", 255.0);
@@ -307,7 +300,7 @@ void params_from_node(Modules& m, const YamlNode& node) {
     const char* key = which ? "std" : "mean";
     if (!o[key].defined()) continue;
     const std::vector<double> v = o.get_vector(key);
-    if (v.size() != 3) throw std::invalid_argument(std::string("output: ") + key + ": a sequence of 3 numbers is expected");
+    if (v.size() != 3) throw std::invalid_argument(sec + ": " + key + ": a sequence of 3 numbers is expected");
     for (int i = 0; i < 3; i++) (which ? out_std : out_mean)[i] = v[i];
   }
   check_output_normalization(out_divisor, out_mean, out_std);
@@ -316,7 +309,7 @@ void params_from_node(Modules& m, const YamlNode& node) {
   if (o["size"].defined()) {
     const std::vector<double> v = o.get_vector("size");
     if (v.size() != 2 || !(v[0] >= 0 && v[0] <= 16384 && v[1] >= 0 && v[1] <= 16384) || v[0] != std::floor(v[0]) || v[1] != std::floor(v[1]))
-      throw std::invalid_argument("output: size: a sequence [width, height] of two integers in 1..16384 (or [0, 0]) is expected");
+      throw std::invalid_argument(sec + ": size: a sequence [width, height] of two integers in 1..16384 (or [0, 0]) is expected");
     out_w = (int)v[0];
     out_h = (int)v[1];
     check_output_size(out_w, out_h);
@@ -325,7 +318,7 @@ void params_from_node(Modules& m, const YamlNode& node) {
   const std::string out_interp = o.get("interpolation", std::string("linear"));
   (void)output_interpolation_id(out_interp);
   if (o["interpolation"].defined() && o["interpolation"].kind != YamlNode::Scalar)
-    throw std::invalid_argument("output: interpolation: one word is expected, \"linear\" or \"area\", \"linear_aa\" or \"cubic_aa\"");
+    throw std::invalid_argument(sec + ": interpolation: one word is expected, \"linear\" or \"area\", \"linear_aa\" or \"cubic_aa\"");
   // extension keys output: roi: [x, y, w, h] / fit: stretch | letterbox | crop / pad: [b, g, r] (rip_set_output_roi,
   // rip_set_output_fit, rip_set_output_pad); absent keys mean the defaults
   int roi[4] = {0, 0, 0, 0}, pad[3] = {114, 114, 114};
@@ -337,8 +330,8 @@ void params_from_node(Modules& m, const YamlNode& node) {
     bool ok = v.size() == n;
     for (size_t i = 0; ok && i < n; i++) ok = v[i] >= 0 && v[i] <= (1 << 22) && v[i] == std::floor(v[i]);
     if (!ok)
-      throw std::invalid_argument(which ? "output: pad: a sequence [b, g, r] of three integers in 0..255 is expected"
-                                        : "output: roi: a sequence [x, y, width, height] of four integers is expected, x and y at least 0, width and height in 1..16384 (or four zeros)");
+      throw std::invalid_argument(which ? sec + ": pad: a sequence [b, g, r] of three integers in 0..255 is expected"
+                                        : sec + ": roi: a sequence [x, y, width, height] of four integers is expected, x and y at least 0, width and height in 1..16384 (or four zeros)");
     for (size_t i = 0; i < n; i++) (which ? pad : roi)[i] = (int)v[i];
   }
   check_output_roi(roi[0], roi[1], roi[2], roi[3]);
@@ -346,16 +339,46 @@ void params_from_node(Modules& m, const YamlNode& node) {
   const std::string out_fit = o.get("fit", std::string("stretch"));
   (void)output_fit_id(out_fit);
   if (o["fit"].defined() && o["fit"].kind != YamlNode::Scalar)
-    throw std::invalid_argument("output: fit: one word is expected, \"stretch\", \"letterbox\" or \"crop\"");
-  m.roi_x = roi[0], m.roi_y = roi[1], m.roi_w = roi[2], m.roi_h = roi[3];
-  m.out_fit = out_fit;
-  for (int i = 0; i < 3; i++) m.out_pad[i] = pad[i];
-  m.out_w = out_w;
-  m.out_h = out_h;
-  m.out_interp = out_interp;
-  m.out_format = out_format;
-  m.out_divisor = out_divisor;
-  for (int i = 0; i < 3; i++) m.out_mean[i] = out_mean[i], m.out_std[i] = out_std[i];
+    throw std::invalid_argument(sec + ": fit: one word is expected, \"stretch\", \"letterbox\" or \"crop\"");
+  OutputHead h;
+  h.roi_x = roi[0], h.roi_y = roi[1], h.roi_w = roi[2], h.roi_h = roi[3];
+  h.out_fit = out_fit;
+  for (int i = 0; i < 3; i++) h.out_pad[i] = pad[i];
+  h.out_w = out_w;
+  h.out_h = out_h;
+  h.out_interp = out_interp;
+  h.out_format = out_format;
+  h.out_divisor = out_divisor;
+  for (int i = 0; i < 3; i++) h.out_mean[i] = out_mean[i], h.out_std[i] = out_std[i];
+  return h;
+}
+
+void params_from_node(Modules& m, const YamlNode& node) {
+  // extension key debayer: method: (not in the reference's files).  Checked before anything is assigned: an unknown method
+  // fails the load and leaves every parameter as it was.
+  const std::string debayer_method = node["debayer"].get("method", std::string("bilinear"));
+  check_debayer_method(debayer_method);
+  // extension keys debayer: accept_16bit: / black_level: / white_level: (rip_set_debayer_16bit, rip_set_debayer_16bit_range);
+  // loadParams re-creates the modules, so absent keys mean off.  An invalid range fails the load like an unknown method.
+  const int black_level = node["debayer"].get("black_level", 0), white_level = node["debayer"].get("white_level", 0);
+  check_debayer_16bit_range(black_level, white_level);
+  // extension keys output: ... (output_head_from_node) and the further heads' sections output_1: .. output_7: with the same keys
+  // (rip_set_output_heads): n = 1 + the largest k present, sections absent in between hold the defaults, head 0 is selected
+  OutputHead heads[kMaxOutputHeads];
+  int n_heads = 1;
+  heads[0] = output_head_from_node(node["output"], "output");
+  for (const auto& kv : node.map) {
+    if (kv.first.compare(0, 7, "output_") != 0) continue;
+    const std::string idx = kv.first.substr(7);
+    if (idx.size() != 1 || idx[0] < '1' || idx[0] > '0' + kMaxOutputHeads - 1)
+      throw std::invalid_argument(kv.first + ": the sections of further output heads are output_1 .. output_" + std::to_string(kMaxOutputHeads - 1));
+    const int k = idx[0] - '0';
+    heads[k] = output_head_from_node(kv.second, kv.first);
+    n_heads = std::max(n_heads, k + 1);
+  }
+  for (int k = 0; k < kMaxOutputHeads; k++) m.heads[k] = heads[k];
+  m.n_heads = n_heads;
+  m.selected = 0;
   m.debayer_method = debayer_method;
   m.debayer_16bit = node["debayer"].get("accept_16bit", false);
   m.raw16_black = black_level;

@@ -45,18 +45,10 @@ bool file_exists(const std::string& path);
 // ---------------------------------------------------------------------------------------------
 // Module parameters.  Field comments cite the reference member they mirror.
 // ---------------------------------------------------------------------------------------------
-struct Modules {
-  bool use_gpu = false, debug = false;
-  // DebayerModule (debayer.hpp:70-72): enable flag stored but ignored by apply (:38-40)
-  bool debayer_enabled = true;
-  std::string debayer_encoding = "auto";
-  bool debayer_16bit = false;  // extension (rip_set_debayer_16bit): accept bayer_*16 instead of throwing like the reference
-  // extension (rip_set_debayer_16bit_range): black and white level of bayer_*16 frames; (0, 0) = off (bgr16 out, no other
-  // stage); 0 <= black < white <= 65535: narrowed to 8 bits right after the demosaic, then the whole chain (PARITY.md)
-  int raw16_black = 0, raw16_white = 0;
-  // extension (rip_set_debayer_method): "bilinear" (the CPU path, debayer.cpp:49-70) or "mht" (Malvar-He-Cutler, what the
-  // CUDA path's cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT) computes, debayer.cpp:93-108)
-  std::string debayer_method = "bilinear";
+// One output head (rip_set_output_heads; PARITY.md "Output heads"): one complete set of the output stage's settings.  A handle holds
+// up to kMaxOutputHeads of them; head 0 is the output of a handle that never asked for more.
+constexpr int kMaxOutputHeads = 8;
+struct OutputHead {
   // extension (rip_set_output_format, rip_set_output_normalization): the output stage behind the last module -- the format the
   // frame calls deliver ("native": the pipeline's own image) and the normalisation of the planar float formats, mean / std in
   // the order of the format's planes
@@ -72,6 +64,26 @@ struct Modules {
   int roi_x = 0, roi_y = 0, roi_w = 0, roi_h = 0;
   std::string out_fit = "stretch";
   int out_pad[3] = {114, 114, 114};
+};
+
+struct Modules {
+  bool use_gpu = false, debug = false;
+  // DebayerModule (debayer.hpp:70-72): enable flag stored but ignored by apply (:38-40)
+  bool debayer_enabled = true;
+  std::string debayer_encoding = "auto";
+  bool debayer_16bit = false;  // extension (rip_set_debayer_16bit): accept bayer_*16 instead of throwing like the reference
+  // extension (rip_set_debayer_16bit_range): black and white level of bayer_*16 frames; (0, 0) = off (bgr16 out, no other
+  // stage); 0 <= black < white <= 65535: narrowed to 8 bits right after the demosaic, then the whole chain (PARITY.md)
+  int raw16_black = 0, raw16_white = 0;
+  // extension (rip_set_debayer_method): "bilinear" (the CPU path, debayer.cpp:49-70) or "mht" (Malvar-He-Cutler, what the
+  // CUDA path's cv::cuda::demosaicing(..., COLOR_Bayer**2BGR_MHT) computes, debayer.cpp:93-108)
+  std::string debayer_method = "bilinear";
+  // extension (rip_set_output_heads, rip_select_output_head): the output stage's settings, one set per head; heads at and beyond
+  // n_heads hold the defaults.  The single-output calls read and write the selected head through out().
+  OutputHead heads[kMaxOutputHeads];
+  int n_heads = 1, selected = 0;
+  OutputHead& out() { return heads[selected]; }
+  const OutputHead& out() const { return heads[selected]; }
   // FlipModule (flip.hpp:63-66)
   bool flip_enabled = false;
   int flip_angle = 0;

@@ -145,7 +145,10 @@ Plan make_plan(const rip::Modules& m, int rows, int cols, int channels, const st
 
 // The output stage on top of a plan (rip_set_output_format): what the frame calls and rip_query_output deliver.  The taps, the
 // debug dumps and rip_query_taps stay with make_plan's image.  Throws before anything is enqueued where the format does not apply.
-void apply_output_format(const rip::Modules& m, Plan& pl) {
+// head: whose settings (rip_set_output_heads); the single-output calls pass the selected one.
+void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
+  const rip::OutputHead& m = mods.heads[head];
+  pl.head = head;
   pl.dl_channels = pl.channels;
   pl.dl_elem_bytes = pl.out_elem_bytes;
   // the resize stage (rip_set_output_size) sits between F and the format: the delivered geometry is the target's

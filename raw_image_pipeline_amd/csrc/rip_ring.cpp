@@ -214,7 +214,7 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     need_device(p);
     if (!image || !encoding || !ticket) throw InvalidArgument("null buffer, encoding or ticket");
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, pl);
+    apply_output_format(p->m, p->m.selected, pl);
     const HostFrameLayout L(p, pl, rows, cols, channels, step);
     {  // destinations given by the caller (rip_submit_to): checked before anything is enqueued or any slot is touched
       if (ext_out && ext_out_capacity < L.out_bytes) throw CapacityError("rip_submit_to: result buffer too small: need " + std::to_string(L.out_bytes) + " bytes");
@@ -330,7 +330,7 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     need_device(p);
     if (!image || !out || !encoding) throw InvalidArgument("null buffer or encoding");
     Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, pl);
+    apply_output_format(p->m, p->m.selected, pl);
     DeviceGuard device_guard(p->device);
     const HostFrameLayout L(p, pl, rows, cols, channels, step);
     L.check_step(pl);
@@ -367,6 +367,59 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     if (out_cols) *out_cols = pl.dl_cols;
     if (out_channels) *out_channels = pl.dl_channels;
     if (encoding_out) copy_string(pl.encoding_out, encoding_out, 32);
+  });
+}
+
+// rip_apply with several delivered images: one upload, one run of the chain, one download per requested head.  No debug dumps are
+// written from here (rip_set_debug is for the single-output calls: the dumps re-run the chain per module).
+rip_status rip_apply_heads(rip_pipeline* p, const uint8_t* image, int rows, int cols, int channels, size_t step, const char* encoding,
+                           uint8_t* const* outs, const size_t* out_capacities, int n_heads, int* out_rows, int* out_cols, int* out_channels) {
+  return guarded(p, [&] {
+    need_device(p);
+    if (!image || !outs || !out_capacities || !encoding) throw InvalidArgument("null buffer, heads or encoding");
+    if (n_heads != p->m.n_heads)
+      throw InvalidArgument("rip_apply_heads: " + std::to_string(n_heads) + " head buffers for a handle with " + std::to_string(p->m.n_heads) + " output heads");
+    bool requested[RIP_MAX_OUTPUT_HEADS] = {};
+    bool any = false;
+    for (int k = 0; k < n_heads; k++) any |= requested[k] = outs[k] != nullptr;
+    if (!any) throw InvalidArgument("rip_apply_heads: no head is requested (every output buffer is null)");
+    const Plan pl = make_plan(p->m, rows, cols, channels, encoding);
+    const HostFrameLayout L(p, pl, rows, cols, channels, step);
+    Plan plans[RIP_MAX_OUTPUT_HEADS];
+    FrameView dsts[RIP_MAX_OUTPUT_HEADS];
+    // the delivered image of a head, tightly packed behind a fixed 16-byte aligned address: the checks need no allocation, the
+    // buffers are reserved once every head has passed
+    plan_heads(p->m, pl, n_heads, requested, false, plans, dsts, [&](int k, const Plan& hp) {
+      if (out_capacities[k] < delivered_bytes(hp)) throw CapacityError("output buffer too small: need " + std::to_string(delivered_bytes(hp)) + " bytes");
+      return HostFrameLayout::delivered(hp, reinterpret_cast<void*>(uintptr_t(4096)));
+    });
+    L.check_step(pl);
+    DeviceGuard device_guard(p->device);
+    p->d_in.reserve(L.in_bytes);
+    for (int k = 0; k < n_heads; k++) {
+      if (!requested[k]) continue;
+      p->d_head_out[k].reserve(delivered_bytes(plans[k]));
+      dsts[k].ptr = p->d_head_out[k].as<uint8_t>();
+    }
+    if (L.keep_deb) p->d_tap_deb.reserve(L.mid_bytes);
+    if (L.keep_col) p->d_tap_col.reserve(L.mid_bytes);
+    const Taps taps = {L.keep_deb ? p->d_tap_deb.as<uint8_t>() : nullptr, L.keep_col ? p->d_tap_col.as<uint8_t>() : nullptr};
+    const ConstFrameView src = L.staged(p->d_in.ptr, rows, cols);
+    HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, L.in_pitch, image, L.step, L.in_row, (size_t)rows, hipMemcpyHostToDevice, p->stream));
+    run_batch_heads(p, pl, plans, dsts, n_heads, src, taps, 1);
+    for (int k = 0; k < n_heads; k++)
+      if (requested[k]) HIP_CHECK(hipMemcpyAsync(outs[k], p->d_head_out[k].ptr, delivered_bytes(plans[k]), hipMemcpyDeviceToHost, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+    for (int i = 0; i < 3; i++) p->last_valid[i] = false;
+    remember_last(p, RIP_IMAGE_DEBAYERED, &p->d_tap_deb, nullptr, pl.mid_rows, pl.mid_cols, pl.channels, L.keep_deb);
+    remember_last(p, RIP_IMAGE_COLOR, &p->d_tap_col, nullptr, pl.mid_rows, pl.mid_cols, pl.channels, L.keep_col);
+    // the delivered buffers are the results: no PROCESSED image
+    remember_last(p, RIP_IMAGE_PROCESSED, &p->d_out, nullptr, pl.out_rows, pl.out_cols, pl.channels, false);
+    for (int k = 0; k < n_heads; k++) {
+      if (out_rows) out_rows[k] = requested[k] ? plans[k].dl_rows : 0;
+      if (out_cols) out_cols[k] = requested[k] ? plans[k].dl_cols : 0;
+      if (out_channels) out_channels[k] = requested[k] ? plans[k].dl_channels : 0;
+    }
   });
 }
 

@@ -54,6 +54,11 @@ def _delivered(rows, cols, channels, encoding):
     return ((rows, cols) if channels == 1 else (rows, cols, channels)), np.dtype(dtype)
 
 
+class _HeadBuffer(C.Structure):
+    """rip_head_buffer (include/rip.h)."""
+    _fields_ = [("d_out", C.c_void_p), ("out_step", C.c_size_t), ("out_frame_stride", C.c_size_t)]
+
+
 class RipError(RuntimeError):
     """HIP/device failure (RIP_ERR_DEVICE, RIP_ERR_CAPACITY)."""
 
@@ -402,22 +407,9 @@ class RawImagePipeline:
     def set_ring_depth(self, depth):
         self._call("rip_set_ring_depth", int(depth))
 
-    def apply_device(self, frames, encoding, out=None, tap_debayered=None, tap_color=None, width=None):
-        """Device-resident batch (rip_apply_device).  ``frames``: uint8 CUDA tensor [n, rows, cols]
-        or [n, rows, cols, c] (torch) already in HBM; returns the output tensor [n, R, C(, 3)].
-        Asynchronous on the handle's stream.
-
-        bayer_*16 frames (``set_debayer_16bit``): the uint8 view [n, rows, cols * 2] of the uint16 rows, pitches in bytes.
-        With a 16-bit range (``set_debayer_16bit_range``) the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be
-        given; without one it is bgr16 as bytes, [n, R, C, 6].
-
-        Packed Bayer encodings: [n, rows, row bytes] uint8 tensors, ``width`` pixels per row (default
-        ``8 * row_bytes // bits``); the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be given.
-
-        Under an output format (``set_output_format``) the result is uint8 [n, R, C, 3] (rgb8) / [n, R, C] (mono8) or float32 /
-        float16 / bfloat16 [n, 3, R, C]; ``out`` may then be a strided view whose innermost elements are contiguous: its row
-        pitch and frame stride are handed on as rip_apply_device's out_step / out_frame_stride (a planar view's planes must lie
-        ``rows`` row pitches apart)."""
+    @staticmethod
+    def _device_frames_geometry(frames, encoding, width):
+        """(n, rows, cols, channels, row pitch, frame stride) of a device batch as apply_device takes it."""
         import torch
         if frames.dtype != torch.uint8 or not frames.is_cuda:
             raise ValueError("frames must be a uint8 CUDA tensor")
@@ -449,6 +441,26 @@ class RawImagePipeline:
             raise ValueError("pixels must be contiguous")
         in_step = frames.stride(1)
         in_frame = frames.stride(0) if n > 1 else in_step * rows
+        return n, rows, cols, cn, in_step, in_frame
+
+    def apply_device(self, frames, encoding, out=None, tap_debayered=None, tap_color=None, width=None):
+        """Device-resident batch (rip_apply_device).  ``frames``: uint8 CUDA tensor [n, rows, cols]
+        or [n, rows, cols, c] (torch) already in HBM; returns the output tensor [n, R, C(, 3)].
+        Asynchronous on the handle's stream.
+
+        bayer_*16 frames (``set_debayer_16bit``): the uint8 view [n, rows, cols * 2] of the uint16 rows, pitches in bytes.
+        With a 16-bit range (``set_debayer_16bit_range``) the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be
+        given; without one it is bgr16 as bytes, [n, R, C, 6].
+
+        Packed Bayer encodings: [n, rows, row bytes] uint8 tensors, ``width`` pixels per row (default
+        ``8 * row_bytes // bits``); the result is the ordinary uint8 [n, R, C, 3] tensor and taps may be given.
+
+        Under an output format (``set_output_format``) the result is uint8 [n, R, C, 3] (rgb8) / [n, R, C] (mono8) or float32 /
+        float16 / bfloat16 [n, 3, R, C]; ``out`` may then be a strided view whose innermost elements are contiguous: its row
+        pitch and frame stride are handed on as rip_apply_device's out_step / out_frame_stride (a planar view's planes must lie
+        ``rows`` row pitches apart)."""
+        import torch
+        n, rows, cols, cn, in_step, in_frame = self._device_frames_geometry(frames, encoding, width)
         orows, ocols, ocn, enc = self.query_output(rows, cols, cn, encoding)
         out_step = out_frame = 0
         if self._output_format != "native" and enc in OUTPUT_FORMATS:
@@ -501,6 +513,145 @@ class RawImagePipeline:
         self.last_encoding = enc
         return out
 
+    # ---- output heads (rip_set_output_heads; no counterpart in the reference's binding) -------------------------------
+    def set_output_heads(self, n):
+        """How many output heads the handle has, 1..8 (include/rip.h rip_set_output_heads): each is one complete set of the output
+        settings; heads at and beyond ``n`` go back to the defaults and a selection at or beyond ``n`` becomes 0."""
+        self._call("rip_set_output_heads", int(n))
+        self._output_format = self.get_output_format()
+
+    def get_output_heads(self):
+        n = C.c_int()
+        self._call("rip_get_output_heads", C.byref(n))
+        return n.value
+
+    def select_output_head(self, head):
+        """The head every single-output setter, getter, query and frame call addresses from now on (rip_select_output_head)."""
+        self._call("rip_select_output_head", int(head))
+        self._output_format = self.get_output_format()
+
+    def get_selected_output_head(self):
+        h = C.c_int()
+        self._call("rip_get_selected_output_head", C.byref(h))
+        return h.value
+
+    def debug_output_head_info(self, head):
+        """(table builds, direct write, copied) of a head (rip_debug_output_head_info)."""
+        b, d, c = C.c_int(), C.c_int(), C.c_int()
+        self._call("rip_debug_output_head_info", int(head), C.byref(b), C.byref(d), C.byref(c))
+        return b.value, d.value, c.value
+
+    def _head_queries(self, heads, rows, cols, cn, encoding):
+        """query_output of every head in ``heads`` (None elsewhere), each under its own selection; the selection is put back."""
+        n = self.get_output_heads()
+        was = self.get_selected_output_head()
+        info = [None] * n
+        try:
+            for k in heads:
+                self._call("rip_select_output_head", int(k))
+                try:
+                    info[k] = self.query_output(rows, cols, cn, encoding) + (self.get_output_format(),)
+                except (ValueError, RipError) as e:  # named as the heads calls of the C ABI name it
+                    raise type(e)("output head %d: %s" % (k, e)) from None
+        finally:
+            self._call("rip_select_output_head", was)
+        return info
+
+    def apply_device_heads(self, frames, encoding, heads=None, outs=None, tap_debayered=None, tap_color=None, width=None):
+        """Device-resident batch, one result per requested output head from one run of the chain (rip_apply_device_heads).
+        ``heads``: the indices to deliver (default: all); ``outs``: a list with one entry per head of the handle, a tensor to
+        write into or None.  Returns a list with one tensor per head, None for heads not requested; dtype and shape of each
+        follow ``apply_device``'s rules for that head's settings.  A given tensor may be a strided view whose innermost elements
+        are contiguous (planes of a planar view ``rows`` row pitches apart)."""
+        import torch
+        n, rows, cols, cn, in_step, in_frame = self._device_frames_geometry(frames, encoding, width)
+        n_heads = self.get_output_heads()
+        wanted = sorted(set(range(n_heads) if heads is None else [int(k) for k in heads]))
+        if not wanted or wanted[0] < 0 or wanted[-1] >= n_heads:
+            raise ValueError("heads must name at least one of the handle's heads 0..%d" % (n_heads - 1))
+        if outs is not None and len(outs) != n_heads:
+            raise ValueError("outs must have one entry per head of the handle (%d)" % n_heads)
+        info = self._head_queries(wanted, rows, cols, cn, encoding)
+        result = [None] * n_heads
+        bufs = (_HeadBuffer * n_heads)()
+        for k in wanted:
+            orows, ocols, ocn, enc, fmt = info[k]
+            out = outs[k] if outs is not None else None
+            if fmt != "native" and enc in OUTPUT_FORMATS:
+                dtype, planar, _ = OUTPUT_FORMATS[enc]
+                tdtype = torch.bfloat16 if enc.endswith("bf16") else {np.uint8: torch.uint8, np.float32: torch.float32, np.float16: torch.float16}[dtype]
+                shape = (n, 3, orows, ocols) if planar else ((n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn))
+            else:
+                planar, tdtype = False, torch.uint8
+                shape = (n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn * (2 if enc.endswith("16") else 1))
+            out_step = out_frame = 0
+            if out is None:
+                out = torch.empty(shape, dtype=tdtype, device=frames.device)
+            elif tuple(out.shape) != shape or out.dtype != tdtype or out.device != frames.device:
+                raise ValueError("outs[%d] must be a %s tensor of shape %s on the device of frames" % (k, tdtype, shape))
+            elif not out.is_contiguous():
+                elem = out.element_size()
+                inner = len(shape) == 4 and not planar
+                ok = out.stride(-1) == 1 and (not inner or out.stride(2) == shape[3]) and (not planar or out.stride(1) == out.stride(2) * orows)
+                if not ok:
+                    raise ValueError("outs[%d]: the elements of a row must be contiguous and the planes of a frame `rows` row pitches apart" % k)
+                out_step = out.stride(2 if planar else 1) * elem
+                out_frame = out.stride(0) * elem if n > 1 else 0
+            result[k] = out
+            bufs[k] = _HeadBuffer(C.c_void_p(out.data_ptr()), out_step, out_frame)
+        if tap_debayered is not None or tap_color is not None:
+            tr, tc, tcn = self.query_taps(rows, cols, cn, encoding)
+            tshape = (n, tr, tc) if tcn == 1 else (n, tr, tc, tcn)
+            for t in (tap_debayered, tap_color):
+                if t is not None and (t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tshape
+                                      or t.device != frames.device):
+                    raise ValueError("tap tensors must be contiguous uint8 CUDA tensors of shape %s" % (tshape,))
+        cur = torch.cuda.current_stream(frames.device)
+        mine = self._torch_stream
+        if mine is not None and mine.cuda_stream != cur.cuda_stream:
+            mine.wait_stream(cur)
+            for t in [frames, tap_debayered, tap_color] + result:
+                if t is not None:
+                    t.record_stream(mine)
+        with torch.cuda.device(frames.device):
+            self._given_last = (None, None, None)
+            self._call("rip_apply_device_heads", C.c_void_p(frames.data_ptr()), C.c_size_t(in_step), C.c_size_t(in_frame), int(n),
+                       int(rows), int(cols), int(cn), encoding.encode(), bufs, int(n_heads),
+                       C.c_void_p(tap_debayered.data_ptr() if tap_debayered is not None else 0),
+                       C.c_void_p(tap_color.data_ptr() if tap_color is not None else 0))
+        return result
+
+    def apply_heads(self, image, encoding, heads=None, width=None):
+        """One host frame, one result per requested output head from one upload and one run of the chain (rip_apply_heads).
+        Returns a list with one numpy array per head of the handle (None for heads not requested), each of the shape and dtype
+        ``process`` returns under that head's settings.  The image getters keep the taps; there is no processed image."""
+        img = np.asarray(image)
+        if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3):
+            raise ValueError("image must be uint8 (or uint16 Bayer), HxW or HxWxC")
+        if img.strides[-1] != img.itemsize or (img.ndim == 3 and img.strides[1] != img.shape[2] * img.itemsize):
+            img = np.ascontiguousarray(img)
+        rows, cols, cn = self._packed_geometry(img, encoding, width)
+        if (img.dtype == np.uint16) != encoding.endswith("16"):
+            raise ValueError("dtype %s does not match encoding %s" % (img.dtype, encoding))
+        n_heads = self.get_output_heads()
+        wanted = sorted(set(range(n_heads) if heads is None else [int(k) for k in heads]))
+        if not wanted or wanted[0] < 0 or wanted[-1] >= n_heads:
+            raise ValueError("heads must name at least one of the handle's heads 0..%d" % (n_heads - 1))
+        info = self._head_queries(wanted, rows, cols, cn, encoding)
+        result = [None] * n_heads
+        ptrs, caps = (C.c_void_p * n_heads)(), (C.c_size_t * n_heads)()
+        for k in wanted:
+            shape, dtype = _delivered(*info[k][:4])
+            result[k] = np.empty(shape, dtype)
+            ptrs[k], caps[k] = result[k].ctypes.data, result[k].nbytes
+        r, c, ch = (C.c_int * n_heads)(), (C.c_int * n_heads)(), (C.c_int * n_heads)()
+        self._given_last = (None, None, None)
+        self._call("rip_apply_heads", img.ctypes.data_as(C.c_void_p), rows, cols, cn, C.c_size_t(img.strides[0]), encoding.encode(),
+                   ptrs, caps, int(n_heads), r, c, ch)
+        for k in wanted:
+            assert (r[k], c[k], ch[k]) == info[k][:3]
+        return result
+
     def set_taps(self, mask):
         self._call("rip_set_taps", int(mask))
 
@@ -552,7 +703,7 @@ class RawImagePipeline:
         try:
             self._call("rip_load_params", path.encode())
         finally:
-            self._output_format = self.get_output_format()  # the params file's `output: format:`
+            self._output_format = self.get_output_format()  # the params file's `output: format:` (head 0 is selected after a load)
 
     def load_camera_calibration(self, path):
         self._call("rip_load_camera_calibration", path.encode())
