@@ -385,8 +385,22 @@ class RawImagePipeline {
 
   Mat getDistDebayeredImage() const { return image(RIP_IMAGE_DEBAYERED); }
   Mat getDistColorImage() const { return image(RIP_IMAGE_COLOR); }
+  // empty as in the reference, which never writes rect_mask_, unless setRectMask asked for masks: then the valid-pixel mask of the
+  // last frame's geometry (CV_8UC1, the maps' size) after a frame that was undistorted
   Mat getRectMask() const { return image(RIP_IMAGE_RECT_MASK); }
   Mat getProcessedImage() const { return image(RIP_IMAGE_PROCESSED); }
+  // Not in the reference: valid-pixel masks (rip.h rip_set_rect_mask).  "off" (default), "coverage" -- cv::remap of an all-255
+  // image -- or "valid" -- 255 where the coverage is 255, else 0.  getOutputMask: the mask of the image the selected head delivers
+  // for an input frame of that geometry (CV_8UC1, the delivered height x width; letterbox bands are 0); no frame need have been processed.
+  void setRectMask(const std::string& mode) { check(rip_set_rect_mask(h_, mode.c_str())); }
+  std::string getRectMaskMode() const { return str(&rip_get_rect_mask_mode); }
+  Mat getOutputMask(int rows, int cols, int channels, const std::string& encoding) const {
+    int height = 0, width = 0;
+    check(rip_get_output_mask(h_, rows, cols, channels, encoding.c_str(), nullptr, 0, &height, &width));
+    Mat out = detail::make_u8(height, width, 1);
+    check(rip_get_output_mask(h_, rows, cols, channels, encoding.c_str(), detail::bytes(out), (size_t)height * width, &height, &width));
+    return out;
+  }
   // Not in the reference: the same three images without a copy for a frame that came through collect() / collectView() --
   // the taps travel with the result into the handle's pinned host memory (rip_get_image_view), so a publisher that serialises
   // the image at once needs no second device read and no memcpy.  Valid until the next collect*() on this object; frames of

@@ -177,8 +177,10 @@ void rip_host_free(void* ptr);
 void rip_copy_host(void* dst, const void* src, size_t bytes);
 
 /* Image getters (hpp:134-137, cpp:222-236): copy of the tap of the most recent rip_apply
- * frame.  RIP_IMAGE_RECT_MASK is always empty (rows = cols = 0): the reference never writes
- * rect_mask_ (undistortion.cpp:150-152). */
+ * frame.  RIP_IMAGE_RECT_MASK: the reference never writes rect_mask_ (undistortion.cpp:150-152), and under the rect mask
+ * mode "off" (the default, rip_set_rect_mask) the image is empty here too (rows = cols = 0).  Under "coverage" / "valid",
+ * after a frame call whose frame was undistorted, it is the valid-pixel mask of that frame's geometry: rows x cols of the maps,
+ * one channel, built on the device when this getter asks; empty when the last frame was not undistorted. */
 rip_status rip_get_image(rip_pipeline* p, int which, uint8_t* out, size_t out_capacity, int* rows, int* cols,
                          int* channels);
 /* The same image without a copy, for frames that came through rip_collect: the final image always, the taps named by
@@ -186,7 +188,8 @@ rip_status rip_get_image(rip_pipeline* p, int which, uint8_t* out, size_t out_ca
  * rip_collect view: until the next rip_collect on the handle or until a rip_submit takes the slot).  *view is NULL -- with
  * the geometry still reported -- when the image only exists on the device (frames of rip_apply; images whose download went
  * into a buffer the caller named with rip_submit_to: that buffer is the caller's again once the ticket is collected and the
- * library does not look at it any more): use rip_get_image then.
+ * library does not look at it any more): use rip_get_image then.  RIP_IMAGE_RECT_MASK always reports its geometry with a NULL
+ * view: the mask lives on the device.
  * hpp:134-137 (getDistDebayeredImage / getDistColorImage / getProcessedImage return Mat headers, no copy either). */
 rip_status rip_get_image_view(rip_pipeline* p, int which, const uint8_t** view, int* rows, int* cols, int* channels);
 /* Which of the kept taps (RIP_TAP_DEBAYERED | RIP_TAP_COLOR) rip_submit ALSO downloads into pinned host memory together
@@ -485,6 +488,44 @@ rip_status rip_apply_heads(rip_pipeline* p, const uint8_t* image, int rows, int 
  * head's tables once; *direct_write / *copied: whether the last frame call that delivered the head had the chain write its buffer
  * directly (also true of a head that delivers F in a single-output call) or copied it from the staging image.  Any pointer may be null. */
 rip_status rip_debug_output_head_info(rip_pipeline* p, int head, int* table_builds, int* direct_write, int* copied);
+/* Extension beyond the reference: valid-pixel masks (PARITY.md "Rect mask").  Delivered pixels that are not image -- the black border
+ * a balance above 0 leaves, the rim where cv::remap blended a source pixel with the border constant, the bands of a letterbox -- are
+ * told apart from image by a mask.  mode: "off" (default: every call behaves exactly as without this extension), "coverage" or "valid";
+ * any other name, or a null one: RIP_ERR_INVALID_ARGUMENT, nothing changed.
+ * The coverage mask M of a frame the plan would undistort is cv::remap(white, map_x, map_y, INTER_LINEAR, BORDER_CONSTANT 0) with
+ * `white` an all-255 image of the size that enters the remap (the frame after the flip): rows x cols of the maps, uint8, one channel.
+ * It depends on the maps and on that size and on no frame content.  "valid" hands out V = (M == 255) ? 255 : 0: a pixel whose taps
+ * outside the source carry at most 64 / 32768 of the weight, so that it differs from a fully interior pixel by at most one level.
+ * RIP_IMAGE_RECT_MASK (rip_get_image) is M or V for the last frame call's geometry.
+ * The delivered mask M' of an output head, H x W as rip_query_output reports for the head: what that head delivers under the format
+ * "native" with the pad (0, 0, 0) for a one-channel frame whose final image is M -- M is all 255 at F's size for a frame that is not
+ * undistorted.  So letterbox bands are 0, a window cuts M, and a resize filters M with the head's own filter.  Under "valid" the
+ * threshold follows the head's geometry: V' = (M' == 255) ? 255 : 0.  A mask is always uint8, one channel; the head's format and
+ * normalisation do not apply.
+ * The frame calls do no mask work, whatever the mode: their launches are the same.  Masks are built by the getters, on the handle's
+ * stream, and cached on the device -- M per (maps, size entering the remap), M' per head -- until the maps are rebuilt or replaced
+ * (calibration, image sizes, balance, fov scale, K, D, model, R, P, rip_init_undistortion, rip_load_params), an output setter of the
+ * head is called, or rip_set_output_heads resets the head.
+ * Works on RIP_DEVICE_NONE handles.  Params YAML: `undistortion: mask: off | coverage | valid`; an absent key means off; an invalid
+ * value fails with RIP_ERR_INVALID_ARGUMENT and leaves the parameters as they were. */
+rip_status rip_set_rect_mask(rip_pipeline* p, const char* mode);
+rip_status rip_get_rect_mask_mode(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
+/* The delivered mask of the selected head for an input frame of that geometry (arguments as for rip_query_output; no frame need have
+ * been processed): H * W bytes, tight rows, into out[capacity]; *height / *width (either may be null) receive H and W.  Refused before
+ * anything is enqueued, in this order: the mode "off" (RIP_ERR_INVALID_ARGUMENT, the message says so); exactly the refusals of
+ * rip_query_output; a capacity below H * W (RIP_ERR_CAPACITY).  out == NULL returns the geometry only and works on RIP_DEVICE_NONE
+ * handles; a non-NULL out on such a handle fails with RIP_ERR_DEVICE.  Synchronous. */
+rip_status rip_get_output_mask(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, uint8_t* out, size_t capacity,
+                               int* height, int* width);
+/* The same image where it is cached on the device: *d_mask, rows *pitch bytes apart (a multiple of 16), written in the order of the
+ * handle's stream.  It stays valid until the next call that drops that head's cache -- also a mask getter for another geometry or mode
+ * under that head -- or destroys the handle.  pitch, height and width may be null. */
+rip_status rip_get_output_mask_device(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, const uint8_t** d_mask,
+                                      size_t* pitch, int* height, int* width);
+/* Test hook: *mask_builds: how often a mask of a frame geometry (M, its thresholded twin, or the all-255 image) was built since the
+ * handle was created; *head_builds: how often the delivered mask of head `head` (0..n-1, else RIP_ERR_INVALID_ARGUMENT) was.  A steady
+ * sequence of identical getter calls builds each once.  Either pointer may be null. */
+rip_status rip_debug_rect_mask_info(rip_pipeline* p, int head, int* mask_builds, int* head_builds);
 rip_status rip_set_flip(rip_pipeline* p, int enabled);                            /* hpp:69 */
 rip_status rip_set_flip_angle(rip_pipeline* p, int angle);                        /* hpp:70 */
 rip_status rip_set_white_balance(rip_pipeline* p, int enabled);                   /* hpp:72 */

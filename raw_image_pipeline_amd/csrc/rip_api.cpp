@@ -280,6 +280,7 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
                          d_tap_color ? static_cast<uint8_t*>(d_tap_color) + (size_t)f0 * tap_frame : nullptr};
       run_batch_formatted(p, pl, frames_from(src, f0), frames_from(dst, f0), taps, std::min(kMaxFramesPerLaunch, n_frames - f0));
     }
+    remember_mask_frame(p, pl);
   });
 }
 
@@ -294,6 +295,7 @@ rip_status rip_set_output_heads(rip_pipeline* p, int n) {
       p->m.heads[k] = rip::OutputHead();
       p->out_table[k].dirty = true;
       p->head_record[k] = {};
+      p->mask_head[k].valid = false;
     }
     p->m.n_heads = n;
     if (p->m.selected >= n) p->m.selected = 0;
@@ -371,6 +373,79 @@ rip_status rip_apply_device_heads(rip_pipeline* p, const void* d_in, size_t in_s
       for (int k = 0; k < n_heads; k++) slice[k] = requested[k] ? frames_from(dsts[k], f0) : dsts[k];
       run_batch_heads(p, pl, plans, slice, n_heads, frames_from(src, f0), taps, std::min(kMaxFramesPerLaunch, n_frames - f0));
     }
+    remember_mask_frame(p, pl);
+  });
+}
+
+// ---- valid-pixel masks ---------------------------------------------------------------------------
+rip_status rip_set_rect_mask(rip_pipeline* p, const char* mode) {
+  return guarded(p, [&] {
+    need(p);
+    if (!mode) throw InvalidArgument("null string");
+    (void)rip::rect_mask_mode_id(mode);
+    p->m.rect_mask = mode;
+  });
+}
+
+rip_status rip_get_rect_mask_mode(const rip_pipeline* p, char* out, size_t capacity) {
+  return guarded(p, [&] {
+    need(p);
+    copy_string(p->m.rect_mask, out, capacity);
+  });
+}
+
+// rip_get_output_mask / rip_get_output_mask_device up to the geometry: the refusals in their order (the mode, then exactly those of
+// rip_query_output), nothing enqueued
+static Plan output_mask_plan(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* mode) {
+  need(p);
+  *mode = rip::rect_mask_mode_id(p->m.rect_mask);
+  if (*mode == 0) throw InvalidArgument("the rect mask mode is 'off': no masks are built (rip_set_rect_mask 'coverage' or 'valid')");
+  if (!encoding) throw InvalidArgument("encoding is null");
+  Plan pl = make_plan(p->m, rows, cols, channels, encoding);
+  apply_output_format(p->m, p->m.selected, pl);
+  return pl;
+}
+
+rip_status rip_get_output_mask(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, uint8_t* out, size_t capacity,
+                               int* height, int* width) {
+  return guarded(p, [&] {
+    int mode = 0;
+    const Plan pl = output_mask_plan(p, rows, cols, channels, encoding, &mode);
+    const size_t bytes = (size_t)pl.dl_rows * (size_t)pl.dl_cols;
+    if (out && capacity < bytes) throw CapacityError("mask buffer too small: need " + std::to_string(bytes) + " bytes");
+    if (height) *height = pl.dl_rows;
+    if (width) *width = pl.dl_cols;
+    if (!out) return;  // the geometry only
+    need_device(p);
+    DeviceGuard device_guard(p->device);
+    const ConstFrameView m = ensure_mask_head(p, pl, mode);
+    HIP_CHECK(hipMemcpy2DAsync(out, (size_t)m.cols, m.ptr, m.step, (size_t)m.cols, (size_t)m.rows, hipMemcpyDeviceToHost, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+  });
+}
+
+rip_status rip_get_output_mask_device(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, const uint8_t** d_mask,
+                                      size_t* pitch, int* height, int* width) {
+  return guarded(p, [&] {
+    int mode = 0;
+    const Plan pl = output_mask_plan(p, rows, cols, channels, encoding, &mode);
+    if (!d_mask) throw InvalidArgument("null mask pointer");
+    need_device(p);
+    const ConstFrameView m = ensure_mask_head(p, pl, mode);
+    *d_mask = m.ptr;
+    if (pitch) *pitch = m.step;
+    if (height) *height = m.rows;
+    if (width) *width = m.cols;
+  });
+}
+
+rip_status rip_debug_rect_mask_info(rip_pipeline* p, int head, int* mask_builds, int* head_builds) {
+  return guarded(p, [&] {
+    need(p);
+    if (head < 0 || head >= p->m.n_heads)
+      throw InvalidArgument("output head " + std::to_string(head) + " does not exist: the handle has heads 0.." + std::to_string(p->m.n_heads - 1));
+    if (mask_builds) *mask_builds = p->mask_base.builds;
+    if (head_builds) *head_builds = p->mask_head[head].builds;
   });
 }
 
@@ -396,6 +471,7 @@ rip_status rip_load_params(rip_pipeline* p, const char* path) {
     }
     p->tables.dirty = p->vignette.dirty = p->ccc.cfg_dirty = true;
     for (auto& t : p->out_table) t.dirty = true;
+    for (auto& h : p->mask_head) h.valid = false;
     und_init(p);  // setBalance / setFovScale re-run init()
   });
 }
@@ -444,6 +520,9 @@ rip_status rip_set_ccc_model(rip_pipeline* p, int w, int h, const float* filter,
   });
 }
 // ---- setters -----------------------------------------------------------------------------------
+// an output setter of the selected head drops that head's delivered mask (rip_get_output_mask), whatever it sets
+static void drop_head_mask(rip_pipeline* p) { p->mask_head[p->m.selected].valid = false; }
+
 #define RIP_SETTER(name, args, body)          \
   rip_status name args {                      \
     return guarded(p, [&] {                   \
@@ -465,20 +544,20 @@ RIP_SETTER(rip_set_debayer_16bit_range, (rip_pipeline * p, int black, int white)
 RIP_SETTER(rip_set_debayer_encoding, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.debayer_encoding = s)
 RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
            rip::check_debayer_method(s); p->m.debayer_method = s)
-RIP_SETTER(rip_set_output_format, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+RIP_SETTER(rip_set_output_format, (rip_pipeline * p, const char* s), drop_head_mask(p); if (!s) throw InvalidArgument("null string");
            (void)rip::output_format_id(s); if (p->m.out().out_format != s) p->out_table[p->m.selected].dirty = true; p->m.out().out_format = s)
-RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, const double* mean, const double* sd),
+RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, const double* mean, const double* sd), drop_head_mask(p);
            if (!mean || !sd) throw InvalidArgument("null mean or std");
            rip::check_output_normalization(divisor, mean, sd); p->m.out().out_divisor = divisor;
            for (int i = 0; i < 3; i++) { p->m.out().out_mean[i] = mean[i]; p->m.out().out_std[i] = sd[i]; } p->out_table[p->m.selected].dirty = true)
-RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), rip::check_output_size(width, height); p->m.out().out_w = width; p->m.out().out_h = height)
-RIP_SETTER(rip_set_output_interpolation, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), drop_head_mask(p); rip::check_output_size(width, height); p->m.out().out_w = width; p->m.out().out_h = height)
+RIP_SETTER(rip_set_output_interpolation, (rip_pipeline * p, const char* s), drop_head_mask(p); if (!s) throw InvalidArgument("null string");
            (void)rip::output_interpolation_id(s); p->m.out().out_interp = s)
-RIP_SETTER(rip_set_output_roi, (rip_pipeline * p, int x, int y, int width, int height), rip::check_output_roi(x, y, width, height);
+RIP_SETTER(rip_set_output_roi, (rip_pipeline * p, int x, int y, int width, int height), drop_head_mask(p); rip::check_output_roi(x, y, width, height);
            p->m.out().roi_x = x; p->m.out().roi_y = y; p->m.out().roi_w = width; p->m.out().roi_h = height)
-RIP_SETTER(rip_set_output_fit, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+RIP_SETTER(rip_set_output_fit, (rip_pipeline * p, const char* s), drop_head_mask(p); if (!s) throw InvalidArgument("null string");
            (void)rip::output_fit_id(s); p->m.out().out_fit = s)
-RIP_SETTER(rip_set_output_pad, (rip_pipeline * p, int b, int g, int r), rip::check_output_pad(b, g, r);
+RIP_SETTER(rip_set_output_pad, (rip_pipeline * p, int b, int g, int r), drop_head_mask(p); rip::check_output_pad(b, g, r);
            p->m.out().out_pad[0] = b; p->m.out().out_pad[1] = g; p->m.out().out_pad[2] = r)
 RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
 RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)

@@ -702,6 +702,105 @@ void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const F
   }
 }
 
+// ---- valid-pixel masks (rip_set_rect_mask; PARITY.md "Rect mask") -------------------------------------------------------------
+namespace {
+MaskBaseConst::Key mask_base_key(const rip_pipeline* p, bool remap, int src_rows, int src_cols, int rows, int cols) {
+  MaskBaseConst::Key k;
+  k.generation = remap ? p->maps_generation : 0;  // an all-255 image does not depend on the maps
+  k.remap = remap ? 1 : 0;
+  k.src_rows = remap ? src_rows : 0;
+  k.src_cols = remap ? src_cols : 0;
+  k.rows = rows;
+  k.cols = cols;
+  return k;
+}
+}  // namespace
+
+// The mask of a frame geometry (rip_handle.hpp): one launch of rect_mask_kernel (librip_mask_hip.so) over the maps the handle keeps
+// on the device, or a fill for a frame that is not undistorted -- its thresholded twin is the same image.
+ConstFrameView ensure_mask_base(rip_pipeline* p, bool remap, int src_rows, int src_cols, int rows, int cols, bool binary) {
+  DeviceGuard device_guard(p->device);
+  LaunchLogScope log_scope(p);
+  MaskBaseConst& mb = p->mask_base;
+  const MaskBaseConst::Key key = mask_base_key(p, remap, src_rows, src_cols, rows, cols);
+  if (!(key == mb.key)) {
+    mb.key = key;
+    mb.cov_valid = mb.bin_valid = false;
+  }
+  const bool twin = binary && remap;
+  DevBuf& buf = twin ? mb.bin : mb.cov;
+  bool& valid = twin ? mb.bin_valid : mb.cov_valid;
+  const size_t pitch = mb.pitch();
+  if (!valid) {
+    p->work_enqueued = true;
+    buf.reserve(pitch * (size_t)rows);
+    if (remap) {
+      ensure_maps(p);
+      rip::RectMaskParams r = {};
+      r.map_xy = p->maps.dev.as<float>();
+      r.drows = rows;
+      r.dcols = cols;
+      r.src_rows = src_rows;
+      r.src_cols = src_cols;
+      r.dst = buf.as<uint8_t>();
+      r.dst_step = pitch;
+      r.binary = binary ? 1 : 0;
+      rip::MaskLaunchInfo info = {};
+      launched(rip::launch_rect_mask(r, p->stream, &info), info, "the rect mask", 0);
+    } else {
+      HIP_CHECK(hipMemsetAsync(buf.ptr, 255, pitch * (size_t)rows, p->stream));
+    }
+    valid = true;
+    mb.builds++;
+  }
+  return {buf.as<uint8_t>(), pitch, pitch * (size_t)rows, rows, cols};
+}
+
+// The delivered mask of a head: the head's own launches behind F (prepare_head / enqueue_head) on a copy of the frame's plan that has
+// one channel, the format "native" and the pad 0, reading the coverage in place of F; under `valid` the threshold follows the head's
+// geometry (mask_threshold_kernel).  A head that delivers F as it is gets a copy of the mask -- under `valid` of its thresholded
+// twin, which the kernel wrote directly -- so that every head's image is its own and lives as long as that head's cache.
+ConstFrameView ensure_mask_head(rip_pipeline* p, const Plan& frame_pl, int mode) {
+  DeviceGuard device_guard(p->device);
+  Plan pl = frame_pl;
+  pl.channels = pl.dl_channels = 1;
+  pl.out_elem_bytes = pl.dl_elem_bytes = 1;
+  pl.fmt_active = pl.dl_planar = false;
+  pl.out_fmt = rip::OUT_NATIVE;
+  for (uint8_t& c : pl.pad) c = 0;
+  const bool identity = identity_head(pl), binary = mode == 2;
+  MaskHeadConst& mh = p->mask_head[pl.head];
+  const MaskBaseConst::Key key = mask_base_key(p, pl.remap, pl.mid_rows, pl.mid_cols, pl.out_rows, pl.out_cols);
+  const int geom[11] = {pl.win_x, pl.win_y, pl.win_w, pl.win_h, pl.pic_x, pl.pic_y, pl.pic_w, pl.pic_h, pl.dl_rows, pl.dl_cols, pl.rsz_active ? 1 + pl.rsz_kind : 0};
+  const size_t pitch = ((size_t)pl.dl_cols + 15) & ~(size_t)15;
+  if (!(mh.valid && mh.base == key && mh.mode == mode && std::equal(geom, geom + 11, mh.geom))) {
+    mh.valid = false;
+    const ConstFrameView base = ensure_mask_base(p, pl.remap, pl.mid_rows, pl.mid_cols, pl.out_rows, pl.out_cols, binary && identity);
+    mh.img.reserve(pitch * (size_t)pl.dl_rows);
+    const FrameView dst = {mh.img.as<uint8_t>(), pitch, pitch * (size_t)pl.dl_rows, pl.dl_rows, pl.dl_cols};
+    p->work_enqueued = true;
+    if (identity) {
+      HIP_CHECK(hipMemcpy2DAsync(dst.ptr, dst.step, base.ptr, base.step, (size_t)base.cols, (size_t)base.rows, hipMemcpyDeviceToDevice, p->stream));
+    } else {
+      const FrameView staged = {const_cast<uint8_t*>(base.ptr), base.step, base.frame_stride, base.rows, base.cols};  // read only
+      const HeadPrep hp = prepare_head(p, pl, staged, 1);
+      enqueue_head(p, pl, hp, staged, dst, 1);
+      if (binary) {
+        LaunchLogScope log_scope(p);
+        rip::MaskThresholdParams t = {dst.ptr, dst.step, dst.rows, dst.cols};
+        rip::MaskLaunchInfo info = {};
+        launched(rip::launch_mask_threshold(t, p->stream, &info), info, "the mask threshold", 0);
+      }
+    }
+    mh.base = key;
+    mh.mode = mode;
+    std::copy(geom, geom + 11, mh.geom);
+    mh.valid = true;
+    mh.builds++;
+  }
+  return {mh.img.as<uint8_t>(), pitch, pitch * (size_t)pl.dl_rows, pl.dl_rows, pl.dl_cols};
+}
+
 // setDebug(true): raw_image_pipeline.hpp:143-172 writes the image after EVERY module -- enabled or not -- to
 // /tmp/0N_<module>.png through saveDebugImage (:179-186: copy, cv::normalize(0, 255, NORM_MINMAX), cv::imwrite).  The modules
 // are one fused kernel here, so the image after module k is produced by running the chain once more with the modules after k

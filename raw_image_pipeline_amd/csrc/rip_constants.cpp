@@ -39,6 +39,7 @@ void und_init(rip_pipeline* p) {
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) m.rect_P[i * 4 + j] = m.rect_K[i * 3 + j];
   p->maps.dirty = true;
+  p->maps_generation++;  // the masks built from the maps before this call are no longer current (MaskBaseConst::Key)
 }
 
 // Where the maps are built: on the device for device handles (rip_maps.hip: one thread per map row, FP64, double-double

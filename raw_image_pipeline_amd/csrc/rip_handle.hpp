@@ -21,6 +21,7 @@
 #include "rip_area.hpp"
 #include "rip_fit.hpp"
 #include "rip_heads.hpp"
+#include "rip_mask.hpp"
 #include "rip_resize.hpp"
 
 namespace rip {
@@ -292,6 +293,35 @@ struct ResizeTableConst {
   // build_resize_aa_tables' precisions for that key, and its tile height and LDS rows for 1 ([0]) and 3 ([1]) channels
   int aa_xprec = 0, aa_yprec = 0, aa_tile_rows[2] = {0, 0}, aa_lds_rows[2] = {0, 0};
 };
+// valid-pixel masks (rip_set_rect_mask; PARITY.md "Rect mask"), built by the getters and never by a frame call.  All images are one
+// channel with the staging image's layout rule (rows padded to 16 bytes), so every one-channel launch behind F takes them as its source.
+// The mask of a frame geometry: the coverage M of the undistortion (rect_mask_kernel), or an all-255 image of F's size for a frame
+// that is not undistorted.  `cov` holds M, `bin` its thresholded twin (M == 255) ? 255 : 0, each built when first asked for.
+struct MaskBaseConst {
+  // what the images were built for: the generation of the maps (und_init counts), whether the frame is undistorted, the size of the
+  // image that enters the remap and the size of the mask itself (the maps' size, or F's)
+  struct Key {
+    uint64_t generation = 0;
+    int remap = 0, src_rows = 0, src_cols = 0, rows = 0, cols = 0;
+    bool operator==(const Key& o) const {
+      return generation == o.generation && remap == o.remap && src_rows == o.src_rows && src_cols == o.src_cols && rows == o.rows && cols == o.cols;
+    }
+  } key;
+  DevBuf cov, bin;
+  bool cov_valid = false, bin_valid = false;
+  int builds = 0;  // images built since the handle was created (rip_debug_rect_mask_info)
+  size_t pitch() const { return ((size_t)key.cols + 15) & ~(size_t)15; }
+};
+// The delivered mask M' of one output head: what the head's window, target, fit mode and filter make of the mask above, under the
+// mode it was built for.  One per head, like the table caches; dropped by the head's output setters and by whatever drops M.
+struct MaskHeadConst {
+  MaskBaseConst::Key base;
+  int mode = 0;
+  int geom[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // win_x, win_y, win_w, win_h, pic_x, pic_y, pic_w, pic_h, dl_rows, dl_cols, filter kernel
+  DevBuf img;
+  bool valid = false;
+  int builds = 0;  // rip_debug_rect_mask_info
+};
 
 }  // namespace rip::api
 
@@ -323,6 +353,16 @@ struct rip_pipeline {
   struct HeadRecord {
     int direct_write = 0, copied = 0;
   } head_record[rip::kMaxOutputHeads];
+  // valid-pixel masks (rip_set_rect_mask): the generation of the maps (und_init counts: everything that rebuilds or replaces them
+  // goes through it), the mask of the last geometry asked for, one delivered mask per head, and the geometry of the last frame call
+  // -- undistorted or not, and the size of the image that entered its remap -- which is all RIP_IMAGE_RECT_MASK needs of a frame
+  uint64_t maps_generation = 1;
+  rip::api::MaskBaseConst mask_base;
+  rip::api::MaskHeadConst mask_head[rip::kMaxOutputHeads];
+  struct MaskFrame {
+    bool remap = false;
+    int src_rows = 0, src_cols = 0;
+  } mask_frame;
   // per-batch scratch.  d_stats.clean_bytes: the prefix known to hold zeroed FrameStats records (the grey-world / pca statistics
   // kernels clean up after themselves).  d_hist.clean_bytes: the leading bytes known to be zero -- the ccc estimator's global-atomic
   // histogram (small batches) hands its counters back zeroed, so a stream of single frames pays for one memset, not one per frame
@@ -490,5 +530,14 @@ void plan_heads(const rip::Modules& m, const Plan& pl, int n_heads, const bool* 
   if (pl.out_elem_bytes == 2 && any_tap) throw InvalidArgument("16-bit Bayer frames have no taps");
 }
 void write_debug_dumps(rip_pipeline* p, const Plan& pl, ConstFrameView src, const uint8_t* final_image);
+// Valid-pixel masks (rip_set_rect_mask; PARITY.md "Rect mask").  What a frame call leaves for RIP_IMAGE_RECT_MASK: two ints and a flag
+inline void remember_mask_frame(rip_pipeline* p, const Plan& pl) { p->mask_frame = {pl.remap, pl.mid_rows, pl.mid_cols}; }
+// The mask of a frame geometry on the device, built on the handle's stream unless it is cached: the coverage M of the current maps
+// for a src_rows x src_cols image entering the remap (remap; rows x cols is then the maps' size), else all 255 of rows x cols;
+// binary: its thresholded twin.  Rows are pitch() bytes apart.
+ConstFrameView ensure_mask_base(rip_pipeline* p, bool remap, int src_rows, int src_cols, int rows, int cols, bool binary);
+// The delivered mask of head pl.head for the frame of `pl` (make_plan + apply_output_format of that frame) under mode 1 (coverage) or
+// 2 (valid): dl_rows x dl_cols, one channel, cached per head.
+ConstFrameView ensure_mask_head(rip_pipeline* p, const Plan& pl, int mode);
 
 }  // namespace rip::api

@@ -362,6 +362,11 @@ void params_from_node(Modules& m, const YamlNode& node) {
   // loadParams re-creates the modules, so absent keys mean off.  An invalid range fails the load like an unknown method.
   const int black_level = node["debayer"].get("black_level", 0), white_level = node["debayer"].get("white_level", 0);
   check_debayer_16bit_range(black_level, white_level);
+  // extension key undistortion: mask: (rip_set_rect_mask); an absent key means off, an unknown word fails the load
+  const std::string rect_mask = node["undistortion"].get("mask", std::string("off"));
+  (void)rect_mask_mode_id(rect_mask);
+  if (node["undistortion"]["mask"].defined() && node["undistortion"]["mask"].kind != YamlNode::Scalar)
+    throw std::invalid_argument("undistortion: mask: one word is expected, \"off\", \"coverage\" or \"valid\"");
   // extension keys output: ... (output_head_from_node) and the further heads' sections output_1: .. output_7: with the same keys
   // (rip_set_output_heads): n = 1 + the largest k present, sections absent in between hold the defaults, head 0 is selected
   OutputHead heads[kMaxOutputHeads];
@@ -412,6 +417,7 @@ void params_from_node(Modules& m, const YamlNode& node) {
   m.und_enabled = u.get("enabled", false);
   m.balance = u.get("balance", 0.0);
   m.fov_scale = u.get("fov_scale", 1.0);
+  m.rect_mask = rect_mask;
 }
 
 void set_camera(Modules& m, int w, int h, const std::vector<double>& K, const std::vector<double>& D,
@@ -461,6 +467,13 @@ void apply_example_params(Modules& m) {
   m.und_enabled = true;
   m.balance = 0.0;
   m.fov_scale = 0.8;
+}
+
+int rect_mask_mode_id(const std::string& name) {
+  if (name == "off") return 0;
+  if (name == "coverage") return 1;
+  if (name == "valid") return 2;
+  throw std::invalid_argument("Rect mask mode [" + name + "] not supported. Supported modes: 'off', 'coverage', 'valid'");
 }
 
 void check_debayer_method(const std::string& method) {

@@ -116,7 +116,12 @@ struct Modules {
   double dist_P[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, rect_P[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   int dist_w = 320, dist_h = 240, rect_w = 320, rect_h = 240;
   double balance = 0.0, fov_scale = 1.0;
+  // extension (rip_set_rect_mask; PARITY.md "Rect mask"): "off", "coverage" or "valid" -- what RIP_IMAGE_RECT_MASK and
+  // rip_get_output_mask hand out.  The frame calls never look at it.
+  std::string rect_mask = "off";
 };
+// the mask modes rip_set_rect_mask accepts: 0 "off", 1 "coverage", 2 "valid"; throws std::invalid_argument naming them otherwise
+int rect_mask_mode_id(const std::string& name);
 
 // Parameter loaders (throw YamlError on malformed files; a missing file is a soft failure
 // that returns false, as the reference's std::cout warning paths do).

@@ -3,18 +3,14 @@
 // counted waits of the ring.
 #pragma once
 #include "rip_device.hpp"
+#include "rip_round_map.hpp"
 
 namespace rip {
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// remap: cv::remap(INTER_LINEAR, BORDER_CONSTANT 0), undistortion.cpp:240-245
+// remap: cv::remap(INTER_LINEAR, BORDER_CONSTANT 0), undistortion.cpp:240-245; round_map: rip_round_map.hpp
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int round_map(float v) {
-  float s = v * 32.f;
-  if (!(s > -2147483648.f && s < 2147483648.f)) return INT_MIN;  // cvRound of NaN/inf/out of range
-  return (int)__builtin_rintf(s);
-}
 
 // Six consecutive source bytes starting at byte offset `off` of the frame (any alignment), fetched
 // as three aligned dwords (one global_load_dwordx3) and realigned with v_alignbyte_b32.

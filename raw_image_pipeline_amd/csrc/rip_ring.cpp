@@ -207,6 +207,12 @@ void remember_last(rip_pipeline* p, int which, DevBuf* buf, const void* host, in
   p->last_cn[which] = channels;
 }
 
+// RIP_IMAGE_RECT_MASK holds something: a mode other than "off", and the last frame call's frame was undistorted -- by an undistortion
+// that still exists (the mask is built from the current maps when a getter asks)
+bool rect_mask_exists(const rip_pipeline* p) {
+  return p->m.rect_mask != "off" && p->mask_frame.remap && p->m.und_available && p->m.dist_model != "none" && p->m.dist_w > 0 && p->m.dist_h > 0;
+}
+
 rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols, int channels, size_t step, const char* encoding,
                        uint8_t* ext_out, size_t ext_out_capacity, uint8_t* ext_deb, uint8_t* ext_col, size_t ext_tap_capacity,
                        uint64_t* ticket) {
@@ -363,6 +369,7 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     remember_last(p, RIP_IMAGE_COLOR, &p->d_tap_col, nullptr, pl.mid_rows, pl.mid_cols, pl.channels, L.keep_col);
     // under a format or a resize the delivered buffer is the result (as for bgr16): no PROCESSED image
     remember_last(p, RIP_IMAGE_PROCESSED, &p->d_out, nullptr, pl.out_rows, pl.out_cols, pl.channels, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1 && !pl.fmt_active && !pl.rsz_active);
+    remember_mask_frame(p, pl);
     if (out_rows) *out_rows = pl.dl_rows;
     if (out_cols) *out_cols = pl.dl_cols;
     if (out_channels) *out_channels = pl.dl_channels;
@@ -415,6 +422,7 @@ rip_status rip_apply_heads(rip_pipeline* p, const uint8_t* image, int rows, int 
     remember_last(p, RIP_IMAGE_COLOR, &p->d_tap_col, nullptr, pl.mid_rows, pl.mid_cols, pl.channels, L.keep_col);
     // the delivered buffers are the results: no PROCESSED image
     remember_last(p, RIP_IMAGE_PROCESSED, &p->d_out, nullptr, pl.out_rows, pl.out_cols, pl.channels, false);
+    remember_mask_frame(p, pl);
     for (int k = 0; k < n_heads; k++) {
       if (out_rows) out_rows[k] = requested[k] ? plans[k].dl_rows : 0;
       if (out_cols) out_cols[k] = requested[k] ? plans[k].dl_cols : 0;
@@ -471,6 +479,7 @@ rip_status rip_collect(rip_pipeline* p, uint64_t ticket, uint8_t* out, size_t ou
     remember_last(p, RIP_IMAGE_DEBAYERED, &sl->d_tap_deb, sl->dl_deb && sl->dst_tap[0] == sl->h_tap[0] ? sl->dst_tap[0] : nullptr, pl.mid_rows, pl.mid_cols, pl.channels, sl->has_deb);
     remember_last(p, RIP_IMAGE_COLOR, &sl->d_tap_col, sl->dl_col && sl->dst_tap[1] == sl->h_tap[1] ? sl->dst_tap[1] : nullptr, pl.mid_rows, pl.mid_cols, pl.channels, sl->has_col);
     remember_last(p, RIP_IMAGE_PROCESSED, &sl->d_out, sl->dst_out == sl->h_out ? sl->dst_out : nullptr, pl.out_rows, pl.out_cols, pl.channels, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1 && !pl.fmt_active && !pl.rsz_active);
+    remember_mask_frame(p, pl);
     if (out_rows) *out_rows = pl.dl_rows;
     if (out_cols) *out_cols = pl.dl_cols;
     if (out_channels) *out_channels = pl.dl_channels;
@@ -516,8 +525,24 @@ void rip_copy_host(void* dst, const void* src, size_t bytes) {
 rip_status rip_get_image(rip_pipeline* p, int which, uint8_t* out, size_t out_capacity, int* rows, int* cols, int* channels) {
   return guarded(p, [&] {
     need(p);
+    if (which == RIP_IMAGE_RECT_MASK && rect_mask_exists(p)) {
+      // built here, on demand, from the maps and the size of the image that entered the last frame's remap (PARITY.md "Rect mask")
+      const int mrows = p->m.dist_h, mcols = p->m.dist_w;
+      const size_t bytes = (size_t)mrows * (size_t)mcols;
+      if (rows) *rows = mrows;
+      if (cols) *cols = mcols;
+      if (channels) *channels = 1;
+      if (!out) return;  // size query
+      if (out_capacity < bytes) throw CapacityError("image buffer too small");
+      need_device(p);
+      DeviceGuard device_guard(p->device);
+      const ConstFrameView m = ensure_mask_base(p, true, p->mask_frame.src_rows, p->mask_frame.src_cols, mrows, mcols, p->m.rect_mask == "valid");
+      HIP_CHECK(hipMemcpy2DAsync(out, (size_t)mcols, m.ptr, m.step, (size_t)mcols, (size_t)mrows, hipMemcpyDeviceToHost, p->stream));
+      HIP_CHECK(hipStreamSynchronize(p->stream));
+      return;
+    }
     if (which == RIP_IMAGE_RECT_MASK || which < 0 || which > 3 || !p->last_valid[which]) {
-      // rect_mask_ is never written by the reference; taps that were not kept are empty too
+      // the reference never writes rect_mask_, and neither does this library under the mode "off"; taps that were not kept are empty too
       if (which < 0 || which > 3) throw InvalidArgument("unknown image id");
       if (rows) *rows = 0;
       if (cols) *cols = 0;
@@ -547,7 +572,14 @@ rip_status rip_get_image_view(rip_pipeline* p, int which, const uint8_t** view, 
     if (!view) throw InvalidArgument("null view");
     if (which < 0 || which > 3) throw InvalidArgument("unknown image id");
     *view = nullptr;
-    const bool have = which != RIP_IMAGE_RECT_MASK && p->last_valid[which];
+    if (which == RIP_IMAGE_RECT_MASK) {  // the mask lives on the device: its geometry with a null view, or empty
+      const bool mask = rect_mask_exists(p);
+      if (rows) *rows = mask ? p->m.dist_h : 0;
+      if (cols) *cols = mask ? p->m.dist_w : 0;
+      if (channels) *channels = mask ? 1 : 0;
+      return;
+    }
+    const bool have = p->last_valid[which];
     if (rows) *rows = have ? p->last_rows[which] : 0;
     if (cols) *cols = have ? p->last_cols[which] : 0;
     if (channels) *channels = have ? p->last_cn[which] : 0;

@@ -39,6 +39,9 @@ NODE_DEFAULTS = OrderedDict([
     ("undistortion/distortion_coefficients/data", [0.0, 0.0, 0.0, 0.0]), ("undistortion/distortion_model", "none"),
     ("undistortion/rectification_matrix/data", [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]),
     ("undistortion/projection_matrix/data", [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]),
+    # extension: "coverage" / "valid" also publish the valid-pixel mask of the rect image on <output_prefix>/image_mask, the topic the
+    # node has commented out (raw_image_pipeline_ros.cpp:201); rip.h rip_set_rect_mask
+    ("rect_mask", "off"),
 ])
 
 
@@ -113,6 +116,7 @@ class CameraStream:
         pipe.set_color_enhancer_saturation_gain(p["color_enhancer/saturation_gain"])
         pipe.set_color_enhancer_value_gain(p["color_enhancer/value_gain"])
         pipe.set_undistortion(p["undistortion/enabled"])
+        pipe.set_rect_mask(p["rect_mask"])
         pipe.set_undistortion_balance(p["undistortion/balance"])
         pipe.set_undistortion_fov_scale(p["undistortion/fov_scale"])
         pipe.load_camera_calibration(p["undistortion/calibration_file"])
@@ -131,6 +135,8 @@ class CameraStream:
         t = []
         if self.pipe.is_undistortion_enabled():
             t += [self.output_prefix + "/" + self.input_type + "_rect/image", self.output_prefix + "/" + self.input_type + "_rect/image/slow"]
+            if self.pipe.get_rect_mask_mode() != "off":
+                t += [self.output_prefix + "/image_mask"]
         if self.input_type == "color":
             t += [self.output_prefix + "/debayered/image", self.output_prefix + "/debayered/slow"]
         t += [self.output_prefix + "/" + self.input_type + "/image", self.output_prefix + "/" + self.input_type + "/image/slow"]
@@ -169,7 +175,7 @@ class CameraStream:
             encoding = "bgr8"  # cv_bridge::toCvCopy(image_msg, "bgr8") for compressed transports
         self._sync_taps()
         processed = self.pipe.apply(img.copy(), encoding, **({} if width is None else {"width": width}))
-        return self._messages(processed, self.pipe.last_encoding, stamp, frame_id)
+        return self._messages(processed, self.pipe.last_encoding, stamp, frame_id, geometry=self._geometry(img, encoding, width))
 
     def submit(self, image, encoding, stamp=0.0, frame_id="camera", width=None):
         """First half of the callback: enqueues upload, kernels and the download of the result AND of the taps the node
@@ -196,7 +202,7 @@ class CameraStream:
             dst["width"] = width
         ticket = self.pipe.submit(img, encoding, **{key: arr for key, arr in dst.items() if arr is not None})
         self._inflight = getattr(self, "_inflight", [])
-        self._inflight.append((ticket, stamp, frame_id))
+        self._inflight.append((ticket, stamp, frame_id, self._geometry(img, encoding, width)))
         return True
 
     def collect(self, copy=True):
@@ -206,9 +212,9 @@ class CameraStream:
         inflight = getattr(self, "_inflight", [])
         if not inflight:
             return []
-        ticket, stamp, frame_id = inflight.pop(0)
+        ticket, stamp, frame_id, geometry = inflight.pop(0)
         processed = self.pipe.collect(ticket, copy=copy)
-        return self._messages(processed, self.pipe.last_encoding, stamp, frame_id, copy=copy)
+        return self._messages(processed, self.pipe.last_encoding, stamp, frame_id, copy=copy, geometry=geometry)
 
     def on_image_pipelined(self, image, encoding, stamp=0.0, frame_id="camera", copy=True, width=None):
         """The same callback with one frame kept in flight (rip_submit / rip_collect): uploads, kernels and downloads of
@@ -224,14 +230,25 @@ class CameraStream:
         """Messages of the frame still in flight, if any."""
         return self.collect(copy=copy)
 
-    def _messages(self, processed, enc, stamp, frame_id, copy=True):
+    def _geometry(self, img, encoding, width):
+        """(rows, cols, channels, encoding) of an input frame, for the mask of the image it delivers; None while no mask is published."""
+        if self.pipe.get_rect_mask_mode() == "off" or not self.pipe.is_undistortion_enabled():
+            return None
+        return tuple(self.pipe._packed_geometry(img, encoding, width)) + (encoding,)
+
+    def _messages(self, processed, enc, stamp, frame_id, copy=True, geometry=None):
         out = []
         pipe = self.pipe
         if pipe.is_undistortion_enabled():
-            self._publish(out, processed, enc, stamp, frame_id, self.input_type + "_rect/image", self.input_type + "_rect/image/slow",
-                          pipe.get_rect_image_height(), pipe.get_rect_image_width(), pipe.get_rect_distortion_model(),
-                          pipe.get_rect_distortion_coefficients(), pipe.get_rect_camera_matrix(),
-                          pipe.get_rect_rectification_matrix(), pipe.get_rect_projection_matrix(), "_skipped_rect")
+            rect = (pipe.get_rect_image_height(), pipe.get_rect_image_width(), pipe.get_rect_distortion_model(),
+                    pipe.get_rect_distortion_coefficients(), pipe.get_rect_camera_matrix(),
+                    pipe.get_rect_rectification_matrix(), pipe.get_rect_projection_matrix())
+            self._publish(out, processed, enc, stamp, frame_id, self.input_type + "_rect/image", self.input_type + "_rect/image/slow", *rect,
+                          "_skipped_rect")
+            if geometry is not None and pipe.get_rect_mask_mode() != "off":
+                # the mask of the image just published -- the selected head's delivered mask, cached on the device between frames --
+                # with the rect CameraInfo; one message, no slow topic
+                self._publish(out, pipe.get_output_mask(*geometry), "mono8", stamp, frame_id, "image_mask", None, *rect, None)
         dist = (pipe.get_dist_image_height(), pipe.get_dist_image_width(), pipe.get_dist_distortion_model(),
                 pipe.get_dist_distortion_coefficients(), pipe.get_dist_camera_matrix(), pipe.get_dist_rectification_matrix(),
                 pipe.get_dist_projection_matrix())
@@ -263,6 +280,8 @@ class CameraStream:
         msg = {"topic": self.output_prefix + "/" + topic, "image": image, "encoding": encoding, "camera_info": info,
                "header": {"stamp": stamp, "frame_id": fid}}
         out.append(msg)
+        if slow_topic is None:
+            return
         skipped = getattr(self, counter)
         if skipped >= self.skip or self.skip <= 0:
             out.append({"topic": self.output_prefix + "/" + slow_topic, "image": image, "encoding": encoding, "camera_info": None,

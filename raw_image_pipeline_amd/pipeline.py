@@ -693,7 +693,43 @@ class RawImagePipeline:
         return self._get_image(IMAGE_COLOR, copy)
 
     def get_rect_mask(self):
+        """The valid-pixel mask of the last frame's geometry, an (R, C) uint8 array of the maps' size, under ``set_rect_mask``
+        "coverage" / "valid" after a frame that was undistorted; else empty, as the reference's never-written rect_mask_ is."""
         return self._get_image(IMAGE_RECT_MASK)
+
+    def set_rect_mask(self, mode):
+        """Extension: valid-pixel masks -- "off" (default), "coverage" (cv::remap of an all-255 image: 0 outside the source, 255
+        inside, in between on the rim) or "valid" (255 where the coverage is 255, else 0).  The frame calls are not affected; the
+        masks are built by ``get_rect_mask`` / ``get_output_mask`` and cached on the device.  include/rip.h rip_set_rect_mask."""
+        self._call("rip_set_rect_mask", mode.encode())
+
+    def get_rect_mask_mode(self):
+        return self._string("rip_get_rect_mask_mode")
+
+    def get_output_mask(self, rows, cols, channels, encoding):
+        """The mask of the image the selected head delivers for such an input frame, (H, W) uint8: the head's window, size, fit mode
+        and filter applied to the coverage (letterbox bands are 0), thresholded behind them under "valid".  No frame need have
+        been processed.  include/rip.h rip_get_output_mask."""
+        h, w = C.c_int(), C.c_int()
+        geometry = (int(rows), int(cols), int(channels), encoding.encode())
+        self._call("rip_get_output_mask", *geometry, None, C.c_size_t(0), C.byref(h), C.byref(w))
+        out = np.empty((h.value, w.value), np.uint8)
+        self._call("rip_get_output_mask", *geometry, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size), C.byref(h), C.byref(w))
+        return out
+
+    def get_output_mask_device(self, rows, cols, channels, encoding):
+        """(device pointer, row pitch in bytes, H, W) of the same mask where the handle caches it: written in the order of the
+        handle's stream, valid until that head's cache is dropped.  include/rip.h rip_get_output_mask_device."""
+        ptr, pitch, h, w = C.c_void_p(), C.c_size_t(), C.c_int(), C.c_int()
+        self._call("rip_get_output_mask_device", int(rows), int(cols), int(channels), encoding.encode(), C.byref(ptr), C.byref(pitch),
+                   C.byref(h), C.byref(w))
+        return ptr.value, pitch.value, h.value, w.value
+
+    def debug_rect_mask_info(self, head):
+        """(mask builds, head builds): test hook, include/rip.h rip_debug_rect_mask_info."""
+        m, k = C.c_int(), C.c_int()
+        self._call("rip_debug_rect_mask_info", int(head), C.byref(m), C.byref(k))
+        return m.value, k.value
 
     def get_processed_image(self, copy=True):
         return self._get_image(IMAGE_PROCESSED, copy)
