@@ -17,6 +17,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from raw_image_pipeline_amd import RawImagePipeline, synth  # noqa: E402
+from raw_image_pipeline_amd.pipeline import yuv_planes  # noqa: E402
 
 # example coefficients of the pinhole models (k1 k2 p1 p2 k3 [k4 k5 k6])
 PINHOLE_EXAMPLES = {"plumb_bob": [-0.28, 0.07, 2e-4, -3e-4, 0.0],
@@ -79,6 +80,15 @@ def main():
         read, picture = proc.get_output_window(h, w, 3, "bgr8")
         print("%s: reads %s of the image, picture at %s of %s" % (fit, read, picture, proc.process(before, "bgr8").shape))
     proc.set_output_fit("stretch")
+    # for an encoder: YUV 4:2:0 in one [3 H / 2, W] buffer, half the bytes of bgr8 on the way to the host
+    proc.set_output_size(w // 2, h // 2)
+    proc.set_output_format("nv12")
+    proc.set_output_yuv_matrix("bt709")
+    nv12 = proc.process(before, "bgr8")
+    y, cb, cr = yuv_planes(nv12, "nv12")
+    print("nv12:", nv12.shape, "Y", y.shape, "Cb / Cr", cb.shape, "mean (Y, Cb, Cr): %.1f %.1f %.1f" % (y.mean(), cb.mean(), cr.mean()))
+    proc.set_output_format("native")
+    proc.set_output_size(0, 0)
     try:
         from PIL import Image
         Image.fromarray(img[..., ::-1]).save(os.path.join(args.out_dir, "output_apply.png"))

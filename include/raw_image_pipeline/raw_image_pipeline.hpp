@@ -229,6 +229,9 @@ class RawImagePipeline {
   // class throw std::invalid_argument while one is set -- use the C interface (handle(), rip_apply / rip_apply_device) for them.
   void setOutputFormat(const std::string& name) { check(rip_set_output_format(h_, name.c_str())); }
   std::string getOutputFormat() const { return str(&rip_get_output_format); }
+  // the matrix and range of the formats "nv12" / "i420" (rip.h rip_set_output_yuv_matrix): "bt601" (default), "bt709", "bt601_full", "bt709_full"
+  void setOutputYuvMatrix(const std::string& name) { check(rip_set_output_yuv_matrix(h_, name.c_str())); }
+  std::string getOutputYuvMatrix() const { return str(&rip_get_output_yuv_matrix); }
   void setOutputNormalization(double divisor, const std::vector<double>& mean, const std::vector<double>& std_dev) {
     if (mean.size() != 3 || std_dev.size() != 3) throw std::invalid_argument("setOutputNormalization: mean and std take 3 values");
     check(rip_set_output_normalization(h_, divisor, mean.data(), std_dev.data()));

@@ -293,6 +293,7 @@ rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t capac
  *                      grey out, the primaries give R 76, G 150, B 29); uint8, 1 channel
  *   rgb_chw_f32 / rgb_chw_f16 / rgb_chw_bf16   planes R, G, B of T_c[v] (rip_set_output_normalization); 4 / 2 / 2 bytes per
  *   bgr_chw_f32 / bgr_chw_f16 / bgr_chw_bf16   planes B, G, R                       element; planar, 3 planes of out_rows x out_cols
+ *   nv12 / i420        YUV 4:2:0 for encoders (rip_set_output_yuv_matrix below); uint8, one channel of 3 H / 2 rows x W bytes
  * A format other than native needs a three-channel 8-bit pipeline result (Bayer 8-bit, 16-bit with a range, packed, bgr8 and rgb8
  * frames).  mono8 on a one-channel 8-bit result is the identity (no kernel); every other format on a one-channel result, and every
  * format other than native on a bgr16 result, fails the frame call and rip_query_output with RIP_ERR_INVALID_ARGUMENT: nothing is
@@ -315,6 +316,37 @@ rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t capac
  * parameters as they were. */
 rip_status rip_set_output_format(rip_pipeline* p, const char* name);
 rip_status rip_get_output_format(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
+/* The formats "nv12" and "i420": the delivered 8-bit B, G, R picture of H rows x W columns (F, or F' behind a resize, window or
+ * letterbox, the pad colour in it) as Y, Cb, Cr with one chroma sample per 2 x 2 block.  Exact integer arithmetic, this library's own
+ * definition from the ITU matrices, not pinned against any encoder's or OpenCV's converter (PARITY.md "Output formats: YUV 4:2:0"):
+ *   Y  = (yb B + yg G + yr R + (yoff << 15) + 16384) >> 15                       per pixel
+ *   Cb = min(255, (cbb SB + cbg SG + cbr SR + (128 << 17) + 65536) >> 17)         per 2 x 2 block, SB, SG, SR the plain sums of the
+ *   Cr = min(255, (crb SB + crg SG + crr SR + (128 << 17) + 65536) >> 17)         four pixels' channels: one rounding, no mean
+ * with the matrix `name` of rip_set_output_yuv_matrix, a setting of the selected output head like every rip_set_output_*:
+ *   bt601 (default)  yoff 16  y 3208 16520 8414   cb 14392  -9535 -4857   cr -2341 -12051 14392     limited range, Y 16..235
+ *   bt709            yoff 16  y 2032 20127 5983   cb 14392 -11094 -3298   cr -1320 -13072 14392     limited range
+ *   bt601_full       yoff 0   y 3735 19235 9798   cb 16384 -10855 -5529   cr -2664 -13720 16384     full range; Y is mono8's
+ *   bt709_full       yoff 0   y 2366 23436 6966   cb 16384 -12630 -3754   cr -1502 -14882 16384     full range
+ * (weights of B, G, R).  An unknown name: RIP_ERR_INVALID_ARGUMENT listing the names, nothing changed.  Works on RIP_DEVICE_NONE
+ * handles; without effect under any other format; rip_set_output_heads resets it for the heads it resets.  Params YAML:
+ * `yuv_matrix:` in `output:` and `output_1:` .. `output_7:`, absent = bt601, an invalid value fails the load.
+ * Layout: the delivered frame is ONE-CHANNEL, 3 H / 2 rows x W bytes (cv::cvtColor(..., COLOR_BGR2YUV_I420)'s convention): the frame
+ * calls and rip_query_output report out_rows = 3 H / 2, out_cols = W, out_channels = 1, encoding_out = the format's name;
+ * rip_query_output_bytes gives 3 H W / 2, elem_bytes 1, planar 0.  The capacity, pitch and stride rules are those of that image:
+ * out_step >= W, frame stride >= out_step * 3 H / 2, 16 MiB per row, 4 GiB per frame; any byte alignment of d_out and the pitch.
+ * With P the resolved row pitch: Y row y at y * P.  nv12: chroma row j (0 <= j < H / 2) at (H + j) * P, byte 2 i = Cb and byte
+ * 2 i + 1 = Cr of block (j, i).  i420: Cb row j at H * P + j * (P / 2), Cr row j at H * P + (H / 2) * (P / 2) + j * (P / 2); tight
+ * rows give the standard contiguous I420.  Written: W bytes of each Y row, W bytes of each nv12 chroma row, W / 2 bytes of each i420
+ * chroma row; row padding and the gaps between frames keep their bytes.
+ * What describes the PICTURE stays H x W: rip_get_output_camera_info (matrices unchanged by the format), rip_get_output_window,
+ * rip_get_output_mask; taps, white-balance info, the ccc track and the debug dumps stay on F; RIP_IMAGE_PROCESSED is empty.
+ * Refusals, RIP_ERR_INVALID_ARGUMENT before anything is enqueued (the ccc filter does not advance), from the frame calls, the heads
+ * calls (prefixed "output head <k>: ") and the queries, in this order: (1) the format rules above in their place -- a bgr16 result,
+ * then a one-channel result; (2) an odd W or an odd H of the delivered picture, the message names the size; (3) rip_apply_device and
+ * rip_apply_device_heads under i420: an odd row pitch.
+ * Cost: one launch per batch in the converter's place (3 bytes read, 1.5 written per pixel) and the staging image of F as above. */
+rip_status rip_set_output_yuv_matrix(rip_pipeline* p, const char* name);
+rip_status rip_get_output_yuv_matrix(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
 /* Normalisation of the planar output formats; mean and std hold 3 values in the order of the format's planes.  Defaults:
  * divisor 255, mean (0, 0, 0), std (1, 1, 1); divisor 1 gives the raw values.  For plane c and channel value v in 0..255 the
  * delivered element is the table entry T_c[v]: y = (v / divisor - mean_c) / std_c evaluated in double with every operation

@@ -1,6 +1,6 @@
-"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the tables COMPANIONS, HEAD_LIBRARIES and
-MASK_LIBRARIES below: the kernels of the output stage, the four libraries of the resize stage, the output heads' copy and the
-valid-pixel masks -- for gfx950 with hipcc.
+"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the tables COMPANIONS, HEAD_LIBRARIES,
+MASK_LIBRARIES and YUV_LIBRARIES below: the kernels of the output stage, the four libraries of the resize stage, the output heads'
+copy, the valid-pixel masks and the YUV 4:2:0 formats -- for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_round_map.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", "rip_mask.hpp", os.path.join("..", "..", "include", "rip.h")]
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_round_map.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", "rip_mask.hpp", "rip_yuv.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
 # what tests/variant_cases.py closes over; each companion's table is closed by a tests/*_variant_cases.py of its own.
 # librip_hip.so -- every build of it: the default one, the sanitizer build and the A/B variants under variants/ -- links against
@@ -55,6 +55,15 @@ MASK_LIBRARIES = {
     "mask": (os.path.join(HERE, "librip_mask_hip.so"), ["rip_mask.hip"], ["rip_mask.hpp", "rip_round_map.hpp"], "build_mask"),
 }
 OUT_MASK, MASK_SOURCES, MASK_HEADERS = MASK_LIBRARIES["mask"][:3]
+# A fourth table of the same rows: the library behind the YUV 4:2:0 output formats.  tests/test_mask_variants.py closes _all_keys()
+# at the three tables above, so this one is reached through _link_keys(), the list that everything which builds, dates or links the
+# libraries goes by.
+#   yuv   yuv420_kernel<true / false>, the delivered BGR picture as nv12 / i420 (rip_set_output_format, rip_set_output_yuv_matrix);
+#         tests/yuv_variant_cases.py
+YUV_LIBRARIES = {
+    "yuv": (os.path.join(HERE, "librip_yuv_hip.so"), ["rip_yuv.hip"], ["rip_yuv.hpp"], "build_yuv"),
+}
+OUT_YUV, YUV_SOURCES, YUV_HEADERS = YUV_LIBRARIES["yuv"][:3]
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -78,11 +87,16 @@ def _tables():
 
 
 def _row(key):
-    return next(t[key] for t in _tables() if key in t)
+    return next(t[key] for t in _tables() + (YUV_LIBRARIES,) if key in t)
 
 
 def _all_keys():
     return [key for t in _tables() for key in t]
+
+
+def _link_keys():
+    """Every library librip_hip.so links against: the three closed tables and YUV_LIBRARIES."""
+    return _all_keys() + list(YUV_LIBRARIES)
 
 
 def _companion_up_to_date(key):
@@ -95,7 +109,7 @@ def _companion_up_to_date(key):
 
 
 def companions_up_to_date():
-    return all(_companion_up_to_date(key) for key in _all_keys())
+    return all(_companion_up_to_date(key) for key in _link_keys())
 
 
 def up_to_date():
@@ -140,6 +154,7 @@ fit_up_to_date, build_fit = functools.partial(_companion_up_to_date, "fit"), fun
 aa_up_to_date, build_aa = functools.partial(_companion_up_to_date, "aa"), functools.partial(_build_companion, "aa")
 heads_up_to_date, build_heads = functools.partial(_companion_up_to_date, "heads"), functools.partial(_build_companion, "heads")
 mask_up_to_date, build_mask = functools.partial(_companion_up_to_date, "mask"), functools.partial(_build_companion, "mask")
+yuv_up_to_date, build_yuv = functools.partial(_companion_up_to_date, "yuv"), functools.partial(_build_companion, "yuv")
 
 
 # --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under
@@ -173,7 +188,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
             return out
     if out is None and not force and up_to_date():
         return OUT
-    for key in _all_keys():  # every build of librip_hip.so links against all of them; `force` is about the library asked for
+    for key in _link_keys():  # every build of librip_hip.so links against all of them; `force` is about the library asked for
         _build_companion(key, verbose=verbose)
     out = out or OUT
     objs = []
@@ -197,7 +212,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
         if verbose and log.strip():
             print(log)
     # the companions are found next to the library ($ORIGIN) or one directory up (variants/*.so)
-    companion = ["-L" + HERE] + ["-l:" + os.path.basename(_row(key)[0]) for key in _all_keys()] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    companion = ["-L" + HERE] + ["-l:" + os.path.basename(_row(key)[0]) for key in _link_keys()] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
     cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

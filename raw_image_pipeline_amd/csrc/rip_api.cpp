@@ -411,9 +411,9 @@ rip_status rip_get_output_mask(rip_pipeline* p, int rows, int cols, int channels
   return guarded(p, [&] {
     int mode = 0;
     const Plan pl = output_mask_plan(p, rows, cols, channels, encoding, &mode);
-    const size_t bytes = (size_t)pl.dl_rows * (size_t)pl.dl_cols;
+    const size_t bytes = (size_t)pl.img_rows * (size_t)pl.dl_cols;  // a mask is the picture's, whatever the format
     if (out && capacity < bytes) throw CapacityError("mask buffer too small: need " + std::to_string(bytes) + " bytes");
-    if (height) *height = pl.dl_rows;
+    if (height) *height = pl.img_rows;
     if (width) *width = pl.dl_cols;
     if (!out) return;  // the geometry only
     need_device(p);
@@ -546,6 +546,8 @@ RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) th
            rip::check_debayer_method(s); p->m.debayer_method = s)
 RIP_SETTER(rip_set_output_format, (rip_pipeline * p, const char* s), drop_head_mask(p); if (!s) throw InvalidArgument("null string");
            (void)rip::output_format_id(s); if (p->m.out().out_format != s) p->out_table[p->m.selected].dirty = true; p->m.out().out_format = s)
+RIP_SETTER(rip_set_output_yuv_matrix, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
+           (void)rip::output_yuv_matrix_id(s); p->m.out().out_yuv_matrix = s)
 RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, const double* mean, const double* sd), drop_head_mask(p);
            if (!mean || !sd) throw InvalidArgument("null mean or std");
            rip::check_output_normalization(divisor, mean, sd); p->m.out().out_divisor = divisor;
@@ -631,6 +633,7 @@ int rip_get_rect_image_width(const rip_pipeline* p) { return p ? p->m.rect_w : 0
   }
 RIP_GET_STRING(rip_get_debayer_method, p->m.debayer_method)
 RIP_GET_STRING(rip_get_output_format, p->m.out().out_format)
+RIP_GET_STRING(rip_get_output_yuv_matrix, p->m.out().out_yuv_matrix)
 RIP_GET_STRING(rip_get_output_interpolation, p->m.out().out_interp)
 RIP_GET_STRING(rip_get_output_fit, p->m.out().out_fit)
 
@@ -724,7 +727,7 @@ rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int c
       pr[7] *= b;
     } else if (pl.rsz_active) {
       // the inverse of the tables' pixel-centre mapping u = (u' + 0.5) / a - 0.5 (PARITY.md "Resize")
-      const double a = (double)pl.dl_cols / pl.out_cols, b = (double)pl.dl_rows / pl.out_rows;
+      const double a = (double)pl.dl_cols / pl.out_cols, b = (double)pl.img_rows / pl.out_rows;
       k[0] *= a;
       k[1] *= a;
       k[2] = a * (k[2] + 0.5) - 0.5;
@@ -738,7 +741,7 @@ rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int c
       pr[6] = b * (pr[6] + 0.5) - 0.5;
       pr[7] *= b;
     }
-    if (height) *height = pl.dl_rows;
+    if (height) *height = pl.img_rows;  // the picture, not the buffer a YUV format delivers it in
     if (width) *width = pl.dl_cols;
     if (K) std::memcpy(K, k, sizeof(k));
     if (P) std::memcpy(P, pr, sizeof(pr));

@@ -503,7 +503,7 @@ struct HeadPrep {
 size_t rsz_bytes(const Plan& pl, int n) {
   if (!pl.rsz_active || pl.out_fmt == rip::OUT_NATIVE) return 0;
   const size_t pitch = ((size_t)pl.dl_cols * pl.channels + 15) & ~(size_t)15;
-  return pitch * (size_t)pl.dl_rows * (size_t)n;
+  return pitch * (size_t)pl.img_rows * (size_t)n;
 }
 
 HeadPrep prepare_head(rip_pipeline* p, const Plan& pl, const FrameView& staged, int n) {
@@ -517,7 +517,7 @@ HeadPrep prepare_head(rip_pipeline* p, const Plan& pl, const FrameView& staged, 
     else hp.rt = ensure_resize_tables(p, pl.head, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w);
     if (pl.out_fmt != rip::OUT_NATIVE) {  // the converter's source alignment
       const size_t pitch = ((size_t)pl.dl_cols * pl.channels + 15) & ~(size_t)15;
-      hp.converted_from = {nullptr, pitch, pitch * (size_t)pl.dl_rows, pl.dl_rows, pl.dl_cols};
+      hp.converted_from = {nullptr, pitch, pitch * (size_t)pl.img_rows, pl.img_rows, pl.dl_cols};
       p->d_rsz.reserve(rsz_bytes(pl, n));  // several heads: reserved for the largest before the first of them is prepared
       hp.converted_from.ptr = p->d_rsz.as<uint8_t>();
     }
@@ -589,7 +589,7 @@ void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const Fra
     f.dst = whole_to.ptr;
     f.dst_step = whole_to.step;
     f.dst_frame_stride = whole_to.frame_stride;
-    f.rows = pl.dl_rows;
+    f.rows = pl.img_rows;
     f.cols = pl.dl_cols;
     f.pic_x = pl.pic_x;
     f.pic_y = pl.pic_y;
@@ -601,6 +601,25 @@ void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const Fra
     launched(rip::launch_fit_pad(f, p->stream, &info), info, "the letterbox pad", n);
   }
   if (pl.out_fmt == rip::OUT_NATIVE) return;
+  if (rip::output_format_yuv(pl.out_fmt)) {  // librip_yuv_hip.so's kernel in the converter's place, from the same source
+    rip::Yuv420Params c = {};
+    c.src = hp.converted_from.ptr;
+    c.src_step = hp.converted_from.step;
+    c.src_frame_stride = hp.converted_from.frame_stride;
+    c.dst = dst.ptr;
+    c.dst_step = dst.step;
+    c.dst_frame_stride = dst.frame_stride;
+    c.rows = pl.img_rows;
+    c.cols = pl.dl_cols;
+    c.n_frames = n;
+    c.semi_planar = pl.out_fmt == rip::OUT_NV12 ? 1 : 0;
+    int coef[9];
+    rip::output_yuv_matrix(pl.yuv_matrix, coef, &c.m.yoff);
+    for (int i = 0; i < 3; i++) c.m.y[i] = coef[i], c.m.cb[i] = coef[3 + i], c.m.cr[i] = coef[6 + i];
+    rip::YuvLaunchInfo yuv_info = {};
+    launched(rip::launch_yuv420(c, p->stream, &yuv_info), yuv_info, "the YUV 4:2:0 converter", n);
+    return;
+  }
   rip::OutputConvertParams c = {};
   c.src = hp.converted_from.ptr;
   c.src_step = hp.converted_from.step;
@@ -608,7 +627,7 @@ void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const Fra
   c.dst = dst.ptr;
   c.dst_step = dst.step;
   c.dst_frame_stride = dst.frame_stride;
-  c.rows = pl.dl_rows;
+  c.rows = pl.img_rows;
   c.cols = pl.dl_cols;
   c.n_frames = n;
   c.format = pl.out_fmt;
@@ -767,6 +786,7 @@ ConstFrameView ensure_mask_head(rip_pipeline* p, const Plan& frame_pl, int mode)
   pl.out_elem_bytes = pl.dl_elem_bytes = 1;
   pl.fmt_active = pl.dl_planar = false;
   pl.out_fmt = rip::OUT_NATIVE;
+  pl.dl_rows = pl.img_rows;  // a mask ignores the format: the picture's rows under a YUV format too
   for (uint8_t& c : pl.pad) c = 0;
   const bool identity = identity_head(pl), binary = mode == 2;
   MaskHeadConst& mh = p->mask_head[pl.head];

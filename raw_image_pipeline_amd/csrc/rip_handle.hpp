@@ -23,6 +23,7 @@
 #include "rip_heads.hpp"
 #include "rip_mask.hpp"
 #include "rip_resize.hpp"
+#include "rip_yuv.hpp"
 
 namespace rip {
 // Launch record (rip_kernels.hpp): the text of a handle's log, one launch per line
@@ -137,13 +138,17 @@ struct Plan {
   // the resize stage (rip_set_output_size; filled in by apply_output_format too): the delivered rows x cols -- out_rows / out_cols
   // stay the pipeline's own image F -- and whether a resize kernel runs between F and the converter (a target other than F's size)
   int dl_rows = 0, dl_cols = 0;
+  // rows of the PICTURE F' that is delivered (what the resize writes and the converter reads; dl_cols is its width): dl_rows, except
+  // under a YUV 4:2:0 format, whose delivered one-channel buffer has 3 * img_rows / 2 rows (rip_yuv.hpp)
+  int img_rows = 0;
+  int yuv_matrix = 0;  // rip::output_yuv_matrix_id of the head's matrix; read under OUT_NV12 / OUT_I420 only
   bool rsz_active = false;
   // which filter's kernel that is, as rip::output_interpolation_id numbers them: 0 the linear path's (also the exact 2 x 2 case under
   // "area", which is its mean kernel, and a copy under any name), 1 the area interpolation's (rip_area.hpp), 2 / 3 the antialiased
   // linear / cubic filter's (rip_aa.hpp)
   int rsz_kind = 0;
   // the window and the fit mode (rip_set_output_roi, rip_set_output_fit; rip::output_window_geometry): win_* is the rectangle of F
-  // the resize reads, pic_* the rectangle of the delivered dl_rows x dl_cols image it writes; every other delivered pixel gets `pad`
+  // the resize reads, pic_* the rectangle of the delivered img_rows x dl_cols picture it writes; every other delivered pixel gets `pad`
   // (channels bytes).  fit_geometry: a window or a fit mode other than "stretch" is set, so these fields decide (without either
   // the window is F, the picture is the delivered image and the code paths are the ones from before there was a window).
   bool fit_geometry = false;
@@ -151,7 +156,7 @@ struct Plan {
   int pic_x = 0, pic_y = 0, pic_w = 0, pic_h = 0;
   uint8_t pad[4] = {0, 0, 0, 0};
   bool win_is_frame() const { return win_x == 0 && win_y == 0 && win_w == out_cols && win_h == out_rows; }
-  bool pic_is_delivered() const { return pic_w == dl_cols && pic_h == dl_rows; }
+  bool pic_is_delivered() const { return pic_w == dl_cols && pic_h == img_rows; }
 };
 
 // n frames of rows x cols pixels in device memory: rows `step` bytes apart, frames `frame_stride` bytes apart (both resolved,

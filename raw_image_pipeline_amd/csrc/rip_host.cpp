@@ -294,6 +294,11 @@ OutputHead output_head_from_node(const YamlNode& o, const std::string& sec) {
   // absent keys mean the defaults, an invalid value fails the load like an unknown debayer method
   const std::string out_format = o.get("format", std::string("native"));
   (void)output_format_id(out_format);
+  // extension key output: yuv_matrix: bt601 | bt709 | bt601_full | bt709_full (rip_set_output_yuv_matrix); absent means bt601
+  const std::string out_yuv_matrix = o.get("yuv_matrix", std::string("bt601"));
+  (void)output_yuv_matrix_id(out_yuv_matrix);
+  if (o["yuv_matrix"].defined() && o["yuv_matrix"].kind != YamlNode::Scalar)
+    throw std::invalid_argument(sec + ": yuv_matrix: one word is expected, \"bt601\", \"bt709\", \"bt601_full\" or \"bt709_full\"");
   const double out_divisor = o.get("divisor", 255.0);
   double out_mean[3] = {0, 0, 0}, out_std[3] = {1, 1, 1};
   for (int which = 0; which < 2; which++) {
@@ -348,6 +353,7 @@ OutputHead output_head_from_node(const YamlNode& o, const std::string& sec) {
   h.out_h = out_h;
   h.out_interp = out_interp;
   h.out_format = out_format;
+  h.out_yuv_matrix = out_yuv_matrix;
   h.out_divisor = out_divisor;
   for (int i = 0; i < 3; i++) h.out_mean[i] = out_mean[i], h.out_std[i] = out_std[i];
   return h;
@@ -482,8 +488,15 @@ void check_debayer_method(const std::string& method) {
 }
 
 namespace {
-const char* const kOutputFormatNames[9] = {"native", "rgb8", "mono8", "rgb_chw_f32", "rgb_chw_f16", "rgb_chw_bf16",
-                                           "bgr_chw_f32", "bgr_chw_f16", "bgr_chw_bf16"};  // index = rip_output.hpp OutputFormat
+const char* const kOutputFormatNames[11] = {"native", "rgb8", "mono8", "rgb_chw_f32", "rgb_chw_f16", "rgb_chw_bf16",
+                                            "bgr_chw_f32", "bgr_chw_f16", "bgr_chw_bf16", "nv12", "i420"};  // index = rip_output.hpp OutputFormat
+// index = the id output_yuv_matrix_id returns; the rows are rip_yuv.hpp's YuvMatrix (PARITY.md "Output formats: YUV 4:2:0")
+const char* const kYuvMatrixNames[4] = {"bt601", "bt709", "bt601_full", "bt709_full"};
+const int kYuvMatrices[4][10] = {
+    {3208, 16520, 8414, 14392, -9535, -4857, -2341, -12051, 14392, 16},
+    {2032, 20127, 5983, 14392, -11094, -3298, -1320, -13072, 14392, 16},
+    {3735, 19235, 9798, 16384, -10855, -5529, -2664, -13720, 16384, 0},
+    {2366, 23436, 6966, 16384, -12630, -3754, -1502, -14882, 16384, 0}};
 
 uint32_t float_bits(float f) {
   uint32_t x;
@@ -523,11 +536,26 @@ uint16_t f32_to_bf16(float f) {
 
 int output_format_id(const std::string& name) {
   std::string names;
-  for (int i = 0; i < 9; i++) {
+  for (int i = 0; i < 11; i++) {
     if (name == kOutputFormatNames[i]) return i;
     names += std::string(i ? ", '" : "'") + kOutputFormatNames[i] + "'";
   }
   throw std::invalid_argument("Output format [" + name + "] not supported. Supported formats: " + names);
+}
+
+int output_yuv_matrix_id(const std::string& name) {
+  std::string names;
+  for (int i = 0; i < 4; i++) {
+    if (name == kYuvMatrixNames[i]) return i;
+    names += std::string(i ? ", '" : "'") + kYuvMatrixNames[i] + "'";
+  }
+  throw std::invalid_argument("Output YUV matrix [" + name + "] not supported. Supported matrices: " + names);
+}
+
+void output_yuv_matrix(int id, int coef[9], int* yoff) {
+  if (id < 0 || id > 3) throw std::invalid_argument("no such YUV matrix");
+  for (int i = 0; i < 9; i++) coef[i] = kYuvMatrices[id][i];
+  *yoff = kYuvMatrices[id][9];
 }
 
 void check_output_normalization(double divisor, const double mean[3], const double sd[3]) {

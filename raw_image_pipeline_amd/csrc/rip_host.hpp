@@ -53,6 +53,8 @@ struct OutputHead {
   // frame calls deliver ("native": the pipeline's own image) and the normalisation of the planar float formats, mean / std in
   // the order of the format's planes
   std::string out_format = "native";
+  // extension (rip_set_output_yuv_matrix): the matrix and range of the formats "nv12" / "i420"; without effect under any other format
+  std::string out_yuv_matrix = "bt601";
   double out_divisor = 255.0, out_mean[3] = {0, 0, 0}, out_std[3] = {1, 1, 1};
   // extension (rip_set_output_size): the size the delivered frames are resized to, in front of the output format; (0, 0) = off
   int out_w = 0, out_h = 0;
@@ -134,6 +136,11 @@ void check_debayer_16bit_range(int black, int white);
 // the output formats rip_set_output_format accepts: the id (rip_output.hpp OutputFormat; 0 = "native"); throws
 // std::invalid_argument listing the names for any other name
 int output_format_id(const std::string& name);
+// the matrices rip_set_output_yuv_matrix accepts: 0 "bt601", 1 "bt709", 2 "bt601_full", 3 "bt709_full"; throws std::invalid_argument
+// listing the names otherwise
+int output_yuv_matrix_id(const std::string& name);
+// the integers of matrix `id` (PARITY.md "Output formats: YUV 4:2:0"): coef = yb, yg, yr, cbb, cbg, cbr, crb, crg, crr and the Y offset
+void output_yuv_matrix(int id, int coef[9], int* yoff);
 // the normalisations rip_set_output_normalization accepts: everything finite, divisor != 0, std_c != 0; throws std::invalid_argument
 void check_output_normalization(double divisor, const double mean[3], const double sd[3]);
 // The 3 x 256 table of a planar format (ids 3 .. 8), plane-major, in the format's element type: for plane c and value v,

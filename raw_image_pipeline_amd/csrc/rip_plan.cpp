@@ -152,7 +152,7 @@ void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
   pl.dl_channels = pl.channels;
   pl.dl_elem_bytes = pl.out_elem_bytes;
   // the resize stage (rip_set_output_size) sits between F and the format: the delivered geometry is the target's
-  pl.dl_rows = pl.out_rows;
+  pl.img_rows = pl.out_rows;
   pl.dl_cols = pl.out_cols;
   pl.win_w = pl.pic_w = pl.out_cols;
   pl.win_h = pl.pic_h = pl.out_rows;
@@ -169,11 +169,11 @@ void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
     pl.win_x = src[0], pl.win_y = src[1], pl.win_w = src[2], pl.win_h = src[3];
     pl.pic_x = dst[0], pl.pic_y = dst[1], pl.pic_w = dst[2], pl.pic_h = dst[3];
     pl.dl_cols = m.out_w > 0 ? m.out_w : pl.win_w;
-    pl.dl_rows = m.out_w > 0 ? m.out_h : pl.win_h;
+    pl.img_rows = m.out_w > 0 ? m.out_h : pl.win_h;
     if (pl.channels == 1) pl.pad[0] = (uint8_t)rip::output_pad_grey(m.out_pad[0], m.out_pad[1], m.out_pad[2]);
     else for (int i = 0; i < 3; i++) pl.pad[i] = (uint8_t)m.out_pad[i];
     // all of F delivered as it is: today's identity rule, nothing is launched
-    if (!(pl.win_is_frame() && pl.pic_is_delivered() && pl.dl_cols == pl.out_cols && pl.dl_rows == pl.out_rows)) {
+    if (!(pl.win_is_frame() && pl.pic_is_delivered() && pl.dl_cols == pl.out_cols && pl.img_rows == pl.out_rows)) {
       if (pl.out_rows > rip::kRszMaxSide || pl.out_cols > rip::kRszMaxSide)
         throw InvalidArgument("output size: the pipeline's image of " + std::to_string(pl.out_cols) + " x " + std::to_string(pl.out_rows) +
                               " is larger than the " + std::to_string(rip::kRszMaxSide) + " pixels per side the resize takes");
@@ -207,12 +207,13 @@ void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
         pl.rsz_kind = filter;
       }
       pl.rsz_active = true;
-      pl.dl_rows = m.out_h;
+      pl.img_rows = m.out_h;
       pl.dl_cols = m.out_w;
       pl.pic_w = pl.dl_cols;
-      pl.pic_h = pl.dl_rows;
+      pl.pic_h = pl.img_rows;
     }
   }
+  pl.dl_rows = pl.img_rows;
   const int fmt = rip::output_format_id(m.out_format);
   if (fmt == rip::OUT_NATIVE) return;
   pl.fmt_active = true;
@@ -223,6 +224,15 @@ void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
       throw InvalidArgument("output format [" + m.out_format + "] needs a three-channel pipeline result; this frame gives one channel ('mono8' and 'native' apply)");
     pl.encoding_out = "mono8";  // the identity: no kernel
     return;
+  }
+  if (rip::output_format_yuv(fmt)) {
+    // 4:2:0 has one chroma sample per 2 x 2 block of the delivered picture.  The delivered buffer is the one-channel image of 3 H / 2
+    // rows x W bytes that holds the three planes; img_rows stays the picture's H (PARITY.md "Output formats: YUV 4:2:0")
+    if ((pl.dl_cols | pl.img_rows) & 1)
+      throw InvalidArgument("output format [" + m.out_format + "] needs a delivered picture of even width and height (one chroma sample per 2 x 2 block); this one is " +
+                            std::to_string(pl.dl_cols) + " x " + std::to_string(pl.img_rows));
+    pl.dl_rows = pl.img_rows / 2 * 3;
+    pl.yuv_matrix = rip::output_yuv_matrix_id(m.out_yuv_matrix);
   }
   pl.out_fmt = fmt;
   pl.dl_channels = rip::output_format_channels(fmt);
@@ -246,6 +256,8 @@ FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, si
   const size_t e = (size_t)pl.dl_elem_bytes, row = v.step;
   if (out_step) v.step = out_step;
   if (v.step < row) throw InvalidArgument("output row pitch smaller than a row");
+  // i420: the chroma rows are half a pitch apart
+  if (pl.out_fmt == rip::OUT_I420 && (v.step & 1)) throw InvalidArgument("output format [i420] needs an even row pitch (a chroma row is half of it), got " + std::to_string(v.step));
   const unsigned long long frame = (unsigned long long)v.step * pl.dl_rows * (pl.dl_planar ? 3ull : 1ull);
   v.frame_stride = out_frame_stride ? out_frame_stride : (size_t)frame;
   if (v.frame_stride < frame) throw InvalidArgument("output frame stride smaller than a frame");

@@ -44,6 +44,30 @@ OUTPUT_FORMATS = {
     "rgb_chw_f32": (np.float32, True, 3), "rgb_chw_f16": (np.float16, True, 3), "rgb_chw_bf16": (np.uint16, True, 3),
     "bgr_chw_f32": (np.float32, True, 3), "bgr_chw_f16": (np.float16, True, 3), "bgr_chw_bf16": (np.uint16, True, 3),
 }
+# The YUV 4:2:0 formats, rows of the same shape: one channel of 3 H / 2 rows x W bytes that holds the three planes (yuv_planes takes it
+# apart).  A table of its own: they are delivered like a native one-channel image -- uint8, [3 H / 2, W], no tensor dtype to pick --
+# and the seeded draws of the suite's fuzzes are taken over OUTPUT_FORMATS as it stands.
+YUV_OUTPUT_FORMATS = {"nv12": (np.uint8, False, 1), "i420": (np.uint8, False, 1)}
+YUV_MATRICES = ("bt601", "bt709", "bt601_full", "bt709_full")
+
+
+def yuv_planes(frame, fmt):
+    """(Y, Cb, Cr) views of a delivered "nv12" / "i420" frame: a numpy array or torch tensor of shape [3 H / 2, W] (or with leading
+    batch axes).  Y is [H, W], Cb and Cr are [H / 2, W / 2]; under "nv12" they are strided views of the interleaved chroma rows,
+    under "i420" views of the two contiguous planes behind Y.  ``frame`` must hold tightly packed rows (what the host calls and
+    ``apply_device`` without ``out`` return)."""
+    if fmt not in ("nv12", "i420"):
+        raise ValueError("yuv_planes: 'nv12' or 'i420', got %r" % (fmt,))
+    rows, w = frame.shape[-2], frame.shape[-1]
+    if rows % 3 or w % 2:
+        raise ValueError("yuv_planes: a [3 H / 2, W] frame with even H and W is expected, got %s" % (tuple(frame.shape),))
+    h = rows // 3 * 2
+    y, c = frame[..., :h, :], frame[..., h:, :]
+    if fmt == "nv12":
+        return y, c[..., 0::2], c[..., 1::2]
+    lead = tuple(frame.shape[:-2])
+    planes = c.reshape(lead + (2, h // 2, w // 2))  # h / 2 rows of w bytes are h / 2 rows of w / 2 bytes twice
+    return y, planes[..., 0, :, :], planes[..., 1, :, :]
 
 
 def _delivered(rows, cols, channels, encoding):
@@ -836,6 +860,15 @@ class RawImagePipeline:
 
     def get_output_format(self):
         return self._string("rip_get_output_format")
+
+    def set_output_yuv_matrix(self, name):
+        """Extension: the matrix and range of the formats "nv12" / "i420" -- "bt601" (default), "bt709", "bt601_full" or
+        "bt709_full"; a setting of the selected output head, without effect under any other format.  The frame calls then deliver
+        uint8 [3 H / 2, W] (``yuv_planes`` takes it apart).  include/rip.h rip_set_output_yuv_matrix."""
+        self._call("rip_set_output_yuv_matrix", name.encode())
+
+    def get_output_yuv_matrix(self):
+        return self._string("rip_get_output_yuv_matrix")
 
     def set_output_normalization(self, divisor=255.0, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
         """Extension: the planar formats deliver ``(v / divisor - mean[c]) / std[c]`` for plane c (mean / std in the order of
