@@ -1,10 +1,10 @@
-"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the tables COMPANIONS, HEAD_LIBRARIES,
-MASK_LIBRARIES and YUV_LIBRARIES below: the kernels of the output stage, the four libraries of the resize stage, the output heads'
-copy, the valid-pixel masks and the YUV 4:2:0 formats -- for gfx950 with hipcc.
+"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the table COMPANIONS below: the kernels of
+the output stage, the four libraries of the resize stage, the output heads' copy, the valid-pixel masks and the YUV 4:2:0 formats --
+for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
-import functools
+import collections
 import os
 import subprocess
 import sys
@@ -12,58 +12,39 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
-SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
+SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_output_stage.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
 HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_round_map.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", "rip_mask.hpp", "rip_yuv.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
 # what tests/variant_cases.py closes over; each companion's table is closed by a tests/*_variant_cases.py of its own.
 # librip_hip.so -- every build of it: the default one, the sanitizer build and the A/B variants under variants/ -- links against
-# these files and finds them through its $ORIGIN rpath.  A companion's interface is its headers alone, so a rebuild of it does not
-# ask for a relink of the libraries that use it.  One row each: (library, sources, headers, build directory).
-#   out   the output stage's kernels (rip_set_output_format) and their one launch function; tests/output_variant_cases.py
-#   rsz   the resize stage's kernels (rip_set_output_size); tests/resize_variant_cases.py
-#   area  the resize stage's area interpolation (rip_set_output_interpolation); tests/area_variant_cases.py
-#   fit   the resize stage's kernels that read a window of the image, and the pad kernel of the letterbox (rip_set_output_roi,
-#         rip_set_output_fit); rip_fit.hpp takes its parameter structs from the two headers before it; tests/fit_variant_cases.py
-#   aa    the resize stage's antialiased filters (rip_set_output_interpolation "linear_aa" / "cubic_aa"), whole frame and window;
-#         its device code is rip_aa_dev.hpp; tests/aa_variant_cases.py
-# rip_resize_dev.hpp is the device code and the launch checks the libraries of the resize stage share.
-RESIZE_SHARED = ["rip_resize_dev.hpp", "rip_resize.hpp", "rip_area.hpp"]
-COMPANIONS = {
-    "out": (os.path.join(HERE, "librip_out_hip.so"), ["rip_output.hip"], ["rip_output.hpp"], "build_out"),
-    "rsz": (os.path.join(HERE, "librip_rsz_hip.so"), ["rip_resize.hip"], RESIZE_SHARED, "build_rsz"),
-    "area": (os.path.join(HERE, "librip_area_hip.so"), ["rip_area.hip"], RESIZE_SHARED, "build_area"),
-    "fit": (os.path.join(HERE, "librip_fit_hip.so"), ["rip_fit.hip"], ["rip_fit.hpp"] + RESIZE_SHARED, "build_fit"),
-    "aa": (os.path.join(HERE, "librip_aa_hip.so"), ["rip_aa.hip"], ["rip_aa.hpp", "rip_aa_dev.hpp"] + RESIZE_SHARED, "build_aa"),
-}
-OUT_COMPANION, COMPANION_SOURCES, COMPANION_HEADERS = COMPANIONS["out"][:3]
-OUT_RSZ, RSZ_SOURCES, RSZ_HEADERS = COMPANIONS["rsz"][:3]
-OUT_AREA, AREA_SOURCES, AREA_HEADERS = COMPANIONS["area"][:3]
-OUT_FIT, FIT_SOURCES, FIT_HEADERS = COMPANIONS["fit"][:3]
-OUT_AA, AA_SOURCES, AA_HEADERS = COMPANIONS["aa"][:3]
-# A second table of the same rows beside COMPANIONS (which tests/test_aa_variants.py closes at five): the libraries behind the output
-# heads.  Built, dated, linked and found through $ORIGIN exactly like the companions, in every build.
+# these files, in the table's order, and finds them through its $ORIGIN rpath.  A companion's interface is its headers alone, so a
+# rebuild of it does not ask for a relink of the libraries that use it.  One row each, closed by tests/test_companion_libraries.py:
+#   out    the output stage's kernels (rip_set_output_format) and their one launch function; tests/output_variant_cases.py
+#   rsz    the resize stage's kernels (rip_set_output_size); tests/resize_variant_cases.py
+#   area   the resize stage's area interpolation (rip_set_output_interpolation); tests/area_variant_cases.py
+#   fit    the resize stage's kernels that read a window of the image, and the pad kernel of the letterbox (rip_set_output_roi,
+#          rip_set_output_fit); rip_fit.hpp takes its parameter structs from the two headers before it; tests/fit_variant_cases.py
+#   aa     the resize stage's antialiased filters (rip_set_output_interpolation "linear_aa" / "cubic_aa"), whole frame and window;
+#          its device code is rip_aa_dev.hpp; tests/aa_variant_cases.py
 #   heads  head_copy_kernel, the copy that delivers F to a further head that asks for it as it is (rip_apply_device_heads);
 #          tests/heads_variant_cases.py
-HEAD_LIBRARIES = {
-    "heads": (os.path.join(HERE, "librip_heads_hip.so"), ["rip_heads.hip"], ["rip_heads.hpp"], "build_heads"),
-}
-OUT_HEADS, HEADS_SOURCES, HEADS_HEADERS = HEAD_LIBRARIES["heads"][:3]
-# A third table of the same rows (tests/test_heads.py closes HEAD_LIBRARIES at one): the library behind the valid-pixel masks.
-#   mask  rect_mask_kernel, the coverage mask of an undistortion from its maps alone, and mask_threshold_kernel (rip_set_rect_mask,
-#         rip_get_output_mask); rip_round_map.hpp is the map quantiser it shares with the remap kernels; tests/mask_variant_cases.py
-MASK_LIBRARIES = {
-    "mask": (os.path.join(HERE, "librip_mask_hip.so"), ["rip_mask.hip"], ["rip_mask.hpp", "rip_round_map.hpp"], "build_mask"),
-}
-OUT_MASK, MASK_SOURCES, MASK_HEADERS = MASK_LIBRARIES["mask"][:3]
-# A fourth table of the same rows: the library behind the YUV 4:2:0 output formats.  tests/test_mask_variants.py closes _all_keys()
-# at the three tables above, so this one is reached through _link_keys(), the list that everything which builds, dates or links the
-# libraries goes by.
-#   yuv   yuv420_kernel<true / false>, the delivered BGR picture as nv12 / i420 (rip_set_output_format, rip_set_output_yuv_matrix);
-#         tests/yuv_variant_cases.py
-YUV_LIBRARIES = {
-    "yuv": (os.path.join(HERE, "librip_yuv_hip.so"), ["rip_yuv.hip"], ["rip_yuv.hpp"], "build_yuv"),
-}
-OUT_YUV, YUV_SOURCES, YUV_HEADERS = YUV_LIBRARIES["yuv"][:3]
+#   mask   rect_mask_kernel, the coverage mask of an undistortion from its maps alone, and mask_threshold_kernel (rip_set_rect_mask,
+#          rip_get_output_mask); rip_round_map.hpp is the map quantiser it shares with the remap kernels; tests/mask_variant_cases.py
+#   yuv    yuv420_kernel<true / false>, the delivered BGR picture as nv12 / i420 (rip_set_output_format, rip_set_output_yuv_matrix);
+#          tests/yuv_variant_cases.py
+# rip_resize_dev.hpp is the device code and the launch checks the libraries of the resize stage share.
+Companion = collections.namedtuple("Companion", "key out sources headers build_dir")
+RESIZE_SHARED = ["rip_resize_dev.hpp", "rip_resize.hpp", "rip_area.hpp"]
+COMPANIONS = tuple(Companion(key, os.path.join(HERE, "librip_%s_hip.so" % key), sources, headers, "build_" + key) for key, sources, headers in (
+    ("out", ["rip_output.hip"], ["rip_output.hpp"]),
+    ("rsz", ["rip_resize.hip"], RESIZE_SHARED),
+    ("area", ["rip_area.hip"], RESIZE_SHARED),
+    ("fit", ["rip_fit.hip"], ["rip_fit.hpp"] + RESIZE_SHARED),
+    ("aa", ["rip_aa.hip"], ["rip_aa.hpp", "rip_aa_dev.hpp"] + RESIZE_SHARED),
+    ("heads", ["rip_heads.hip"], ["rip_heads.hpp"]),
+    ("mask", ["rip_mask.hip"], ["rip_mask.hpp", "rip_round_map.hpp"]),
+    ("yuv", ["rip_yuv.hip"], ["rip_yuv.hpp"]),
+))
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
 # six waves per SIMD and gains 2.3 % from the extra instruction-level parallelism inside a wave (2.311 -> 2.257 ms per 256
 # frames); the same strategy costs the memory-bound remap 3.5 % and the ccc kernels 8 %, so it is not a global flag.
@@ -82,34 +63,22 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def _tables():
-    return (COMPANIONS, HEAD_LIBRARIES, MASK_LIBRARIES)
+def companion(key):
+    """The row of COMPANIONS with that key."""
+    return next(c for c in COMPANIONS if c.key == key)
 
 
-def _row(key):
-    return next(t[key] for t in _tables() + (YUV_LIBRARIES,) if key in t)
-
-
-def _all_keys():
-    return [key for t in _tables() for key in t]
-
-
-def _link_keys():
-    """Every library librip_hip.so links against: the three closed tables and YUV_LIBRARIES."""
-    return _all_keys() + list(YUV_LIBRARIES)
-
-
-def _companion_up_to_date(key):
-    out, sources, headers, _ = _row(key)
-    if not os.path.exists(out):
+def companion_up_to_date(key):
+    c = companion(key)
+    if not os.path.exists(c.out):
         return False
-    t = os.path.getmtime(out)
-    deps = [os.path.join(CSRC, s) for s in sources + headers] + [os.path.abspath(__file__)]
+    t = os.path.getmtime(c.out)
+    deps = [os.path.join(CSRC, s) for s in c.sources + c.headers] + [os.path.abspath(__file__)]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
 def companions_up_to_date():
-    return all(_companion_up_to_date(key) for key in _link_keys())
+    return all(companion_up_to_date(c.key) for c in COMPANIONS)
 
 
 def up_to_date():
@@ -120,10 +89,10 @@ def up_to_date():
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def _build_companion(key, force=False, verbose=False):
+def build_companion(key, force=False, verbose=False):
     """One companion library, next to librip_hip.so."""
-    out, sources, _, bdir_name = _row(key)
-    if not force and _companion_up_to_date(key):
+    _, out, sources, _, bdir_name = companion(key)
+    if not force and companion_up_to_date(key):
         return out
     bdir = os.path.join(HERE, bdir_name)
     os.makedirs(bdir, exist_ok=True)
@@ -144,17 +113,6 @@ def _build_companion(key, force=False, verbose=False):
     if r.returncode != 0:
         raise RuntimeError("link failed:\n" + r.stdout)
     return out
-
-
-# the names the tests and the probes use
-companion_up_to_date, build_companion = functools.partial(_companion_up_to_date, "out"), functools.partial(_build_companion, "out")
-rsz_up_to_date, build_rsz = functools.partial(_companion_up_to_date, "rsz"), functools.partial(_build_companion, "rsz")
-area_up_to_date, build_area = functools.partial(_companion_up_to_date, "area"), functools.partial(_build_companion, "area")
-fit_up_to_date, build_fit = functools.partial(_companion_up_to_date, "fit"), functools.partial(_build_companion, "fit")
-aa_up_to_date, build_aa = functools.partial(_companion_up_to_date, "aa"), functools.partial(_build_companion, "aa")
-heads_up_to_date, build_heads = functools.partial(_companion_up_to_date, "heads"), functools.partial(_build_companion, "heads")
-mask_up_to_date, build_mask = functools.partial(_companion_up_to_date, "mask"), functools.partial(_build_companion, "mask")
-yuv_up_to_date, build_yuv = functools.partial(_companion_up_to_date, "yuv"), functools.partial(_build_companion, "yuv")
 
 
 # --asan: the HOST layer (every .cpp of SOURCES: YAML reader, loaders, table builders, frame ring, copy threads) under
@@ -188,8 +146,8 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
             return out
     if out is None and not force and up_to_date():
         return OUT
-    for key in _link_keys():  # every build of librip_hip.so links against all of them; `force` is about the library asked for
-        _build_companion(key, verbose=verbose)
+    for c in COMPANIONS:  # every build of librip_hip.so links against all of them; `force` is about the library asked for
+        build_companion(c.key, verbose=verbose)
     out = out or OUT
     objs = []
     procs = []
@@ -212,7 +170,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
         if verbose and log.strip():
             print(log)
     # the companions are found next to the library ($ORIGIN) or one directory up (variants/*.so)
-    companion = ["-L" + HERE] + ["-l:" + os.path.basename(_row(key)[0]) for key in _link_keys()] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    companion = ["-L" + HERE] + ["-l:" + os.path.basename(c.out) for c in COMPANIONS] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
     cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

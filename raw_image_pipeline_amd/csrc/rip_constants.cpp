@@ -365,7 +365,7 @@ static void ensure_keyed_tables(rip_pipeline* p, int head, const int (&key)[5], 
 
 // The linear tables (rip::build_resize_tables).  One buffer: xofs, alpha (both padded to whole lanes), yofs, beta -- every part starts
 // 16-byte aligned.
-ResizeTables ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W) {
+void ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W, rip::ResizeParams& r) {
   const size_t wp = rip::resize_table_cols(W), hp = ((size_t)H + 3) & ~(size_t)3;
   const size_t o_alpha = wp * 4, o_yofs = o_alpha + wp * 4, o_beta = o_yofs + hp * 8, bytes = o_beta + hp * 4;
   ensure_keyed_tables(p, head, {R, C, H, W, 0}, bytes, [&](uint8_t* h) {
@@ -373,14 +373,28 @@ ResizeTables ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H
                              reinterpret_cast<int16_t*>(h + o_beta), &p->rsz_tables[head].area2);
   });
   const uint8_t* d = p->rsz_tables[head].dev.as<uint8_t>();
-  return {reinterpret_cast<const int32_t*>(d), reinterpret_cast<const int16_t*>(d + o_alpha), reinterpret_cast<const int32_t*>(d + o_yofs),
-          reinterpret_cast<const int16_t*>(d + o_beta), p->rsz_tables[head].area2};
+  r.xofs = reinterpret_cast<const int32_t*>(d);
+  r.alpha = reinterpret_cast<const int16_t*>(d + o_alpha);
+  r.yofs = reinterpret_cast<const int32_t*>(d + o_yofs);
+  r.beta = reinterpret_cast<const int16_t*>(d + o_beta);
+  r.area2 = p->rsz_tables[head].area2;
+}
+
+// the six index tables AreaParams and AaParams (P) share: xfirst, xcount, xwofs [W] at d, yfirst, ycount, ywofs [H] at d + o_y
+template <typename P>
+static void set_tap_lists(P& r, const int32_t* d, size_t o_y, int H, int W) {
+  r.xfirst = d;
+  r.xcount = d + W;
+  r.xwofs = d + 2 * (size_t)W;
+  r.yfirst = d + o_y;
+  r.ycount = d + o_y + H;
+  r.ywofs = d + o_y + 2 * (size_t)H;
 }
 
 // The tables of the area interpolation (rip::build_resize_area_tables) in the same buffer and under the same key, told apart by the
 // key's last entry.  Parts, all of 4-byte entries: xfirst, xcount, xwofs [W], yfirst, ycount, ywofs [H], xweight [C + 2 W],
 // yweight [R + 2 H]; wofs is the running sum of count.
-AreaTables ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, int W) {
+void ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, int W, rip::AreaParams& r) {
   const size_t o_y = (size_t)W * 3, o_xw = o_y + (size_t)H * 3, o_yw = o_xw + (size_t)C + 2 * (size_t)W, words = o_yw + (size_t)R + 2 * (size_t)H;
   ensure_keyed_tables(p, head, {R, C, H, W, 1}, words * 4, [&](uint8_t* bytes) {
     int32_t* h = reinterpret_cast<int32_t*>(bytes);
@@ -398,14 +412,17 @@ AreaTables ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, in
     }
   });
   const int32_t* d = p->rsz_tables[head].dev.as<int32_t>();
-  return {d, d + W, d + 2 * (size_t)W, d + o_y, d + o_y + H, d + o_y + 2 * (size_t)H, reinterpret_cast<const float*>(d + o_xw),
-          reinterpret_cast<const float*>(d + o_yw), p->rsz_tables[head].whole, p->rsz_tables[head].scale};
+  set_tap_lists(r, d, o_y, H, W);
+  r.xweight = reinterpret_cast<const float*>(d + o_xw);
+  r.yweight = reinterpret_cast<const float*>(d + o_yw);
+  r.whole = p->rsz_tables[head].whole;
+  r.scale = p->rsz_tables[head].scale;
 }
 
 // The tables of an antialiased filter (rip::build_resize_aa_tables) in the same buffer and under the same key, whose last entry is
 // the filter.  Parts: xfirst, xcount, xwofs [W], yfirst, ycount, ywofs [H] of 4-byte entries, then the int16 weights of the columns
 // and of the rows, each part of its capacity rounded up to an even count.
-AaTables ensure_aa_tables(rip_pipeline* p, int head, int filter, int R, int C, int H, int W) {
+void ensure_aa_tables(rip_pipeline* p, int head, int filter, int channels, int R, int C, int H, int W, rip::AaParams& r) {
   const size_t o_y = (size_t)W * 3, o_xw = o_y + (size_t)H * 3;  // in 4-byte entries
   const size_t cap_x = (rip::resize_aa_weight_capacity(filter, C, W) + 1) & ~(size_t)1, cap_y = (rip::resize_aa_weight_capacity(filter, R, H) + 1) & ~(size_t)1;
   const size_t bytes = o_xw * 4 + (cap_x + cap_y) * 2;
@@ -418,8 +435,13 @@ AaTables ensure_aa_tables(rip_pipeline* p, int head, int filter, int R, int C, i
   });
   const int32_t* d = t.dev.as<int32_t>();
   const int16_t* dw = reinterpret_cast<const int16_t*>(d + o_xw);
-  return {d, d + W, d + 2 * (size_t)W, d + o_y, d + o_y + H, d + o_y + 2 * (size_t)H, dw, dw + cap_x, t.aa_xprec, t.aa_yprec,
-          {t.aa_tile_rows[0], t.aa_tile_rows[1]}, {t.aa_lds_rows[0], t.aa_lds_rows[1]}};
+  set_tap_lists(r, d, o_y, H, W);
+  r.xweight = dw;
+  r.yweight = dw + cap_x;
+  r.xprec = t.aa_xprec;
+  r.yprec = t.aa_yprec;
+  r.tile_rows = t.aa_tile_rows[channels == 3];
+  r.lds_rows = t.aa_lds_rows[channels == 3];
 }
 
 }  // namespace rip::api

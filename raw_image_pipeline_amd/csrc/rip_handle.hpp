@@ -1,7 +1,7 @@
 // rip_handle.hpp -- internal to librip_hip.so (not installed): the handle behind include/rip.h and what the host units
 // share.  rip_plan.cpp turns a frame's geometry and encoding into a Plan, rip_constants.cpp keeps the device-resident constants
-// current, rip_batch.cpp enqueues the kernels of a batch, rip_ring.cpp holds the host-frame calls and their ring, rip_api.cpp the
-// rest of the C ABI.
+// current, rip_batch.cpp enqueues the kernels of a batch, rip_output_stage.cpp those of the output stage behind it, rip_ring.cpp
+// holds the host-frame calls and their ring, rip_api.cpp the rest of the C ABI.
 #pragma once
 #include "../../include/rip.h"
 
@@ -172,6 +172,8 @@ struct FrameView {
   int rows, cols;
   operator ConstFrameView() const { return {ptr, step, frame_stride, rows, cols}; }
 };
+// bytes of a row rounded up to 16: the pitch of the staging images and of the masks
+inline size_t pitch16(size_t row_bytes) { return (row_bytes + 15) & ~(size_t)15; }
 // the view from frame f0 on
 template <typename View>
 View frames_from(View v, int f0) {
@@ -315,7 +317,7 @@ struct MaskBaseConst {
   DevBuf cov, bin;
   bool cov_valid = false, bin_valid = false;
   int builds = 0;  // images built since the handle was created (rip_debug_rect_mask_info)
-  size_t pitch() const { return ((size_t)key.cols + 15) & ~(size_t)15; }
+  size_t pitch() const { return pitch16((size_t)key.cols); }
 };
 // The delivered mask M' of one output head: what the head's window, target, fit mode and filter make of the mask above, under the
 // mode it was built for.  One per head, like the table caches; dropped by the head's output setters and by whatever drops M.
@@ -475,32 +477,15 @@ void ensure_tables(rip_pipeline* p);
 void ensure_vignette(rip_pipeline* p, int rows, int cols);
 void ensure_ccc(rip_pipeline* p, int rows, int cols);
 void ensure_output_table(rip_pipeline* p, int head, int fmt);
-// the resize stage's tables as the kernels' parameter blocks take them (device pointers into ResizeTableConst::dev)
-struct ResizeTables {
-  const int32_t* xofs;
-  const int16_t* alpha;
-  const int32_t* yofs;
-  const int16_t* beta;
-  int area2;
-};
-struct AreaTables {
-  const int32_t *xfirst, *xcount, *xwofs, *yfirst, *ycount, *ywofs;
-  const float *xweight, *yweight;
-  int whole;
-  float scale;
-};
-ResizeTables ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W);
-AreaTables ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, int W);
-struct AaTables {
-  const int32_t *xfirst, *xcount, *xwofs, *yfirst, *ycount, *ywofs;
-  const int16_t *xweight, *yweight;
-  int xprec, yprec;
-  int tile_rows[2], lds_rows[2];  // for 1 and for 3 channels
-};
-// filter: 2 (linear_aa) or 3 (cubic_aa), rip::output_interpolation_id's numbers
-AaTables ensure_aa_tables(rip_pipeline* p, int head, int filter, int R, int C, int H, int W);
+// The resize stage's tables of head `head` for an R x C window and an H x W picture, written into the table fields of the launch's
+// parameter block `r` -- device pointers into ResizeTableConst::dev and the flags that go with them; the other fields are left alone.
+void ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W, rip::ResizeParams& r);
+void ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, int W, rip::AreaParams& r);
+// filter: 2 (linear_aa) or 3 (cubic_aa), rip::output_interpolation_id's numbers; channels: 1 or 3, picks tile_rows and lds_rows
+void ensure_aa_tables(rip_pipeline* p, int head, int filter, int channels, int R, int C, int H, int W, rip::AaParams& r);
 
-// rip_batch.cpp
+// rip_batch.cpp: the chain (run_batch) and write_debug_dumps.  rip_output_stage.cpp: everything else down to the end of this
+// namespace -- what follows the chain: resize, pad, converter, heads and masks
 size_t fmt_pitch(const Plan& pl);
 void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb = false);
 void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n);

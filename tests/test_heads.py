@@ -226,29 +226,6 @@ def test_facade(tmp_path, rip_lib, branch):
     assert r.returncode == 0 and "heads host OK" in r.stdout, r.stdout + r.stderr
 
 
-# ---- the build -----------------------------------------------------------------------------------------------------------------
-def test_the_build_covers_the_heads_library(rip_lib):
-    from raw_image_pipeline_amd import LIB_PATH
-    from raw_image_pipeline_amd import build as B
-    assert os.path.exists(B.OUT_HEADS) and os.path.dirname(B.OUT_HEADS) == os.path.dirname(LIB_PATH)
-    assert B.up_to_date() and B.heads_up_to_date() and B.companions_up_to_date()
-    assert len(B.COMPANIONS) == 5 and "heads" not in B.COMPANIONS and list(B.HEAD_LIBRARIES) == ["heads"]
-    for f in B.HEADS_SOURCES + B.HEADS_HEADERS:
-        assert os.path.exists(os.path.join(B.CSRC, f))
-    assert "rip_heads.hpp" in B.HEADERS        # rip_handle.hpp includes it
-    # up_to_date() looks at the library's file: older than its source, it is out of date
-    src = os.path.join(B.CSRC, "rip_heads.hip")
-    before = os.stat(B.OUT_HEADS)
-    try:
-        os.utime(B.OUT_HEADS, (before.st_atime, os.path.getmtime(src) - 10))
-        assert not B.heads_up_to_date() and not B.up_to_date()
-    finally:
-        os.utime(B.OUT_HEADS, (before.st_atime, before.st_mtime))
-    assert B.up_to_date()
-    needed = subprocess.run(["readelf", "-d", LIB_PATH], capture_output=True, text=True).stdout
-    assert "librip_heads_hip.so" in needed and "$ORIGIN" in needed
-
-
 # ---- the kernel on the host ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_the_kernel_run_on_the_host_copies_every_byte_and_no_other(tmp_path, sanitize):
