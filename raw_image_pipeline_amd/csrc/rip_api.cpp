@@ -38,6 +38,7 @@ Tunables tunables_from_env() {
   t.remap_frames = positive("RIP_REMAP_FRAMES", t.remap_frames);
   t.remap_exp = positive("RIP_REMAP_EXP", t.remap_exp);
   if (const char* e = std::getenv("RIP_REMAP_DEAL")) t.remap_deal = std::max(0, std::atoi(e));
+  if (const char* e = std::getenv("RIP_REMAP_ORDER")) t.remap_order = std::max(0, std::min(2, std::atoi(e)));
   if (const char* e = std::getenv("RIP_CHAIN_DEAL")) t.chain_deal = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("RIP_REMAP_FUSED")) t.remap_fused = std::atoi(e) != 0;
   if (const char* e = std::getenv("RIP_CHAIN_FOOTPRINT")) t.chain_footprint = std::atoi(e) != 0;
@@ -1089,6 +1090,7 @@ rip_status rip_set_tunable(rip_pipeline* p, const char* name, int value) {
     else if (n == "chain_footprint") t.chain_footprint = value != 0;
     else if (n == "remap_exp") t.remap_exp = value;
     else if (n == "remap_deal") t.remap_deal = value;
+    else if (n == "remap_order") t.remap_order = value <= 2 ? value : 0;
     else if (n == "chain_deal") t.chain_deal = value;
     else if (n == "chain_nt") t.chain_nt = value;
     else if (n == "remap_tiled") p->use_tiled_remap = value != 0;

@@ -231,7 +231,8 @@ struct RemapTiledParams {
   const uint8_t* mono_lut;
   int mono_flip180;
   int deal_run;                // set by the launcher (remap_deal_run): tiles per run of the round-robin deal to the XCDs; 0 = one contiguous range per XCD
-  int exp;                     // timing-only experiment switches (Tunables::remap_exp); read by -DRIP_EXPERIMENTS builds only
+  int deal_order, deal_shift;  // set by the launcher (rip_tile_deal.hpp tile_deal_geometry): order inside a run, 0 = row-major, 1 = column strips of 2^deal_shift tile rows
+  int exp;                    // timing-only experiment switches (Tunables::remap_exp); read by -DRIP_EXPERIMENTS builds only
 };
 
 // Undistortion maps on the device (rip_maps.hip): iR = (P R)^-1 from the host, K / D of the distorted camera.  pinhole == 0:
@@ -285,7 +286,8 @@ struct Tunables {
   int remap_frames = 0;       // RIP_REMAP_FRAMES: frames per tile visit (0: by the size of a source frame, 4 .. 12)
   int chain_deal = 1;         // RIP_CHAIN_DEAL: the fast chain kernel deals runs of 3 x 512 items (of 4 x 2 pixels; 2.5 row pairs of a 2448-wide frame) round-robin to the XCDs, so that the whole chip reads and writes one band of the frame (round 6: default stage set 1.270 -> 1.204 ms, Lab chain alone 2.216 -> 2.158; runs of 1 .. 6 chunks run alike, 10 / 24 lose; the run length is a compile-time constant of the kernel) -- 1: when no remap gathers from the image afterwards (in front of the remap it gains nothing and fetches a third more input), 2: always, 0: one contiguous range of chunks per XCD (rounds 1-5)
   int remap_deal = 4;         // RIP_REMAP_DEAL: how the ring kernels deal the tiles to the eight XCDs -- k > 0: runs of about k tile rows round-robin (all XCDs work on one band of the image; round 6: -5 % at 4 frames per visit, -12 % with 6-8; 1, 2 and 4 tile rows run alike, 4 fetches least: 7.58 / 7.11 / 6.54 GB per 256 frames at the L2s), 0: one contiguous range of tiles per XCD (rounds 1-5)
-  int remap_exp = 0;          // RIP_REMAP_EXP: bit mask of timing-only experiments (wrong pixels), honoured by -DRIP_EXPERIMENTS builds only (tools/probes/remap_exp_probe.py)
+  int remap_order = 2;        // RIP_REMAP_ORDER: the order of the tiles inside a run of the deal -- 0: row-major, 1: column strips (the run is then remap_deal rounded down to a power of two of whole tile rows; consecutive workgroups of an XCD take vertical neighbours, rip_tile_deal.hpp), 2: column strips where the strips deal out evenly over the XCDs, row-major elsewhere; EXPERIMENTS.md "remap: the order inside a run"
+  int remap_exp = 0;         // RIP_REMAP_EXP: bit mask of timing-only experiments (wrong pixels), honoured by -DRIP_EXPERIMENTS builds only (tools/probes/remap_exp_probe.py)
   int remap_fused = 1;        // RIP_REMAP_FUSED=0: never run the chain inside the remap's tiles (rip_fused.hip)
   int chain_footprint = 1;    // RIP_CHAIN_FOOTPRINT=0: the fast chain kernel in front of the remap computes every pixel, not only the ones the remap reads (ChainParams::item_list)
   int chain_nt = -1;          // RIP_CHAIN_NT: non-temporal stores of the fused chain for batches of >= 8 frames; -1 = always (round 5: also when the remap reads the image back), 0 = never, 1 = only when no kernel of the batch reads the image again (rounds 3-4)
@@ -319,8 +321,10 @@ inline const char* launch_log_bool(bool b) { return b ? "true" : "false"; }
 // Returns false (and launches nothing) when the geometry does not qualify for the tiled kernel.
 // dry_run: only answer (the API decides with it whether a mono8 chain can be folded into the gather).
 bool launch_remap_tiled(const RemapTiledParams& p, const Tunables& tn, hipStream_t stream, bool dry_run = false);
-// tiles per run of the round-robin deal (RemapTiledParams::deal_run) for a plan of tiles_x x tiles_y tiles; 0 = contiguous ranges
-int remap_deal_run(int tiles_x, int tiles_y, const Tunables& tn);
+// the deal of a plan of tiles_x x tiles_y tiles under tn (remap_deal, remap_order) for a batch of n_frames, written into
+// q.deal_run / deal_order / deal_shift; batches of fewer than 4 frames take contiguous ranges.  fused: the launch is rip_fused.hip's,
+// where column strips lose even when they deal out evenly (2448 x 2048: 2.023 against 1.999 ms), so order 2 means row-major there
+void set_remap_deal(RemapTiledParams& q, int n_frames, const Tunables& tn, bool fused = false);
 // rip_fused.hip: debayer + memory-rate stages + remap in one kernel over the Bayer frames (p.base.src); false when the
 // configuration / geometry does not qualify (nothing launched).  dry_run: only answer.
 bool launch_remap_fused(const RemapTiledParams& p, const ChainParams& c, int max_rect_w, int max_rect_h, const Tunables& tn, hipStream_t stream,

@@ -233,8 +233,7 @@ __global__ __launch_bounds__(kRemapTileThreads) void remap_ring_kernel(RemapTile
   const bool flip = CN == 1 && p.mono_flip180 != 0;
   constexpr unsigned kStage = (unsigned)PRE * kRemapTileThreads * 16u;  // bytes per stage
   const RemapParams& b = p.base;
-  const int ntiles = p.tiles_x * p.tiles_y;
-  const TileDeal deal(ntiles, p.deal_run);
+  const TileDeal deal(p.tiles_x, p.tiles_y, p.deal_run, p.deal_order, p.deal_shift);
   const int xcd = blockIdx.x & 7;
   const int tid = threadIdx.x;
   const int lrow = tid / kRemapGroupsPerRow, lgrp = tid % kRemapGroupsPerRow;
@@ -455,12 +454,13 @@ void launch_ring_pre(int pre, const RemapTiledParams& q, dim3 grid, unsigned lds
 
 }  // namespace
 
-int remap_deal_run(int tiles_x, int tiles_y, const Tunables& tn) {
-  if (tn.remap_deal <= 0 || tiles_x <= 0 || tiles_y <= 0) return 0;
-  // runs of about remap_deal tile rows, sized so that every XCD gets the same number of runs (a ragged last run at most)
-  const int ntiles = tiles_x * tiles_y;
-  const int runs_per_xcd = (tiles_y + 8 * tn.remap_deal - 1) / (8 * tn.remap_deal);
-  return (ntiles + 8 * runs_per_xcd - 1) / (8 * runs_per_xcd);
+void set_remap_deal(RemapTiledParams& q, int n_frames, const Tunables& tn, bool fused) {
+  // batches only: a single frame (latency calls: 63.5 against 64.9 us for the reference's example configuration) gains nothing
+  // from one band across the chip and loses the neighbouring rectangles' meeting in one L2
+  const TileDealGeometry g = tile_deal_geometry(q.tiles_x, q.tiles_y, n_frames >= 4 ? tn.remap_deal : 0, fused && tn.remap_order == 2 ? 0 : tn.remap_order);
+  q.deal_run = g.run;
+  q.deal_order = g.order;
+  q.deal_shift = g.shift;
 }
 
 bool launch_remap_tiled(const RemapTiledParams& p, const Tunables& tn, hipStream_t stream, bool dry_run) {
@@ -493,9 +493,7 @@ bool launch_remap_tiled(const RemapTiledParams& p, const Tunables& tn, hipStream
     const unsigned stage_bytes = (unsigned)pre * kRemapTileThreads * 16u;
     q.stages = std::max(2, std::min(4, stages_env));
     q.exp = tn.remap_exp;
-    // batches only: a single frame (latency calls: 63.5 against 64.9 us for the reference's example configuration) gains nothing
-    // from one band across the chip and loses the neighbouring rectangles' meeting in one L2
-    q.deal_run = b.n_frames >= 4 ? remap_deal_run(p.tiles_x, p.tiles_y, tn) : 0;
+    set_remap_deal(q, b.n_frames, tn);
     const unsigned lds = (unsigned)q.stages * stage_bytes + 16u;  // the three-dword tap reads run up to 11 B past a row
     const int per_cu = std::max(1, std::min(tn.remap_per_cu > 0 ? tn.remap_per_cu : 6, (int)((160u * 1024u) / (lds + 256u))));
     int blocks = std::min(256 * per_cu, (ntiles + 7) / 8 * 8);

@@ -4,7 +4,7 @@ ONE process on ONE handle and ONE output allocation -- the remap's duration has 
 (EXPERIMENTS.md "the run-to-run spread"), so separate processes cannot resolve differences below 10 %.  The masks are
 walked round-robin `--rounds` times; prints per-class kernel times of every trial and the per-mask medians.
 
-usage: RIP_LIBRARY=raw_image_pipeline_amd/variants/exp.so remap_exp_probe.py --masks 0,1,2,4,6 [--tunable name=v1,v2]
+usage: RIP_LIBRARY=raw_image_pipeline_amd/variants/exp.so remap_exp_probe.py --masks 0,1,2,4,6 [--tunable name=v1,v2 [--tunable ...]]
        [--rounds 3] [--steps 6] [--workload config2]
        remap_exp_probe.py --libs head=raw_image_pipeline_amd/variants/head.so,new= [--set new:remap_persistent=0] ...
 --libs: several builds in the one process (name=path; an empty path is the tree's library), one handle each, the same input and
@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--masks", default="0")
-    ap.add_argument("--tunable", default="", help="name=v1,v2,...: a second axis, walked inside every mask")
+    ap.add_argument("--tunable", action="append", default=[], help="name=v1,v2,...: a further axis, walked inside every mask; may be repeated (the product is walked)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--batch", type=int, default=256)
@@ -63,10 +63,10 @@ def main():
     orows, ocols, ocn, _ = pipe.query_output(height, width, 1, pattern)
     out = torch.empty((args.batch, orows, ocols, ocn), dtype=torch.uint8, device="cuda")
     masks = [int(m, 0) for m in args.masks.split(",")]
-    tname, tvals = "", [None]
-    if args.tunable:
-        tname, _, v = args.tunable.partition("=")
-        tvals = [int(x) for x in v.split(",")]
+    import itertools
+    tnames = [t.partition("=")[0] for t in args.tunable]
+    tvals = list(itertools.product(*[[int(x) for x in t.partition("=")[2].split(",")] for t in args.tunable]))  # [()] without --tunable
+    label = lambda tv: " ".join("%s=%d" % nv for nv in zip(tnames, tv))
     results = {}
     for r in range(args.rounds):
       for lname, pipe in pipes.items():
@@ -77,10 +77,10 @@ def main():
                 except Exception:
                     if m:
                         continue
-                if tname:
+                for tname, v in zip(tnames, tv):
                     try:
-                        pipe.set_tunable(tname, tv)
-                    except Exception:
+                        pipe.set_tunable(tname, v)
+                    except Exception:  # a library that does not know the tunable runs as it is
                         pass
                 for _ in range(2):
                     pipe.apply_device(frames, pattern, out=out)
@@ -96,12 +96,13 @@ def main():
                 ms["wall"] = round(wall, 4)
                 key = (lname, m, tv)
                 results.setdefault(key, []).append(ms)
-                print("round %d %s mask %3d %s%s  %s" % (r, lname, m, tname, "" if tv is None else "=%d" % tv, ms), flush=True)
+                print("round %d %s mask %3d %s  %s" % (r, lname, m, label(tv), ms), flush=True)
     print("--- medians (ms per %d frames)" % args.batch)
     for (lname, m, tv), lst in results.items():
         keys = sorted({k for d in lst for k in d})
         med = {k: round(statistics.median(d.get(k, 0.0) for d in lst), 4) for k in keys}
-        print("mask %3d %s %s%s  %s" % (m, lname, tname, "" if tv is None else "=%d" % tv, med), flush=True)
+        spread = {k: round(max(d.get(k, 0.0) for d in lst) - min(d.get(k, 0.0) for d in lst), 4) for k in ("remap",) if k in keys}
+        print("mask %3d %s %s  %s  spread %s" % (m, lname, label(tv), med, spread), flush=True)
 
 
 if __name__ == "__main__":

@@ -45,7 +45,13 @@ case $exp in
       echo "== config5 3840x2160 deal=$deal"; RIP_REMAP_DEAL=$deal python tools/probes/remap_exp_probe.py --workload config5 --size 3840x2160 --rounds 2 --tunable remap_frames=8,12,16 2>&1 | grep "^mask"
     done | tee $out/config5.log
     python -m pytest tests -m gpu -x -q -k "undist or remap or fused or config" 2>&1 | tail -5 | tee $out/pytest.log ;;
-  asan)          # the host-frame ring, copy threads, rig, fork handling under ASan + UBSan on the GPU box (tools/run_asan.sh)
+  remap_order)   # the order inside a run (RIP_REMAP_ORDER) x run length x frames per visit against the parent commit's library ($V/head.so) in one process
+    python tools/probes/remap_exp_probe.py --workload config2 --size 2448x2048 --rounds 4 --libs head=$V/head.so,new= --tunable remap_order=0,1 --tunable remap_deal=4,8,16 --tunable remap_frames=4,5,6 2>&1 | grep "^mask" | tee $out/config2_2448.log
+    python tools/probes/remap_exp_probe.py --workload config5 --size 3840x2160 --rounds 4 --libs head=$V/head.so,new= --tunable remap_order=0,1 --tunable remap_deal=4,8,16 --tunable remap_frames=12,16 2>&1 | grep "^mask" | tee $out/config5_3840.log
+    for size in 1920x1200 3840x2160; do python tools/probes/remap_exp_probe.py --workload config2 --size $size --rounds 3 --libs head=$V/head.so,new= --tunable remap_order=0,1 --tunable remap_deal=4,8,16 2>&1 | grep "^mask" | sed "s/^/$size /"; done | tee $out/config2_sizes.log
+    python tools/probes/remap_exp_probe.py --workload config2 --size 2448x2048 --rounds 5 --libs new=,head=$V/head.so,new2=,head2=$V/head.so --tunable remap_order=0,1,2 --tunable remap_frames=0,5 2>&1 | tee $out/ab_config2.log | grep "^mask"
+    python tools/probes/remap_exp_probe.py --workload config5 --size 2448x2048 --rounds 5 --libs new=,head=$V/head.so --tunable remap_order=0,1 --tunable remap_deal=4,8 2>&1 | grep "^mask" | tee $out/ab_config5.log ;;
+  asan)         # the host-frame ring, copy threads, rig, fork handling under ASan + UBSan on the GPU box (tools/run_asan.sh)
     tools/run_asan.sh python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "${1:-submit or collect or ring or rig or thread or fork or pageable or pool or frontend or facade or error or taps or abi}" > $out/pytest_full.log 2>&1
     grep -v "^  File\|^Loading" $out/pytest_full.log | head -c 20000 | tee $out/pytest.log | tail -30 ;;
   remap_exp8)    # stores: half-line segments? frame stride?  (timing only)
