@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
-SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_host.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_output_stage.cpp", "rip_ring.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile_deal.hpp", "rip_round_map.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", "rip_mask.hpp", "rip_yuv.hpp", os.path.join("..", "..", "include", "rip.h")]
+SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_yaml.cpp", "rip_params.cpp", "rip_output_tables.cpp", "rip_color_tables.cpp", "rip_undistort.cpp", "rip_ccc_model.cpp", "rip_png.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_output_stage.cpp", "rip_ring.cpp", "rip_settings.cpp", "rip_api.cpp"]  # compiled in parallel
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile_deal.hpp", "rip_round_map.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_yaml.hpp", "rip_params.hpp", "rip_output_tables.hpp", "rip_color_tables.hpp", "rip_undistort.hpp", "rip_ccc_model.hpp", "rip_png.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", "rip_mask.hpp", "rip_yuv.hpp", os.path.join("..", "..", "include", "rip.h")]
 # The companion libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
 # what tests/variant_cases.py closes over; each companion's table is closed by a tests/*_variant_cases.py of its own.
 # librip_hip.so -- every build of it: the default one, the sanitizer build and the A/B variants under variants/ -- links against

@@ -1,6 +1,6 @@
-// rip_api.cpp -- the C-ABI declared in include/rip.h, minus the host-frame calls (rip_ring.cpp): one handle owns the
-// module parameters (rip_host.hpp), the device-resident constants and scratch; rip_apply_device enqueues the kernels of a
-// batch on the caller's HIP stream (rip_batch.cpp).  There is no CPU execution path.
+// rip_api.cpp -- the C-ABI declared in include/rip.h, minus the host-frame calls (rip_ring.cpp) and the loaders, setters and
+// getters (rip_settings.cpp): one handle owns the module parameters (rip_params.hpp), the device-resident constants and scratch;
+// rip_apply_device enqueues the kernels of a batch on the caller's HIP stream (rip_batch.cpp).  There is no CPU execution path.
 #include <algorithm>
 #include <cstdarg>
 #include <cstring>
@@ -88,10 +88,22 @@ void need_device(const rip_pipeline* p) {
                       "processed on a HIP device; there is no CPU execution path");
 }
 
+void need_head(const rip_pipeline* p, int head) {
+  if (head < 0 || head >= p->m.n_heads)
+    throw InvalidArgument("output head " + std::to_string(head) + " does not exist: the handle has heads 0.." + std::to_string(p->m.n_heads - 1));
+}
+
 void copy_string(const std::string& s, char* out, size_t cap) {
   if (!out || cap == 0) throw InvalidArgument("null output buffer");
   if (s.size() + 1 > cap) throw CapacityError("string buffer too small");
   std::memcpy(out, s.c_str(), s.size() + 1);
+}
+
+Plan delivered_plan(const rip_pipeline* p, int rows, int cols, int channels, const char* encoding) {
+  if (!encoding) throw InvalidArgument("encoding is null");
+  Plan pl = make_plan(p->m, rows, cols, channels, encoding);
+  apply_output_format(p->m, p->m.selected, pl);
+  return pl;
 }
 
 }  // namespace rip::api
@@ -215,9 +227,7 @@ rip_status rip_query_output(rip_pipeline* p, int rows, int cols, int channels, c
                             int* out_cols, int* out_channels, char encoding_out[32]) {
   return guarded(p, [&] {
     need(p);
-    if (!encoding) throw InvalidArgument("encoding is null");
-    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, p->m.selected, pl);
+    const Plan pl = delivered_plan(p, rows, cols, channels, encoding);
     if (out_rows) *out_rows = pl.dl_rows;
     if (out_cols) *out_cols = pl.dl_cols;
     if (out_channels) *out_channels = pl.dl_channels;
@@ -229,9 +239,7 @@ rip_status rip_query_output_bytes(rip_pipeline* p, int rows, int cols, int chann
                                   int* planar) {
   return guarded(p, [&] {
     need(p);
-    if (!encoding) throw InvalidArgument("encoding is null");
-    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, p->m.selected, pl);
+    const Plan pl = delivered_plan(p, rows, cols, channels, encoding);
     if (bytes) *bytes = delivered_bytes(pl);
     if (elem_bytes) *elem_bytes = pl.dl_elem_bytes;
     if (planar) *planar = pl.dl_planar ? 1 : 0;
@@ -258,20 +266,12 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     if (!d_in || !d_out || !encoding) throw InvalidArgument("null buffer or encoding");
     if (n_frames < 0) throw InvalidArgument("negative frame count");
     if (n_frames == 0) return;
-    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, p->m.selected, pl);
-    const size_t in_row = row_bytes(pl, cols, channels);
-    if (in_step == 0) in_step = in_row;
-    if (in_frame_stride == 0) in_frame_stride = in_step * rows;
-    if (in_step < in_row) throw InvalidArgument("input row pitch smaller than a row");
+    const Plan pl = delivered_plan(p, rows, cols, channels, encoding);  // a null encoding was refused above, in this call's words
+    resolve_input_pitches(pl, rows, cols, channels, in_step, in_frame_stride);
     // bgr16 results (the 16-bit range is off); with a range the frame is an 8-bit one after the demosaic and keeps its taps
     if (pl.out_elem_bytes == 2 && (d_tap_debayered || d_tap_color)) throw InvalidArgument("16-bit Bayer frames have no taps");
     const FrameView dst = resolve_output_layout(pl, d_out, out_step, out_frame_stride);
-    // the input under the same limits as the output: 32-bit byte offsets inside a frame, 24-bit row multiplies
-    if (in_frame_stride < in_step * (size_t)(rows - 1) + in_row) throw InvalidArgument("input frame stride smaller than a frame");
-    if (in_step >= (1u << 24) || (unsigned long long)in_step * rows >= (1ull << 32))
-      throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
-    const ConstFrameView src = {static_cast<const uint8_t*>(d_in), in_step, in_frame_stride, rows, cols};
+    const ConstFrameView src = resolve_input_layout(pl, d_in, in_step, in_frame_stride, rows, cols, channels);
     const size_t tap_frame = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
     // several kernels put the frame index on gridDim.y (<= 65535): longer batches go through in slices.  The
     // frames of a stream are processed in order either way (the ccc Kalman state lives on the device).
@@ -286,51 +286,10 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
 }
 
 // ---- output heads --------------------------------------------------------------------------------
-rip_status rip_set_output_heads(rip_pipeline* p, int n) {
-  return guarded(p, [&] {
-    need(p);
-    if (n < 1 || n > RIP_MAX_OUTPUT_HEADS) throw InvalidArgument("output heads: 1.." + std::to_string(RIP_MAX_OUTPUT_HEADS) + " expected, got " + std::to_string(n));
-    for (auto& s : p->ring)
-      if (s->busy) throw InvalidArgument("rip_set_output_heads: frames are in flight");
-    for (int k = n; k < RIP_MAX_OUTPUT_HEADS; k++) {
-      p->m.heads[k] = rip::OutputHead();
-      p->out_table[k].dirty = true;
-      p->head_record[k] = {};
-      p->mask_head[k].valid = false;
-    }
-    p->m.n_heads = n;
-    if (p->m.selected >= n) p->m.selected = 0;
-  });
-}
-
-rip_status rip_get_output_heads(rip_pipeline* p, int* n) {
-  return guarded(p, [&] {
-    need(p);
-    if (n) *n = p->m.n_heads;
-  });
-}
-
-rip_status rip_select_output_head(rip_pipeline* p, int head) {
-  return guarded(p, [&] {
-    need(p);
-    if (head < 0 || head >= p->m.n_heads)
-      throw InvalidArgument("output head " + std::to_string(head) + " does not exist: the handle has heads 0.." + std::to_string(p->m.n_heads - 1));
-    p->m.selected = head;
-  });
-}
-
-rip_status rip_get_selected_output_head(rip_pipeline* p, int* head) {
-  return guarded(p, [&] {
-    need(p);
-    if (head) *head = p->m.selected;
-  });
-}
-
 rip_status rip_debug_output_head_info(rip_pipeline* p, int head, int* table_builds, int* direct_write, int* copied) {
   return guarded(p, [&] {
     need(p);
-    if (head < 0 || head >= p->m.n_heads)
-      throw InvalidArgument("output head " + std::to_string(head) + " does not exist: the handle has heads 0.." + std::to_string(p->m.n_heads - 1));
+    need_head(p, head);
     if (table_builds) *table_builds = p->out_table[head].builds + p->rsz_tables[head].builds;
     if (direct_write) *direct_write = p->head_record[head].direct_write;
     if (copied) *copied = p->head_record[head].copied;
@@ -356,15 +315,7 @@ rip_status rip_apply_device_heads(rip_pipeline* p, const void* d_in, size_t in_s
     FrameView dsts[RIP_MAX_OUTPUT_HEADS];
     plan_heads(p->m, pl, n_heads, requested, d_tap_debayered || d_tap_color, plans, dsts,
                [&](int k, const Plan& hp) { return resolve_output_layout(hp, heads[k].d_out, heads[k].out_step, heads[k].out_frame_stride); });
-    // the input: rip_apply_device's rules
-    const size_t in_row = row_bytes(pl, cols, channels);
-    if (in_step == 0) in_step = in_row;
-    if (in_frame_stride == 0) in_frame_stride = in_step * rows;
-    if (in_step < in_row) throw InvalidArgument("input row pitch smaller than a row");
-    if (in_frame_stride < in_step * (size_t)(rows - 1) + in_row) throw InvalidArgument("input frame stride smaller than a frame");
-    if (in_step >= (1u << 24) || (unsigned long long)in_step * rows >= (1ull << 32))
-      throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
-    const ConstFrameView src = {static_cast<const uint8_t*>(d_in), in_step, in_frame_stride, rows, cols};
+    const ConstFrameView src = resolve_input_layout(pl, d_in, in_step, in_frame_stride, rows, cols, channels);  // rip_apply_device's rules
     const size_t tap_frame = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
     constexpr int kMaxFramesPerLaunch = 16384;  // rip_apply_device's slices: per slice the chain runs once, then the heads
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
@@ -379,32 +330,13 @@ rip_status rip_apply_device_heads(rip_pipeline* p, const void* d_in, size_t in_s
 }
 
 // ---- valid-pixel masks ---------------------------------------------------------------------------
-rip_status rip_set_rect_mask(rip_pipeline* p, const char* mode) {
-  return guarded(p, [&] {
-    need(p);
-    if (!mode) throw InvalidArgument("null string");
-    (void)rip::rect_mask_mode_id(mode);
-    p->m.rect_mask = mode;
-  });
-}
-
-rip_status rip_get_rect_mask_mode(const rip_pipeline* p, char* out, size_t capacity) {
-  return guarded(p, [&] {
-    need(p);
-    copy_string(p->m.rect_mask, out, capacity);
-  });
-}
-
 // rip_get_output_mask / rip_get_output_mask_device up to the geometry: the refusals in their order (the mode, then exactly those of
 // rip_query_output), nothing enqueued
 static Plan output_mask_plan(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* mode) {
   need(p);
   *mode = rip::rect_mask_mode_id(p->m.rect_mask);
   if (*mode == 0) throw InvalidArgument("the rect mask mode is 'off': no masks are built (rip_set_rect_mask 'coverage' or 'valid')");
-  if (!encoding) throw InvalidArgument("encoding is null");
-  Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-  apply_output_format(p->m, p->m.selected, pl);
-  return pl;
+  return delivered_plan(p, rows, cols, channels, encoding);
 }
 
 rip_status rip_get_output_mask(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, uint8_t* out, size_t capacity,
@@ -443,56 +375,12 @@ rip_status rip_get_output_mask_device(rip_pipeline* p, int rows, int cols, int c
 rip_status rip_debug_rect_mask_info(rip_pipeline* p, int head, int* mask_builds, int* head_builds) {
   return guarded(p, [&] {
     need(p);
-    if (head < 0 || head >= p->m.n_heads)
-      throw InvalidArgument("output head " + std::to_string(head) + " does not exist: the handle has heads 0.." + std::to_string(p->m.n_heads - 1));
+    need_head(p, head);
     if (mask_builds) *mask_builds = p->mask_base.builds;
     if (head_builds) *head_builds = p->mask_head[head].builds;
   });
 }
 
-// ---- loaders -----------------------------------------------------------------------------------
-rip_status rip_load_params(rip_pipeline* p, const char* path) {
-  return guarded(p, [&] {
-    need(p);
-    if (!path) throw InvalidArgument("path is null");
-    std::fprintf(stderr, "Loading raw_image_pipeline params from file %s\n", path);
-    if (!rip::load_params_file(p->m, path)) {
-      std::fprintf(stderr, "Warning: parameters file doesn't exist\n");  // nothing else happens (:162-164)
-    } else {
-      // loadParams re-creates every module (std::make_unique, raw_image_pipeline.cpp:56-160): whatever
-      // loadColorCalibration / loadCameraCalibration had loaded is gone (identity matrix, calibration not available --
-      // the constructors reload them afterwards, :27-29), and the white balancer starts over with a fresh ccc
-      // estimator (first frame, new Kalman filter)
-      const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-      for (int i = 0; i < 9; i++) p->m.cc_matrix[i] = (float)eye[i];
-      for (int i = 0; i < 4; i++) p->m.cc_bias[i] = 0;
-      p->m.cc_available = false;
-      p->m.und_available = false;
-      p->ccc.state_init = false;
-    }
-    p->tables.dirty = p->vignette.dirty = p->ccc.cfg_dirty = true;
-    for (auto& t : p->out_table) t.dirty = true;
-    for (auto& h : p->mask_head) h.valid = false;
-    und_init(p);  // setBalance / setFovScale re-run init()
-  });
-}
-rip_status rip_load_camera_calibration(rip_pipeline* p, const char* path) {
-  return guarded(p, [&] {
-    need(p);
-    if (!path) throw InvalidArgument("path is null");
-    std::fprintf(stderr, "Loading camera calibration from file %s\n", path);
-    if (!rip::load_camera_calibration_file(p->m, path)) std::fprintf(stderr, "Warning: Calibration file doesn't exist\n");
-    und_init(p);
-  });
-}
-rip_status rip_load_color_calibration(rip_pipeline* p, const char* path) {
-  return guarded(p, [&] {
-    need(p);
-    if (!path) throw InvalidArgument("path is null");
-    std::fprintf(stderr, "Loading color calibration from file %s\n", path);
-    if (!rip::load_color_calibration_file(p->m, path)) std::fprintf(stderr, "Warning: Color calibration file doesn't exist\n");
-  });
-}
 rip_status rip_init_undistortion(rip_pipeline* p) {
   return guarded(p, [&] {
     need(p);
@@ -504,190 +392,6 @@ rip_status rip_init_undistortion(rip_pipeline* p) {
     }
   });
 }
-rip_status rip_load_ccc_model(rip_pipeline* p, const char* path) {
-  return guarded(p, [&] {
-    need(p);
-    if (!path) throw InvalidArgument("path is null");
-    if (!rip::ccc_load_model_file(p->ccc.model, path)) throw rip::YamlError(std::string("cannot read CCC model ") + path);
-    p->ccc.uploaded = false;
-  });
-}
-rip_status rip_set_ccc_model(rip_pipeline* p, int w, int h, const float* filter, const float* bias) {
-  return guarded(p, [&] {
-    need(p);
-    if (!filter || !bias) throw InvalidArgument("null model planes");
-    rip::ccc_build_model(p->ccc.model, w, h, filter, bias);
-    p->ccc.uploaded = false;
-  });
-}
-// ---- setters -----------------------------------------------------------------------------------
-// an output setter of the selected head drops that head's delivered mask (rip_get_output_mask), whatever it sets
-static void drop_head_mask(rip_pipeline* p) { p->mask_head[p->m.selected].valid = false; }
-
-#define RIP_SETTER(name, args, body)          \
-  rip_status name args {                      \
-    return guarded(p, [&] {                   \
-      need(p);                                \
-      body;                                   \
-    });                                       \
-  }
-
-RIP_SETTER(rip_set_taps, (rip_pipeline * p, int mask), p->tap_mask = mask & 7)
-RIP_SETTER(rip_set_tap_download, (rip_pipeline * p, int mask), p->tap_download_mask = mask & (RIP_TAP_DEBAYERED | RIP_TAP_COLOR))
-RIP_SETTER(rip_set_ccc_kalman_model, (rip_pipeline * p, double h, double r), p->ccc.kf_h = h; p->ccc.kf_r = r; p->ccc.cfg_dirty = true)
-RIP_SETTER(rip_reset_white_balance_temporal_consistency, (rip_pipeline * p), if (p->m.wb_method == "ccc") p->ccc.reset_pending = true)  // white_balance.cpp:42-47
-RIP_SETTER(rip_set_gpu, (rip_pipeline * p, int v), p->m.use_gpu = v != 0)
-RIP_SETTER(rip_set_debug, (rip_pipeline * p, int v), p->m.debug = v != 0)
-RIP_SETTER(rip_set_debayer, (rip_pipeline * p, int v), p->m.debayer_enabled = v != 0)
-RIP_SETTER(rip_set_debayer_16bit, (rip_pipeline * p, int v), p->m.debayer_16bit = v != 0)
-RIP_SETTER(rip_set_debayer_16bit_range, (rip_pipeline * p, int black, int white), rip::check_debayer_16bit_range(black, white);
-           p->m.raw16_black = black; p->m.raw16_white = white)
-RIP_SETTER(rip_set_debayer_encoding, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.debayer_encoding = s)
-RIP_SETTER(rip_set_debayer_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
-           rip::check_debayer_method(s); p->m.debayer_method = s)
-RIP_SETTER(rip_set_output_format, (rip_pipeline * p, const char* s), drop_head_mask(p); if (!s) throw InvalidArgument("null string");
-           (void)rip::output_format_id(s); if (p->m.out().out_format != s) p->out_table[p->m.selected].dirty = true; p->m.out().out_format = s)
-RIP_SETTER(rip_set_output_yuv_matrix, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
-           (void)rip::output_yuv_matrix_id(s); p->m.out().out_yuv_matrix = s)
-RIP_SETTER(rip_set_output_normalization, (rip_pipeline * p, double divisor, const double* mean, const double* sd), drop_head_mask(p);
-           if (!mean || !sd) throw InvalidArgument("null mean or std");
-           rip::check_output_normalization(divisor, mean, sd); p->m.out().out_divisor = divisor;
-           for (int i = 0; i < 3; i++) { p->m.out().out_mean[i] = mean[i]; p->m.out().out_std[i] = sd[i]; } p->out_table[p->m.selected].dirty = true)
-RIP_SETTER(rip_set_output_size, (rip_pipeline * p, int width, int height), drop_head_mask(p); rip::check_output_size(width, height); p->m.out().out_w = width; p->m.out().out_h = height)
-RIP_SETTER(rip_set_output_interpolation, (rip_pipeline * p, const char* s), drop_head_mask(p); if (!s) throw InvalidArgument("null string");
-           (void)rip::output_interpolation_id(s); p->m.out().out_interp = s)
-RIP_SETTER(rip_set_output_roi, (rip_pipeline * p, int x, int y, int width, int height), drop_head_mask(p); rip::check_output_roi(x, y, width, height);
-           p->m.out().roi_x = x; p->m.out().roi_y = y; p->m.out().roi_w = width; p->m.out().roi_h = height)
-RIP_SETTER(rip_set_output_fit, (rip_pipeline * p, const char* s), drop_head_mask(p); if (!s) throw InvalidArgument("null string");
-           (void)rip::output_fit_id(s); p->m.out().out_fit = s)
-RIP_SETTER(rip_set_output_pad, (rip_pipeline * p, int b, int g, int r), drop_head_mask(p); rip::check_output_pad(b, g, r);
-           p->m.out().out_pad[0] = b; p->m.out().out_pad[1] = g; p->m.out().out_pad[2] = r)
-RIP_SETTER(rip_set_flip, (rip_pipeline * p, int v), p->m.flip_enabled = v != 0)
-RIP_SETTER(rip_set_flip_angle, (rip_pipeline * p, int a), p->m.flip_angle = a)
-RIP_SETTER(rip_set_white_balance, (rip_pipeline * p, int v), p->m.wb_enabled = v != 0)
-RIP_SETTER(rip_set_white_balance_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.wb_method = s)
-RIP_SETTER(rip_set_white_balance_percentile, (rip_pipeline * p, double v), p->m.wb_percentile = v)
-RIP_SETTER(rip_set_white_balance_saturation_threshold, (rip_pipeline * p, double b, double d), p->m.wb_bright_thr = b; p->m.wb_dark_thr = d)
-RIP_SETTER(rip_set_white_balance_temporal_consistency, (rip_pipeline * p, int v), p->m.wb_temporal = v != 0; p->ccc.cfg_dirty = true)
-RIP_SETTER(rip_set_color_calibration, (rip_pipeline * p, int v), p->m.cc_enabled = v != 0)
-RIP_SETTER(rip_set_color_calibration_matrix, (rip_pipeline * p, const double* v, int n),
-           if (!v || n != 9) throw InvalidArgument("color calibration matrix needs 9 values");
-           for (int i = 0; i < 9; i++) p->m.cc_matrix[i] = (float)v[i])  // Matx33d -> Matx33f, color_calibration.cpp:79
-RIP_SETTER(rip_set_color_calibration_bias, (rip_pipeline * p, const double* v, int n),
-           if (!v || n < 3) throw InvalidArgument("color calibration bias needs 3 values");  // vector::at throws
-           for (int i = 0; i < 3; i++) p->m.cc_bias[i] = v[i]; p->m.cc_bias[3] = 0)
-RIP_SETTER(rip_set_gamma_correction, (rip_pipeline * p, int v), p->m.gamma_enabled = v != 0; p->tables.dirty = true)
-RIP_SETTER(rip_set_gamma_correction_method, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string"); p->m.gamma_method = s)
-RIP_SETTER(rip_set_gamma_correction_k, (rip_pipeline * p, double k), p->m.gamma_k = k; p->tables.dirty = true)
-RIP_SETTER(rip_set_fp_contraction, (rip_pipeline * p, int mode),
-           if (mode != 0 && mode != 1) throw InvalidArgument("fp contraction model must be 0 (none) or 1 (fused)");
-           if (mode != p->fp_contract) p->vignette.dirty = true;  // the mask plane's k = r^2 a2 + r^4 a4 is one of the contracted expressions
-           p->fp_contract = mode)
-RIP_SETTER(rip_set_vignetting_correction, (rip_pipeline * p, int v), p->m.vig_enabled = v != 0)
-RIP_SETTER(rip_set_vignetting_correction_parameters, (rip_pipeline * p, double s, double a2, double a4),
-           p->m.vig_scale = s; p->m.vig_a2 = a2; p->m.vig_a4 = a4; p->vignette.dirty = true)
-RIP_SETTER(rip_set_color_enhancer, (rip_pipeline * p, int v), p->m.ce_enabled = v != 0)
-// cross-wired exactly as color_enhancer.cpp:23-33
-RIP_SETTER(rip_set_color_enhancer_hue_gain, (rip_pipeline * p, double g), p->m.ce_value_gain = g)
-RIP_SETTER(rip_set_color_enhancer_saturation_gain, (rip_pipeline * p, double g), p->m.ce_saturation_gain = g)
-RIP_SETTER(rip_set_color_enhancer_value_gain, (rip_pipeline * p, double g), p->m.ce_hue_gain = g)
-RIP_SETTER(rip_set_undistortion, (rip_pipeline * p, int v), p->m.und_enabled = v != 0)
-RIP_SETTER(rip_set_undistortion_image_size, (rip_pipeline * p, int w, int h), p->m.dist_w = p->m.rect_w = w; p->m.dist_h = p->m.rect_h = h; und_init(p))
-RIP_SETTER(rip_set_undistortion_new_image_size, (rip_pipeline * p, int w, int h), p->m.rect_w = w; p->m.rect_h = h; und_init(p))
-RIP_SETTER(rip_set_undistortion_balance, (rip_pipeline * p, double b), p->m.balance = b; und_init(p))
-RIP_SETTER(rip_set_undistortion_fov_scale, (rip_pipeline * p, double f), p->m.fov_scale = f; und_init(p))
-RIP_SETTER(rip_set_undistortion_camera_matrix, (rip_pipeline * p, const double* v, int n),
-           if (!v || n < 9) throw InvalidArgument("camera matrix needs 9 values");
-           for (int i = 0; i < 9; i++) p->m.dist_K[i] = p->m.rect_K[i] = v[i]; und_init(p))
-RIP_SETTER(rip_set_undistortion_distortion_coefficients, (rip_pipeline * p, const double* v, int n),
-           if (!v || n < 4) throw InvalidArgument("distortion coefficients need 4 values");
-           for (int i = 0; i < 8; i++) p->m.dist_D[i] = p->m.rect_D[i] = i < n ? v[i] : 0.0; und_init(p))
-RIP_SETTER(rip_set_undistortion_distortion_model, (rip_pipeline * p, const char* s), if (!s) throw InvalidArgument("null string");
-           p->m.dist_model = p->m.rect_model = s; und_init(p))
-RIP_SETTER(rip_set_undistortion_rectification_matrix, (rip_pipeline * p, const double* v, int n),
-           if (!v || n < 9) throw InvalidArgument("rectification matrix needs 9 values");
-           for (int i = 0; i < 9; i++) p->m.dist_R[i] = p->m.rect_R[i] = v[i]; und_init(p))
-RIP_SETTER(rip_set_undistortion_projection_matrix, (rip_pipeline * p, const double* v, int n),
-           if (!v || n < 12) throw InvalidArgument("projection matrix needs 12 values");
-           for (int i = 0; i < 12; i++) p->m.dist_P[i] = p->m.rect_P[i] = v[i]; und_init(p))
-
-// ---- getters -----------------------------------------------------------------------------------
-int rip_is_debayer_enabled(const rip_pipeline* p) { return p && p->m.debayer_enabled; }
-int rip_is_flip_enabled(const rip_pipeline* p) { return p && p->m.flip_enabled; }
-int rip_is_white_balance_enabled(const rip_pipeline* p) { return p && p->m.wb_enabled; }
-int rip_is_color_calibration_enabled(const rip_pipeline* p) { return p && p->m.cc_enabled; }
-int rip_is_gamma_correction_enabled(const rip_pipeline* p) { return p && p->m.gamma_enabled; }
-int rip_is_vignetting_correction_enabled(const rip_pipeline* p) { return p && p->m.vig_enabled; }
-int rip_is_color_enhancer_enabled(const rip_pipeline* p) { return p && p->m.ce_enabled; }
-int rip_is_undistortion_enabled(const rip_pipeline* p) { return p && p->m.und_enabled; }
-int rip_get_dist_image_height(const rip_pipeline* p) { return p ? p->m.dist_h : 0; }
-int rip_get_dist_image_width(const rip_pipeline* p) { return p ? p->m.dist_w : 0; }
-int rip_get_rect_image_height(const rip_pipeline* p) { return p ? p->m.rect_h : 0; }
-int rip_get_rect_image_width(const rip_pipeline* p) { return p ? p->m.rect_w : 0; }
-
-#define RIP_GET_STRING(name, value)                                \
-  rip_status name(const rip_pipeline* p, char* out, size_t cap) { \
-    return guarded(p, [&] {                                        \
-      need(p);                                                     \
-      copy_string(value, out, cap);                                \
-    });                                                            \
-  }
-RIP_GET_STRING(rip_get_debayer_method, p->m.debayer_method)
-RIP_GET_STRING(rip_get_output_format, p->m.out().out_format)
-RIP_GET_STRING(rip_get_output_yuv_matrix, p->m.out().out_yuv_matrix)
-RIP_GET_STRING(rip_get_output_interpolation, p->m.out().out_interp)
-RIP_GET_STRING(rip_get_output_fit, p->m.out().out_fit)
-
-rip_status rip_get_output_normalization(const rip_pipeline* p, double* divisor, double* mean, double* sd) {
-  return guarded(p, [&] {
-    need(p);
-    if (divisor) *divisor = p->m.out().out_divisor;
-    for (int i = 0; i < 3; i++) {
-      if (mean) mean[i] = p->m.out().out_mean[i];
-      if (sd) sd[i] = p->m.out().out_std[i];
-    }
-  });
-}
-
-rip_status rip_get_output_size(const rip_pipeline* p, int* width, int* height) {
-  return guarded(p, [&] {
-    need(p);
-    if (width) *width = p->m.out().out_w;
-    if (height) *height = p->m.out().out_h;
-  });
-}
-
-rip_status rip_get_output_roi(const rip_pipeline* p, int* x, int* y, int* width, int* height) {
-  return guarded(p, [&] {
-    need(p);
-    if (x) *x = p->m.out().roi_x;
-    if (y) *y = p->m.out().roi_y;
-    if (width) *width = p->m.out().roi_w;
-    if (height) *height = p->m.out().roi_h;
-  });
-}
-
-rip_status rip_get_output_pad(const rip_pipeline* p, int* b, int* g, int* r) {
-  return guarded(p, [&] {
-    need(p);
-    if (b) *b = p->m.out().out_pad[0];
-    if (g) *g = p->m.out().out_pad[1];
-    if (r) *r = p->m.out().out_pad[2];
-  });
-}
-
-rip_status rip_get_output_window(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int src_xywh[4], int dst_xywh[4]) {
-  return guarded(p, [&] {
-    need(p);
-    if (!encoding) throw InvalidArgument("encoding is null");
-    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, p->m.selected, pl);
-    const int src[4] = {pl.win_x, pl.win_y, pl.win_w, pl.win_h}, dst[4] = {pl.pic_x, pl.pic_y, pl.pic_w, pl.pic_h};
-    if (src_xywh) std::memcpy(src_xywh, src, sizeof(src));
-    if (dst_xywh) std::memcpy(dst_xywh, dst, sizeof(dst));
-  });
-}
-
 rip_status rip_debug_output_window(int cols, int rows, const int roi_xywh[4], int width, int height, const char* fit, int src_xywh[4], int dst_xywh[4]) {
   return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
     if (!roi_xywh || !fit || !src_xywh || !dst_xywh) throw InvalidArgument("rip_debug_output_window: null argument");
@@ -695,57 +399,6 @@ rip_status rip_debug_output_window(int cols, int rows, const int roi_xywh[4], in
     rip::check_output_roi(roi_xywh[0], roi_xywh[1], roi_xywh[2], roi_xywh[3]);
     rip::check_output_size(width, height);
     rip::output_window_geometry(cols, rows, roi_xywh, width, height, rip::output_fit_id(fit), src_xywh, dst_xywh);
-  });
-}
-
-rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int channels, const char* encoding, int* height, int* width, double K[9],
-                                      double P[12]) {
-  return guarded(p, [&] {
-    need(p);
-    if (!encoding) throw InvalidArgument("encoding is null");
-    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, p->m.selected, pl);
-    const rip::Modules& m = p->m;
-    double k[9], pr[12];
-    for (int i = 0; i < 9; i++) k[i] = pl.remap ? m.rect_K[i] : m.dist_K[i];
-    for (int i = 0; i < 12; i++) pr[i] = pl.remap ? m.rect_P[i] : m.dist_P[i];
-    if (pl.fit_geometry) {
-      // the same mapping from the window that is read to the picture's rectangle: u = (u' - left + 0.5) / a - 0.5 + xs (PARITY.md
-      // "Resize: window and fit"); every operation rounded, in this order
-      const double a = (double)pl.pic_w / pl.win_w, b = (double)pl.pic_h / pl.win_h;
-      const double xs = pl.win_x, ys = pl.win_y, left = pl.pic_x, top = pl.pic_y;
-      k[0] *= a;
-      k[1] *= a;
-      k[2] = (a * ((k[2] - xs) + 0.5) - 0.5) + left;
-      k[4] *= b;
-      k[5] = (b * ((k[5] - ys) + 0.5) - 0.5) + top;
-      pr[0] *= a;
-      pr[1] *= a;
-      pr[2] = (a * ((pr[2] - xs) + 0.5) - 0.5) + left;
-      pr[3] *= a;
-      pr[5] *= b;
-      pr[6] = (b * ((pr[6] - ys) + 0.5) - 0.5) + top;
-      pr[7] *= b;
-    } else if (pl.rsz_active) {
-      // the inverse of the tables' pixel-centre mapping u = (u' + 0.5) / a - 0.5 (PARITY.md "Resize")
-      const double a = (double)pl.dl_cols / pl.out_cols, b = (double)pl.img_rows / pl.out_rows;
-      k[0] *= a;
-      k[1] *= a;
-      k[2] = a * (k[2] + 0.5) - 0.5;
-      k[4] *= b;
-      k[5] = b * (k[5] + 0.5) - 0.5;
-      pr[0] *= a;
-      pr[1] *= a;
-      pr[2] = a * (pr[2] + 0.5) - 0.5;
-      pr[3] *= a;
-      pr[5] *= b;
-      pr[6] = b * (pr[6] + 0.5) - 0.5;
-      pr[7] *= b;
-    }
-    if (height) *height = pl.img_rows;  // the picture, not the buffer a YUV format delivers it in
-    if (width) *width = pl.dl_cols;
-    if (K) std::memcpy(K, k, sizeof(k));
-    if (P) std::memcpy(P, pr, sizeof(pr));
   });
 }
 
@@ -787,14 +440,6 @@ rip_status rip_debug_output_table(const char* name, double divisor, const double
   });
 }
 
-rip_status rip_get_debayer_16bit_range(const rip_pipeline* p, int* black, int* white) {
-  return guarded(p, [&] {
-    need(p);
-    if (black) *black = p->m.raw16_black;
-    if (white) *white = p->m.raw16_white;
-  });
-}
-
 rip_status rip_debug_raw16_narrow(int black, int white, const uint16_t* in, uint8_t* out, size_t n) {
   return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
     rip::check_debayer_16bit_range(black, white);
@@ -833,50 +478,6 @@ rip_status rip_debug_unpack(const char* encoding, const uint8_t* in, size_t step
           default: o[x] = (uint16_t)rip::unpack_sample<rip::PACKED_12_CSI2>(row, x); break;
         }
       }
-    }
-  });
-}
-
-RIP_GET_STRING(rip_get_dist_distortion_model, p->m.und_available ? p->m.dist_model : std::string("none"))  // undistortion.cpp:106-112
-// undistortion.cpp:94-104: "none" once undistortion is enabled (the published image is rectified)
-RIP_GET_STRING(rip_get_rect_distortion_model, p->m.und_available && !p->m.und_enabled ? p->m.rect_model : std::string("none"))
-
-#define RIP_GET_VEC(name, field, n)                              \
-  rip_status name(const rip_pipeline* p, double* out) {          \
-    return guarded(p, [&] {                                      \
-      need(p);                                                   \
-      if (!out) throw InvalidArgument("null output");            \
-      for (int i = 0; i < n; i++) out[i] = (double)p->m.field[i]; \
-    });                                                          \
-  }
-RIP_GET_VEC(rip_get_color_calibration_matrix, cc_matrix, 9)
-RIP_GET_VEC(rip_get_color_calibration_bias, cc_bias, 4)
-RIP_GET_VEC(rip_get_dist_camera_matrix, dist_K, 9)
-RIP_GET_VEC(rip_get_dist_distortion_coefficients, dist_D, 4)
-RIP_GET_VEC(rip_get_dist_rectification_matrix, dist_R, 9)
-RIP_GET_VEC(rip_get_dist_projection_matrix, dist_P, 12)
-RIP_GET_VEC(rip_get_rect_camera_matrix, rect_K, 9)
-RIP_GET_VEC(rip_get_rect_distortion_coefficients, rect_D, 4)
-RIP_GET_VEC(rip_get_rect_rectification_matrix, rect_R, 9)
-RIP_GET_VEC(rip_get_rect_projection_matrix, rect_P, 12)
-
-rip_status rip_get_distortion_coefficients_n(const rip_pipeline* p, int rect, double* out, int capacity, int* n) {
-  return guarded(p, [&] {
-    need(p);
-    if (rect != 0 && rect != 1) throw InvalidArgument("rect must be 0 (dist) or 1 (rect)");
-    const rip::Modules& m = p->m;
-    const int count = rip::distortion_coefficient_count(rect ? m.rect_model : m.dist_model);
-    if (n) *n = count;
-    if (!out) return;  // the count alone
-    if (capacity < count) throw CapacityError("coefficient buffer too small");
-    if (rect) {
-      for (int i = 0; i < count; i++) out[i] = m.rect_D[i];
-    } else if (rip::is_pinhole_model(m.dist_model)) {
-      double k[8];
-      rip::pinhole_coefficients(m.dist_model, m.dist_D, k);  // what the model evaluates: radtan reports k3 = 0
-      for (int i = 0; i < count; i++) out[i] = k[i];
-    } else {
-      for (int i = 0; i < count; i++) out[i] = m.dist_D[i];
     }
   });
 }
@@ -1068,36 +669,6 @@ rip_status rip_get_vignetting_mask(rip_pipeline* p, int rows, int cols, float* o
     std::vector<float> m;
     rip::build_vignette_mask(rows, cols, p->m.vig_scale, p->m.vig_a2, p->m.vig_a4, m, p->fp_contract);
     std::memcpy(out, m.data(), m.size() * sizeof(float));
-  });
-}
-
-rip_status rip_set_tunable(rip_pipeline* p, const char* name, int value) {
-  return guarded(p, [&] {
-    need(p);
-    if (!name) throw InvalidArgument("tunable name is null");
-    if (value < 0) throw InvalidArgument("tunable values are non-negative");
-    const std::string n = name;
-    const rip::Tunables dflt;
-    rip::Tunables& t = p->tn;
-    if (n == "chain_blocks") t.chain_blocks = value;
-    else if (n == "chain_frames") t.chain_frames = value;
-    else if (n == "stats_blocks") t.stats_blocks = value > 0 ? value : dflt.stats_blocks;
-    else if (n == "remap_ring") t.remap_ring = value;
-    else if (n == "remap_stages") t.remap_stages = value > 0 ? value : dflt.remap_stages;
-    else if (n == "remap_per_cu") t.remap_per_cu = value;
-    else if (n == "remap_frames") t.remap_frames = value;
-    else if (n == "remap_fused") t.remap_fused = value;
-    else if (n == "chain_footprint") t.chain_footprint = value != 0;
-    else if (n == "remap_exp") t.remap_exp = value;
-    else if (n == "remap_deal") t.remap_deal = value;
-    else if (n == "remap_order") t.remap_order = value <= 2 ? value : 0;
-    else if (n == "chain_deal") t.chain_deal = value;
-    else if (n == "chain_nt") t.chain_nt = value;
-    else if (n == "remap_tiled") p->use_tiled_remap = value != 0;
-    else if (n == "ccc_lds_hist_min") t.ccc_lds_hist_min = value > 0 ? value : dflt.ccc_lds_hist_min;
-    else if (n == "overlap_groups") t.overlap_groups = value;
-    else if (n == "overlap_mode") t.overlap_mode = value;
-    else throw InvalidArgument("unknown tunable [" + n + "]");
   });
 }
 

@@ -42,6 +42,22 @@ void und_init(rip_pipeline* p) {
   p->maps_generation++;  // the masks built from the maps before this call are no longer current (MaskBaseConst::Key)
 }
 
+// ------------------------------------------------------------------------------------------------
+// what a setting invalidates (rip_settings.cpp): the flags the ensure_* functions below look at, set here and nowhere else
+// ------------------------------------------------------------------------------------------------
+void invalidate_head(rip_pipeline* p, int head, bool table) {
+  p->mask_head[head].valid = false;
+  if (table) p->out_table[head].dirty = true;
+}
+void invalidate_all_heads(rip_pipeline* p) {
+  for (int k = 0; k < rip::kMaxOutputHeads; k++) invalidate_head(p, k, true);
+}
+void invalidate_color_tables(rip_pipeline* p) { p->tables.dirty = true; }
+void invalidate_vignette(rip_pipeline* p) { p->vignette.dirty = true; }
+void invalidate_ccc_config(rip_pipeline* p) { p->ccc.cfg_dirty = true; }
+void invalidate_ccc_model(rip_pipeline* p) { p->ccc.uploaded = false; }
+void restart_ccc_estimator(rip_pipeline* p) { p->ccc.state_init = false; }
+
 // Where the maps are built: on the device for device handles (rip_maps.hip: one thread per map row, FP64, double-double
 // atan -- milliseconds instead of 0.25-0.5 s of host threads per calibration change), on the host for RIP_DEVICE_NONE handles
 // and when RIP_MAPS_ON_HOST is set (A/B and debugging).  Both produce the same floats (tests/test_parity_gpu.py).

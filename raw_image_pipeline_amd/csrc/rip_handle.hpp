@@ -1,7 +1,11 @@
 // rip_handle.hpp -- internal to librip_hip.so (not installed): the handle behind include/rip.h and what the host units
 // share.  rip_plan.cpp turns a frame's geometry and encoding into a Plan, rip_constants.cpp keeps the device-resident constants
-// current, rip_batch.cpp enqueues the kernels of a batch, rip_output_stage.cpp those of the output stage behind it, rip_ring.cpp
-// holds the host-frame calls and their ring, rip_api.cpp the rest of the C ABI.
+// current and says what a setting invalidates, rip_batch.cpp enqueues the kernels of a batch, rip_output_stage.cpp those of the
+// output stage behind it, rip_ring.cpp holds the host-frame calls and their ring, rip_settings.cpp the loaders, setters and
+// getters, rip_api.cpp the rest of the C ABI.  Below the handle, without any HIP call and one header each behind rip_host.hpp:
+// rip_yaml (the config files' reader), rip_params (module parameters, loaders, the checks of the settings), rip_output_tables
+// (output table, window geometry, resize tables), rip_color_tables (gamma, Lab / HSV, vignetting), rip_undistort (maps, remap
+// plan, footprint), rip_ccc_model (model spectra, host FFT) and rip_png (debug dumps).
 #pragma once
 #include "../../include/rip.h"
 
@@ -455,7 +459,10 @@ rip_status guarded(const rip_pipeline* p, F&& fn) {
 // rip_api.cpp
 void need(const rip_pipeline* p);         // a handle
 void need_device(const rip_pipeline* p);  // ... that has a device
+void need_head(const rip_pipeline* p, int head);  // ... and this output head
 void copy_string(const std::string& s, char* out, size_t cap);
+// what the selected head delivers for such a frame: make_plan + apply_output_format, behind the refusal of a null encoding
+Plan delivered_plan(const rip_pipeline* p, int rows, int cols, int channels, const char* encoding);
 
 // rip_plan.cpp: no HIP call
 int parse_packed(const std::string& e, int& ry, int& rx);
@@ -465,6 +472,11 @@ Plan make_plan(const rip::Modules& m, int rows, int cols, int channels, const st
 void apply_output_format(const rip::Modules& m, int head, Plan& pl);
 FrameView tight_output_view(const Plan& pl, void* d_out);
 FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, size_t out_frame_stride);
+// The caller's input frames as a view, the pitches resolved (0: tightly packed) and refused in this order: a row pitch smaller than
+// a row -- resolve_input_pitches, for the frame call that has refusals of its own to place behind this one -- then a frame stride
+// smaller than a frame, then a pitch or a frame too large.
+void resolve_input_pitches(const Plan& pl, int rows, int cols, int channels, size_t& in_step, size_t& in_frame_stride);
+ConstFrameView resolve_input_layout(const Plan& pl, const void* d_in, size_t in_step, size_t in_frame_stride, int rows, int cols, int channels);
 
 // rip_constants.cpp: the device-resident constants, each rebuilt and uploaded when what it was built from has changed
 void und_init(rip_pipeline* p);
@@ -483,6 +495,16 @@ void ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W,
 void ensure_area_tables(rip_pipeline* p, int head, int R, int C, int H, int W, rip::AreaParams& r);
 // filter: 2 (linear_aa) or 3 (cubic_aa), rip::output_interpolation_id's numbers; channels: 1 or 3, picks tile_rows and lds_rows
 void ensure_aa_tables(rip_pipeline* p, int head, int filter, int channels, int R, int C, int H, int W, rip::AaParams& r);
+// What a setting invalidates, said once: the loaders and setters (rip_settings.cpp) call these and und_init and write no flag
+// themselves.  invalidate_head: the delivered mask of output head `head` and, with `table`, its output table (the resize tables
+// are keyed, not flagged); invalidate_all_heads: both of every head.
+void invalidate_head(rip_pipeline* p, int head, bool table);
+void invalidate_all_heads(rip_pipeline* p);
+void invalidate_color_tables(rip_pipeline* p);  // gamma and the Lab / HSV tables (ensure_tables)
+void invalidate_vignette(rip_pipeline* p);      // the mask plane (ensure_vignette)
+void invalidate_ccc_config(rip_pipeline* p);    // the estimator's configuration (ensure_ccc)
+void invalidate_ccc_model(rip_pipeline* p);     // the model spectra on the device
+void restart_ccc_estimator(rip_pipeline* p);    // first frame, new Kalman filter
 
 // rip_batch.cpp: the chain (run_batch) and write_debug_dumps.  rip_output_stage.cpp: everything else down to the end of this
 // namespace -- what follows the chain: resize, pad, converter, heads and masks

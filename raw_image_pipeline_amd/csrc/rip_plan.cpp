@@ -268,4 +268,22 @@ FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, si
   return v;
 }
 
+// The caller's frames of rip_apply_device and rip_apply_device_heads (0 = tight) under the same limits as the output: 32-bit byte
+// offsets inside a frame, 24-bit row multiplies.  The refusals come in two steps, so that rip_apply_device can place refusals of its
+// own between them: resolve_input_pitches is the first, and running it again on resolved pitches changes nothing.
+void resolve_input_pitches(const Plan& pl, int rows, int cols, int channels, size_t& in_step, size_t& in_frame_stride) {
+  const size_t in_row = row_bytes(pl, cols, channels);
+  if (in_step == 0) in_step = in_row;
+  if (in_frame_stride == 0) in_frame_stride = in_step * rows;
+  if (in_step < in_row) throw InvalidArgument("input row pitch smaller than a row");
+}
+
+ConstFrameView resolve_input_layout(const Plan& pl, const void* d_in, size_t in_step, size_t in_frame_stride, int rows, int cols, int channels) {
+  resolve_input_pitches(pl, rows, cols, channels, in_step, in_frame_stride);
+  if (in_frame_stride < in_step * (size_t)(rows - 1) + row_bytes(pl, cols, channels)) throw InvalidArgument("input frame stride smaller than a frame");
+  if (in_step >= (1u << 24) || (unsigned long long)in_step * rows >= (1ull << 32))
+    throw InvalidArgument("row pitch too large: pitches must stay below 16 MiB and a frame below 4 GiB");
+  return {static_cast<const uint8_t*>(d_in), in_step, in_frame_stride, rows, cols};
+}
+
 }  // namespace rip::api

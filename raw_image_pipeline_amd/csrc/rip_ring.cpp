@@ -219,8 +219,7 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
   return guarded(p, [&] {
     need_device(p);
     if (!image || !encoding || !ticket) throw InvalidArgument("null buffer, encoding or ticket");
-    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, p->m.selected, pl);
+    const Plan pl = delivered_plan(p, rows, cols, channels, encoding);  // a null encoding was refused above
     const HostFrameLayout L(p, pl, rows, cols, channels, step);
     {  // destinations given by the caller (rip_submit_to): checked before anything is enqueued or any slot is touched
       if (ext_out && ext_out_capacity < L.out_bytes) throw CapacityError("rip_submit_to: result buffer too small: need " + std::to_string(L.out_bytes) + " bytes");
@@ -335,8 +334,7 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
   return guarded(p, [&] {
     need_device(p);
     if (!image || !out || !encoding) throw InvalidArgument("null buffer or encoding");
-    Plan pl = make_plan(p->m, rows, cols, channels, encoding);
-    apply_output_format(p->m, p->m.selected, pl);
+    const Plan pl = delivered_plan(p, rows, cols, channels, encoding);  // a null encoding was refused above
     DeviceGuard device_guard(p->device);
     const HostFrameLayout L(p, pl, rows, cols, channels, step);
     L.check_step(pl);

@@ -379,7 +379,7 @@ def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path,
     cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
     exe = str(tmp_path / "fit_kernel_host")
     cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "fit_kernel_host.cpp"), os.path.join(csrc, "rip_host.cpp"),
+        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "fit_kernel_host.cpp"), os.path.join(csrc, "rip_output_tables.cpp"),
         "-o", exe, "-lm", "-lpthread"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

@@ -344,7 +344,7 @@ def test_the_kernel_run_on_the_host_equals_the_oracle_byte_for_byte(tmp_path, ri
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "resize_kernel_host.cpp"), os.path.join(csrc, "rip_host.cpp"), obj,
+        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "resize_kernel_host.cpp"), os.path.join(csrc, "rip_output_tables.cpp"), obj,
         "-o", exe, "-lm", "-lpthread"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
