@@ -89,6 +89,16 @@ def main():
     print("nv12:", nv12.shape, "Y", y.shape, "Cb / Cr", cb.shape, "mean (Y, Cb, Cr): %.1f %.1f %.1f" % (y.mean(), cb.mean(), cr.mean()))
     proc.set_output_format("native")
     proc.set_output_size(0, 0)
+    # for a visual-inertial front end: the colour image on head 0 and, from the same chain run, the equalised grey image a feature
+    # tracker wants on head 1 -- cv2.createCLAHE(3.0, (8, 8)).apply(grey) restated, on the GPU
+    proc.set_output_heads(2)
+    proc.select_output_head(1)
+    proc.set_output_format("mono8")
+    proc.set_output_clahe(3.0, 8, 8)
+    proc.select_output_head(0)
+    colour, grey = proc.apply_heads(before, "bgr8")
+    print("heads:", colour.shape, "and mono8 + CLAHE", grey.shape, "std of the grey image %.1f" % grey.std())
+    proc.set_output_heads(1)
     try:
         from PIL import Image
         Image.fromarray(img[..., ::-1]).save(os.path.join(args.out_dir, "output_apply.png"))

@@ -255,6 +255,10 @@ class RawImagePipeline {
   std::string getOutputFit() const { return str(&rip_get_output_fit); }
   void setOutputPad(int b, int g, int r) { check(rip_set_output_pad(h_, b, g, r)); }
   void getOutputPad(int& b, int& g, int& r) const { check(rip_get_output_pad(h_, &b, &g, &r)); }
+  // not in the reference: CLAHE, cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply() restated, on the delivered one-channel
+  // picture (rip.h rip_set_output_clahe): a mono camera, or the format "mono8".  Tiles (0, 0) turn it off.
+  void setOutputClahe(double clip_limit, int tiles_x, int tiles_y) { check(rip_set_output_clahe(h_, clip_limit, tiles_x, tiles_y)); }
+  void getOutputClahe(double& clip_limit, int& tiles_x, int& tiles_y) const { check(rip_get_output_clahe(h_, &clip_limit, &tiles_x, &tiles_y)); }
   void getOutputWindow(int rows, int cols, int channels, const std::string& encoding, int src_xywh[4], int dst_xywh[4]) const {
     check(rip_get_output_window(h_, rows, cols, channels, encoding.c_str(), src_xywh, dst_xywh));
   }

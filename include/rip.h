@@ -347,6 +347,28 @@ rip_status rip_get_output_format(const rip_pipeline* p, char* out, size_t capaci
  * Cost: one launch per batch in the converter's place (3 bytes read, 1.5 written per pixel) and the staging image of F as above. */
 rip_status rip_set_output_yuv_matrix(rip_pipeline* p, const char* name);
 rip_status rip_get_output_yuv_matrix(const rip_pipeline* p, char* out, size_t capacity); /* NUL-terminated copy */
+/* Extension beyond the reference: CLAHE -- contrast-limited adaptive histogram equalisation, cv::createCLAHE(clip_limit,
+ * Size(tiles_x, tiles_y))->apply() for CV_8UC1 restated (PARITY.md "Local contrast: CLAHE"; pinned against no OpenCV binary) -- on the
+ * delivered ONE-CHANNEL picture of the selected output head: what a visual-inertial front end computes on the grey image before it
+ * tracks features.  clip_limit: finite, >= 0, 0 = no clipping.  tiles_x, tiles_y: both in 1 .. 16, or both 0 = off (the default; a
+ * handle that never turns it on launches what it launched before).  Anything else: RIP_ERR_INVALID_ARGUMENT, nothing changed.
+ * The picture is the rectangle the resize writes (rip_get_output_window's dst), or all of the image: letterbox bands are neither
+ * counted nor changed.  CLAHE is the last launch of the head: a one-channel frame under native (or mono8) without a resize goes
+ * through the staging image, behind a resize it is equalised in place in the delivered buffer, and a colour frame under mono8 is
+ * equalised in place behind the converter -- cv::CLAHE of the grey image.  The result does not depend on rip_set_fp_contraction.
+ * Refusals, RIP_ERR_INVALID_ARGUMENT before anything is enqueued (the ccc filter does not advance), from the frame calls, the heads
+ * calls (prefixed "output head <k>: ") and rip_query_output, rip_query_output_bytes, rip_get_output_camera_info and
+ * rip_get_output_window, behind every other refusal of that head and in this order: (a) the delivered picture has more than one
+ * channel (a colour result under native, rgb8, a planar or a YUV format; a bgr16 result) -- set the format mono8; (b) a picture
+ * narrower than 2 tiles_x or lower than 2 tiles_y pixels.
+ * Unchanged: the delivered geometry, rip_get_output_camera_info, rip_get_output_window, the masks, the taps, the white-balance info,
+ * the ccc track and the debug dumps (all on F).  RIP_IMAGE_PROCESSED is empty while CLAHE is active, as under a resize.
+ * Cost: two launches per batch -- one table per (tile, frame), 1 byte read per pixel; the blend, 1 byte read and 1 written per
+ * pixel -- and n_frames x tiles_x x tiles_y x 256 bytes of device memory for the tables.  Works on RIP_DEVICE_NONE handles.
+ * Params YAML: `clahe_clip_limit: 3.0` and `clahe_tiles: [8, 8]` in `output:` and `output_1:` .. `output_7:`; absent keys mean off,
+ * an invalid value fails the load. */
+rip_status rip_set_output_clahe(rip_pipeline* p, double clip_limit, int tiles_x, int tiles_y);
+rip_status rip_get_output_clahe(const rip_pipeline* p, double* clip_limit, int* tiles_x, int* tiles_y); /* any pointer may be null */
 /* Normalisation of the planar output formats; mean and std hold 3 values in the order of the format's planes.  Defaults:
  * divisor 255, mean (0, 0, 0), std (1, 1, 1); divisor 1 gives the raw values.  For plane c and channel value v in 0..255 the
  * delivered element is the table entry T_c[v]: y = (v / divisor - mean_c) / std_c evaluated in double with every operation

@@ -22,6 +22,7 @@
 #include "rip_kernels.hpp"
 #include "rip_output.hpp"
 #include "rip_aa.hpp"
+#include "rip_clahe.hpp"
 #include "rip_area.hpp"
 #include "rip_fit.hpp"
 #include "rip_heads.hpp"
@@ -159,6 +160,11 @@ struct Plan {
   int win_x = 0, win_y = 0, win_w = 0, win_h = 0;
   int pic_x = 0, pic_y = 0, pic_w = 0, pic_h = 0;
   uint8_t pad[4] = {0, 0, 0, 0};
+  // CLAHE on the delivered one-channel picture (rip_set_output_clahe), the last launches of the head; such a head does not deliver F
+  // as it is.  Off: the three other fields are not read.
+  bool clahe = false;
+  int clahe_tx = 0, clahe_ty = 0;
+  double clahe_clip = 0.0;
   bool win_is_frame() const { return win_x == 0 && win_y == 0 && win_w == out_cols && win_h == out_rows; }
   bool pic_is_delivered() const { return pic_w == dl_cols && pic_h == img_rows; }
 };
@@ -382,6 +388,8 @@ struct rip_pipeline {
   // output and resize stage: the pipeline's final image of a batch slice in front of the converter, and the resized image of the slice
   // in front of the converter (only under a format); rows of both padded to 16 bytes
   rip::api::DevBuf d_fmt, d_rsz;
+  // the tables of a head's CLAHE (rip_clahe.hpp), n frames x tiles x 256 bytes: written and read inside one call, nothing is kept
+  rip::api::DevBuf d_clahe;
   int last_chain_walked = 0;  // items per frame the last chain launch of run_batch walked (rip_debug_chain_footprint)
   bool use_tiled_remap = true;
   int last_batch_frames = 0;

@@ -1,7 +1,8 @@
 // rip_output_stage.cpp -- everything behind the pipeline's image F: the staging image the chain's last kernel writes, the resize,
 // pad, converter and YUV launches of one output head (prepare_head, enqueue_head), several heads from one run of the chain
 // (run_batch_heads) and the valid-pixel masks, which run a head's launches on the coverage image.  The kernels live in the
-// companion libraries (rip_output/resize/area/fit/aa/heads/mask/yuv.hpp); the chain in front is rip_batch.cpp's run_batch.
+// companion libraries (rip_output/resize/area/fit/aa/heads/mask/yuv.hpp) and in librip_clahe_hip.so (rip_clahe.hpp), whose two launches
+// end a head that equalises its picture; the chain in front is rip_batch.cpp's run_batch.
 #include <algorithm>
 
 #include "rip_handle.hpp"
@@ -68,6 +69,9 @@ size_t rsz_bytes(const Plan& pl, int n) {
   return resized_view(pl).frame_stride * (size_t)n;
 }
 
+// bytes of d_clahe a head needs for n frames: the tables of its CLAHE
+size_t clahe_bytes(const Plan& pl, int n) { return pl.clahe ? rip::clahe_lut_bytes(pl.clahe_tx, pl.clahe_ty, n) : 0; }
+
 HeadPrep prepare_head(rip_pipeline* p, const Plan& pl, const FrameView& staged, int n) {
   HeadPrep hp;
   if (pl.dl_planar) ensure_output_table(p, pl.head, pl.out_fmt);
@@ -83,6 +87,7 @@ HeadPrep prepare_head(rip_pipeline* p, const Plan& pl, const FrameView& staged, 
       hp.converted_from.ptr = p->d_rsz.as<uint8_t>();
     }
   }
+  p->d_clahe.reserve(clahe_bytes(pl, n));  // several heads: as d_rsz
   return hp;
 }
 
@@ -95,10 +100,9 @@ void launched(bool accepted, const Info& info, const char* what, int n) {
   RIP_LOG_LAUNCH(dim3(info.grid_x, info.grid_y), info.block, n, "%s", info.kernel);
 }
 
-// The launches behind F for one head: the resize, window resize, area or antialiased launch, then the pad, then the converter, reading
-// F in `staged` (16-byte aligned base, pitch and frame stride) and writing the head's delivered frames `dst`.
-void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const FrameView& staged, FrameView dst, int n) {
-  LaunchLogScope log_scope(p);
+// The launches behind F for one head up to its delivered image: the resize, window resize, area or antialiased launch, then the pad,
+// then the converter, reading F in `staged` (16-byte aligned base, pitch and frame stride) and writing the head's delivered frames `dst`.
+void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const FrameView& staged, FrameView dst, int n) {
   // F': the caller's buffer under "native", else the second staging image; the picture's rectangle of it is what the resize writes
   const FrameView whole_to = pl.out_fmt != rip::OUT_NATIVE ? hp.converted_from : dst;
   FrameView to = whole_to;
@@ -160,8 +164,31 @@ void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const Fra
   launched(rip::launch_output_convert(c, p->stream, &out_info), out_info, "the output converter", n);
 }
 
+// Every launch of one head: its delivered image, then CLAHE on the picture's rectangle of it (PARITY.md "Local contrast: CLAHE") -- in
+// place in the delivered buffer, or, where nothing else is launched, from the staging image into the delivered buffer.  The tables
+// in d_clahe are written by the first launch and read by the second.
+void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const FrameView& staged, FrameView dst, int n) {
+  LaunchLogScope log_scope(p);
+  enqueue_head_image(p, pl, hp, staged, dst, n);
+  if (!pl.clahe) return;
+  const bool from_staging = pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active;
+  rip::ClaheParams c = {};
+  bind_dst(c, dst);
+  c.dst += (size_t)pl.pic_y * dst.step + (size_t)pl.pic_x;
+  if (from_staging) bind_src(c, staged);  // the picture is all of F
+  else c.src = c.dst, c.src_step = c.dst_step, c.src_frame_stride = c.dst_frame_stride;
+  c.lut = p->d_clahe.as<uint8_t>();
+  c.rows = pl.pic_h;
+  c.cols = pl.pic_w;
+  c.n_frames = n;
+  rip::clahe_constants(pl.pic_h, pl.pic_w, pl.clahe_tx, pl.clahe_ty, pl.clahe_clip, c);
+  rip::ClaheLaunchInfo info = {};
+  launched(rip::launch_clahe_lut(c, p->stream, &info), info, "the CLAHE tables", n);
+  launched(rip::launch_clahe_apply(c, p->stream, &info), info, "the CLAHE blend", n);
+}
+
 // a head that launches nothing behind F: the pipeline's image as it is
-bool identity_head(const Plan& pl) { return pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active; }
+bool identity_head(const Plan& pl) { return pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active && !pl.clahe; }
 
 MaskBaseConst::Key mask_base_key(const rip_pipeline* p, bool remap, int src_rows, int src_cols, int rows, int cols) {
   MaskBaseConst::Key k;
@@ -227,6 +254,10 @@ void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const F
   for (int k = 0; k < n_heads; k++)
     if (dsts[k].ptr) rsz = std::max(rsz, rsz_bytes(plans[k], n));
   p->d_rsz.reserve(rsz);
+  size_t clahe = 0;
+  for (int k = 0; k < n_heads; k++)
+    if (dsts[k].ptr) clahe = std::max(clahe, clahe_bytes(plans[k], n));
+  p->d_clahe.reserve(clahe);
   HeadPrep hp[rip::kMaxOutputHeads];
   for (int k = 0; k < n_heads; k++)
     if (dsts[k].ptr && !identity_head(plans[k])) hp[k] = prepare_head(p, plans[k], staged, n);
@@ -304,6 +335,7 @@ ConstFrameView ensure_mask_head(rip_pipeline* p, const Plan& frame_pl, int mode)
   pl.channels = pl.dl_channels = 1;
   pl.out_elem_bytes = pl.dl_elem_bytes = 1;
   pl.fmt_active = pl.dl_planar = false;
+  pl.clahe = false;  // a mask is coverage, not a picture
   pl.out_fmt = rip::OUT_NATIVE;
   pl.dl_rows = pl.img_rows;  // a mask ignores the format: the picture's rows under a YUV format too
   for (uint8_t& c : pl.pad) c = 0;

@@ -83,7 +83,20 @@ OutputHead output_head_from_node(const YamlNode& o, const std::string& sec) {
   (void)output_fit_id(out_fit);
   if (o["fit"].defined() && o["fit"].kind != YamlNode::Scalar)
     throw std::invalid_argument(sec + ": fit: one word is expected, \"stretch\", \"letterbox\" or \"crop\"");
+  // extension keys output: clahe_clip_limit: 3.0 / clahe_tiles: [tiles_x, tiles_y] (rip_set_output_clahe); absent keys mean off
+  const double clahe_clip_limit = o.get("clahe_clip_limit", 0.0);
+  int clahe_tiles[2] = {0, 0};
+  if (o["clahe_tiles"].defined()) {
+    const std::vector<double> v = o.get_vector("clahe_tiles");
+    if (v.size() != 2 || !(v[0] >= 0 && v[0] <= 16 && v[1] >= 0 && v[1] <= 16) || v[0] != std::floor(v[0]) || v[1] != std::floor(v[1]))
+      throw std::invalid_argument(sec + ": clahe_tiles: a sequence [tiles_x, tiles_y] of two integers in 1..16 (or [0, 0]) is expected");
+    clahe_tiles[0] = (int)v[0];
+    clahe_tiles[1] = (int)v[1];
+  }
+  check_output_clahe(clahe_clip_limit, clahe_tiles[0], clahe_tiles[1]);
   OutputHead h;
+  h.clahe_clip_limit = clahe_clip_limit;
+  h.clahe_tiles_x = clahe_tiles[0], h.clahe_tiles_y = clahe_tiles[1];
   h.roi_x = roi[0], h.roi_y = roi[1], h.roi_w = roi[2], h.roi_h = roi[3];
   h.out_fit = out_fit;
   for (int i = 0; i < 3; i++) h.out_pad[i] = pad[i];
@@ -275,6 +288,14 @@ void check_output_pad(int b, int g, int r) {
   for (int v : {b, g, r})
     if (v < 0 || v > 255)
       throw std::invalid_argument("output pad (" + std::to_string(b) + ", " + std::to_string(g) + ", " + std::to_string(r) + ") not supported: every component is in 0..255");
+}
+
+void check_output_clahe(double clip_limit, int tiles_x, int tiles_y) {
+  if (!std::isfinite(clip_limit) || clip_limit < 0)
+    throw std::invalid_argument("output clahe: the clip limit must be finite and at least 0 (0: no clipping), got " + std::to_string(clip_limit));
+  const bool off = tiles_x == 0 && tiles_y == 0;
+  if (!off && (tiles_x < 1 || tiles_x > 16 || tiles_y < 1 || tiles_y > 16))
+    throw std::invalid_argument("output clahe: tiles (" + std::to_string(tiles_x) + ", " + std::to_string(tiles_y) + ") not supported: both in 1..16, or (0, 0) for off");
 }
 
 int output_interpolation_id(const std::string& name) {

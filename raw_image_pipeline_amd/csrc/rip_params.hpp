@@ -30,6 +30,10 @@ struct OutputHead {
   int roi_x = 0, roi_y = 0, roi_w = 0, roi_h = 0;
   std::string out_fit = "stretch";
   int out_pad[3] = {114, 114, 114};
+  // extension (rip_set_output_clahe; PARITY.md "Local contrast: CLAHE"): cv::CLAHE on the delivered one-channel picture, the last
+  // launch of the head; tiles (0, 0) = off
+  double clahe_clip_limit = 0.0;
+  int clahe_tiles_x = 0, clahe_tiles_y = 0;
 };
 
 struct Modules {
@@ -114,6 +118,8 @@ void check_output_roi(int x, int y, int width, int height);
 int output_fit_id(const std::string& name);
 // the pad colours rip_set_output_pad accepts: every component in 0 .. 255; throws std::invalid_argument
 void check_output_pad(int b, int g, int r);
+// the settings rip_set_output_clahe accepts: a finite clip limit >= 0 and tiles both in 1 .. 16 or both 0; throws std::invalid_argument
+void check_output_clahe(double clip_limit, int tiles_x, int tiles_y);
 bool load_camera_calibration_file(Modules& m, const std::string& path); // undistortion.cpp:157-195
 bool load_color_calibration_file(Modules& m, const std::string& path);  // color_calibration.cpp:52-76
 void apply_example_camera_calibration(Modules& m);  // values of config/alphasense_calib_example.yaml

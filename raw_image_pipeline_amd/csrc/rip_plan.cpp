@@ -146,7 +146,8 @@ Plan make_plan(const rip::Modules& m, int rows, int cols, int channels, const st
 // The output stage on top of a plan (rip_set_output_format): what the frame calls and rip_query_output deliver.  The taps, the
 // debug dumps and rip_query_taps stay with make_plan's image.  Throws before anything is enqueued where the format does not apply.
 // head: whose settings (rip_set_output_heads); the single-output calls pass the selected one.
-void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
+namespace {
+void apply_format_and_size(const rip::Modules& mods, int head, Plan& pl) {
   const rip::OutputHead& m = mods.heads[head];
   pl.head = head;
   pl.dl_channels = pl.channels;
@@ -239,6 +240,24 @@ void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
   pl.dl_elem_bytes = rip::output_format_elem_bytes(fmt);
   pl.dl_planar = rip::output_format_planar(fmt);
   pl.encoding_out = m.out_format;
+}
+}  // namespace
+
+// The format, the resize and -- behind every refusal of theirs -- CLAHE on the delivered one-channel picture (rip_set_output_clahe;
+// PARITY.md "Local contrast: CLAHE"), which changes nothing about the delivered geometry.
+void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
+  apply_format_and_size(mods, head, pl);
+  const rip::OutputHead& m = mods.heads[head];
+  if (m.clahe_tiles_x == 0) return;
+  if (pl.dl_channels != 1 || pl.dl_elem_bytes != 1 || rip::output_format_yuv(pl.out_fmt))
+    throw InvalidArgument("output clahe needs a delivered one-channel 8-bit picture; this head delivers [" + pl.encoding_out + "] (set the output format 'mono8', or the clahe tiles (0, 0))");
+  if (pl.pic_w < 2 * m.clahe_tiles_x || pl.pic_h < 2 * m.clahe_tiles_y)
+    throw InvalidArgument("output clahe: the delivered picture of " + std::to_string(pl.pic_w) + " x " + std::to_string(pl.pic_h) + " is smaller than two pixels per tile and side under the tiles (" +
+                          std::to_string(m.clahe_tiles_x) + ", " + std::to_string(m.clahe_tiles_y) + ")");
+  pl.clahe = true;
+  pl.clahe_tx = m.clahe_tiles_x;
+  pl.clahe_ty = m.clahe_tiles_y;
+  pl.clahe_clip = m.clahe_clip_limit;
 }
 
 // The tightly packed DELIVERED frames at d_out: what a row pitch and a frame stride of 0 stand for.  Planar formats: `step` is

@@ -351,7 +351,7 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     HIP_CHECK(hipStreamSynchronize(p->stream));
     const bool eb1 = pl.out_elem_bytes == 1;
     if (p->m.debug && eb1) {
-      if (pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active) {
+      if (pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active && !pl.clahe) {
         write_debug_dumps(p, pl, src, out);
       } else {  // the dumps show the pipeline's image, not the delivered buffer: fetch it from the staging buffer
         const size_t row = (size_t)pl.out_cols * pl.channels;
@@ -365,8 +365,8 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     for (int i = 0; i < 3; i++) p->last_valid[i] = false;
     remember_last(p, RIP_IMAGE_DEBAYERED, &p->d_tap_deb, nullptr, pl.mid_rows, pl.mid_cols, pl.channels, L.keep_deb);
     remember_last(p, RIP_IMAGE_COLOR, &p->d_tap_col, nullptr, pl.mid_rows, pl.mid_cols, pl.channels, L.keep_col);
-    // under a format or a resize the delivered buffer is the result (as for bgr16): no PROCESSED image
-    remember_last(p, RIP_IMAGE_PROCESSED, &p->d_out, nullptr, pl.out_rows, pl.out_cols, pl.channels, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1 && !pl.fmt_active && !pl.rsz_active);
+    // under a format, a resize or CLAHE the delivered buffer is the result (as for bgr16): no PROCESSED image
+    remember_last(p, RIP_IMAGE_PROCESSED, &p->d_out, nullptr, pl.out_rows, pl.out_cols, pl.channels, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1 && !pl.fmt_active && !pl.rsz_active && !pl.clahe);
     remember_mask_frame(p, pl);
     if (out_rows) *out_rows = pl.dl_rows;
     if (out_cols) *out_cols = pl.dl_cols;
@@ -476,7 +476,7 @@ rip_status rip_collect(rip_pipeline* p, uint64_t ticket, uint8_t* out, size_t ou
     // they may be freed or edited, so the getters go back to the device image in the slot this frame keeps held.
     remember_last(p, RIP_IMAGE_DEBAYERED, &sl->d_tap_deb, sl->dl_deb && sl->dst_tap[0] == sl->h_tap[0] ? sl->dst_tap[0] : nullptr, pl.mid_rows, pl.mid_cols, pl.channels, sl->has_deb);
     remember_last(p, RIP_IMAGE_COLOR, &sl->d_tap_col, sl->dl_col && sl->dst_tap[1] == sl->h_tap[1] ? sl->dst_tap[1] : nullptr, pl.mid_rows, pl.mid_cols, pl.channels, sl->has_col);
-    remember_last(p, RIP_IMAGE_PROCESSED, &sl->d_out, sl->dst_out == sl->h_out ? sl->dst_out : nullptr, pl.out_rows, pl.out_cols, pl.channels, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1 && !pl.fmt_active && !pl.rsz_active);
+    remember_last(p, RIP_IMAGE_PROCESSED, &sl->d_out, sl->dst_out == sl->h_out ? sl->dst_out : nullptr, pl.out_rows, pl.out_cols, pl.channels, (p->tap_mask & RIP_TAP_PROCESSED) != 0 && eb1 && !pl.fmt_active && !pl.rsz_active && !pl.clahe);
     remember_mask_frame(p, pl);
     if (out_rows) *out_rows = pl.dl_rows;
     if (out_cols) *out_cols = pl.dl_cols;

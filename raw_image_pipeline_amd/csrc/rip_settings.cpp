@@ -296,6 +296,16 @@ rip_status rip_set_output_pad(rip_pipeline* p, int b, int g, int r) {
     p->m.out().out_pad[2] = r;
   });
 }
+rip_status rip_set_output_clahe(rip_pipeline* p, double clip_limit, int tiles_x, int tiles_y) {
+  return guarded(p, [&] {
+    need(p);
+    invalidate_head(p, p->m.selected, false);
+    rip::check_output_clahe(clip_limit, tiles_x, tiles_y);
+    p->m.out().clahe_clip_limit = clip_limit;
+    p->m.out().clahe_tiles_x = tiles_x;
+    p->m.out().clahe_tiles_y = tiles_y;
+  });
+}
 rip_status rip_set_flip(rip_pipeline* p, int v) {
   return guarded(p, [&] {
     need(p);
@@ -610,6 +620,15 @@ rip_status rip_get_output_pad(const rip_pipeline* p, int* b, int* g, int* r) {
     if (b) *b = p->m.out().out_pad[0];
     if (g) *g = p->m.out().out_pad[1];
     if (r) *r = p->m.out().out_pad[2];
+  });
+}
+
+rip_status rip_get_output_clahe(const rip_pipeline* p, double* clip_limit, int* tiles_x, int* tiles_y) {
+  return guarded(p, [&] {
+    need(p);
+    if (clip_limit) *clip_limit = p->m.out().clahe_clip_limit;
+    if (tiles_x) *tiles_x = p->m.out().clahe_tiles_x;
+    if (tiles_y) *tiles_y = p->m.out().clahe_tiles_y;
   });
 }
 

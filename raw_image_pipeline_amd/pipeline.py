@@ -939,6 +939,18 @@ class RawImagePipeline:
         self._call("rip_get_output_pad", *[C.byref(i) for i in v])
         return tuple(i.value for i in v)
 
+    def set_output_clahe(self, clip_limit, tiles_x, tiles_y):
+        """Extension: CLAHE, ``cv2.createCLAHE(clip_limit, (tiles_x, tiles_y)).apply`` restated, on the delivered one-channel picture
+        of the selected output head (a mono camera, or the format "mono8"); the last launch of the head, letterbox bands stay as they
+        are.  clip_limit >= 0 (0: no clipping), tiles both in 1..16 or (0, 0) for off.  include/rip.h rip_set_output_clahe."""
+        self._call("rip_set_output_clahe", C.c_double(clip_limit), int(tiles_x), int(tiles_y))
+
+    def get_output_clahe(self):
+        """(clip_limit, tiles_x, tiles_y) of the selected output head."""
+        clip, tx, ty = C.c_double(), C.c_int(), C.c_int()
+        self._call("rip_get_output_clahe", C.byref(clip), C.byref(tx), C.byref(ty))
+        return clip.value, tx.value, ty.value
+
     def get_output_window(self, rows, cols, channels, encoding):
         """((x, y, w, h) of the final image that is read, (x, y, w, h) of the delivered image that holds picture) for such an input
         frame; everything outside the second rectangle is pad.  include/rip.h rip_get_output_window."""
