@@ -87,6 +87,14 @@ def main():
     nv12 = proc.process(before, "bgr8")
     y, cb, cr = yuv_planes(nv12, "nv12")
     print("nv12:", nv12.shape, "Y", y.shape, "Cb / Cr", cb.shape, "mean (Y, Cb, Cr): %.1f %.1f %.1f" % (y.mean(), cb.mean(), cr.mean()))
+    # the same picture as a baseline JPEG, encoded on the GPU: process() returns the stream, trimmed to its length
+    proc.set_output_format("jpeg")
+    proc.set_output_jpeg(90, 1)
+    stream = proc.process(before, "bgr8")
+    jpg = os.path.join(args.out_dir, "apply_pipeline.jpg")
+    with open(jpg, "wb") as f:
+        f.write(stream.tobytes())
+    print("jpeg: %d bytes (quality 90) -> %s" % (stream.size, jpg))
     proc.set_output_format("native")
     proc.set_output_size(0, 0)
     # for a visual-inertial front end: the colour image on head 0 and, from the same chain run, the equalised grey image a feature

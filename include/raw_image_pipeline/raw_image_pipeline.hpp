@@ -259,6 +259,17 @@ class RawImagePipeline {
   // picture (rip.h rip_set_output_clahe): a mono camera, or the format "mono8".  Tiles (0, 0) turn it off.
   void setOutputClahe(double clip_limit, int tiles_x, int tiles_y) { check(rip_set_output_clahe(h_, clip_limit, tiles_x, tiles_y)); }
   void getOutputClahe(double& clip_limit, int& tiles_x, int& tiles_y) const { check(rip_get_output_clahe(h_, &clip_limit, &tiles_x, &tiles_y)); }
+  // Extension: quality (1..100) and MCU rows per restart interval (1..64) of the output format "jpeg" (rip.h rip_set_output_jpeg), and
+  // the stream lengths of the frames of the selected head's last frame call (0: the stream did not fit its slot).
+  void setOutputJpeg(int quality, int restart_rows) { check(rip_set_output_jpeg(h_, quality, restart_rows)); }
+  void getOutputJpeg(int& quality, int& restart_rows) const { check(rip_get_output_jpeg(h_, &quality, &restart_rows)); }
+  std::vector<uint32_t> getOutputJpegSizes() {
+    int n = 0;
+    check(rip_get_output_jpeg_sizes(h_, nullptr, 0, &n));
+    std::vector<uint32_t> sizes((size_t)n);
+    if (n) check(rip_get_output_jpeg_sizes(h_, sizes.data(), n, &n));
+    return sizes;
+  }
   void getOutputWindow(int rows, int cols, int channels, const std::string& encoding, int src_xywh[4], int dst_xywh[4]) const {
     check(rip_get_output_window(h_, rows, cols, channels, encoding.c_str(), src_xywh, dst_xywh));
   }

@@ -294,6 +294,8 @@ rip_status rip_get_debayer_method(const rip_pipeline* p, char* out, size_t capac
  *   rgb_chw_f32 / rgb_chw_f16 / rgb_chw_bf16   planes R, G, B of T_c[v] (rip_set_output_normalization); 4 / 2 / 2 bytes per
  *   bgr_chw_f32 / bgr_chw_f16 / bgr_chw_bf16   planes B, G, R                       element; planar, 3 planes of out_rows x out_cols
  *   nv12 / i420        YUV 4:2:0 for encoders (rip_set_output_yuv_matrix below); uint8, one channel of 3 H / 2 rows x W bytes
+ *   jpeg               one baseline JFIF stream per frame, encoded on the device (rip_set_output_jpeg below); uint8, one row of
+ *                      `slot` bytes per frame; also takes a one-channel result
  * A format other than native needs a three-channel 8-bit pipeline result (Bayer 8-bit, 16-bit with a range, packed, bgr8 and rgb8
  * frames).  mono8 on a one-channel 8-bit result is the identity (no kernel); every other format on a one-channel result, and every
  * format other than native on a bgr16 result, fails the frame call and rip_query_output with RIP_ERR_INVALID_ARGUMENT: nothing is
@@ -369,6 +371,47 @@ rip_status rip_get_output_yuv_matrix(const rip_pipeline* p, char* out, size_t ca
  * an invalid value fails the load. */
 rip_status rip_set_output_clahe(rip_pipeline* p, double clip_limit, int tiles_x, int tiles_y);
 rip_status rip_get_output_clahe(const rip_pipeline* p, double* clip_limit, int* tiles_x, int* tiles_y); /* any pointer may be null */
+/* The format "jpeg" (PARITY.md "Output formats: JPEG"): the delivered 8-bit picture of H rows x W columns (F, or F' behind a resize,
+ * window or letterbox, where "nv12" sits) as a baseline JFIF 1.01 stream -- three components Y Cb Cr 4:2:0 from a three-channel
+ * result, one component from a one-channel result -- that every JPEG decoder opens.  Exact integer arithmetic, tolerance 0 against
+ * tests/jpeg_reference.py: full-range BT.601 (the "bt601_full" row of rip_set_output_yuv_matrix, whatever that setting says), the
+ * picture extended to whole MCUs (16 x 16, or 8 x 8 for one component) by repeating its last column and row -- odd sizes are fine
+ * --, an integer forward DCT, the Annex K tables scaled by the IJG rule for `quality` (1 .. 100, default 90), the Annex K Huffman
+ * tables, a restart interval of `restart_rows` MCU rows (1 .. 64, default 1) with RSTm markers.  Header: SOI, APP0, DQT, SOF0 (the
+ * true H and W), DHT, DRI, SOS; then the scan and EOI.  The setting has no effect under any other format; anything outside the
+ * ranges: RIP_ERR_INVALID_ARGUMENT, nothing changed.
+ * Delivered buffer: one SLOT per frame.  rip_query_output reports out_rows 1, out_cols slot, out_channels 1 and "jpeg";
+ * rip_query_output_bytes gives the default slot: header (613 bytes, 330 for one component) + one byte per coded sample of the
+ * extended picture (1.5 per pixel, 1 for one component) + 2 per restart interval + 2.  rip_apply_device(_heads): a non-zero out_step
+ * is the capacity of a slot the caller chose, at least header + 2; out_frame_stride (0 = the slot) is at least the slot.  A stream
+ * starts at its slot's first byte, at any alignment; the bytes of a slot behind the stream and between slots keep their contents.
+ * A stream's length depends on the picture: rip_get_output_jpeg_sizes gives the lengths of the frames of the selected head's last
+ * frame call (it waits for the handle's stream; sizes null: the count only; capacity below the count: RIP_ERR_CAPACITY).  The
+ * count is 0 before the first frame call, after a frame call that delivered another format from that head and for a head
+ * rip_set_output_heads has reset; a refused frame call, which enqueues nothing, leaves the lengths of the call before;
+ * rip_get_output_jpeg_sizes_device the device array the kernels wrote (valid until that head's next frame call, ordered on the
+ * handle's stream).  OVERFLOW: a frame whose stream does not fit its slot gets the length 0 and its slot is not written at all;
+ * the call still returns RIP_OK and the other frames are unaffected.  The lengths are known before a byte of a stream is written.
+ * rip_apply and rip_apply_heads check the capacity against the default slot, download the length first and then only the used
+ * bytes; rip_submit, rip_submit_to (and so rip_collect) refuse a jpeg head with RIP_ERR_INVALID_ARGUMENT before anything is enqueued.
+ * Refusals, RIP_ERR_INVALID_ARGUMENT before anything is enqueued (the ccc filter does not advance), behind the refusals of the
+ * resize and in this order: a bgr16 result (the message of every other format); CLAHE on the same head; a picture beyond 65535
+ * pixels per side or a restart interval beyond 65535 MCUs (the stream's 16-bit fields); from rip_apply_device(_heads) a slot below
+ * header + 2.
+ * Unchanged: rip_get_output_camera_info, rip_get_output_window and rip_get_output_mask (they describe the picture), the taps, the
+ * white-balance info, the ccc track and the debug dumps.  A handle that never asks for "jpeg" launches, allocates and delivers what
+ * it did before.
+ * Cost: four launches per batch slice -- transform, sizing pass, scan, writing pass -- and device memory of 2 bytes per coded sample
+ * (the quantised coefficients) plus 4 bytes per restart interval and frame; no stream is staged.  Works on RIP_DEVICE_NONE handles
+ * (the setters, getters and queries).  Params YAML: `jpeg_quality: 90` and `jpeg_restart_rows: 1` in `output:` and `output_1:` ..
+ * `output_7:`; absent keys mean the defaults, an invalid value fails the load. */
+rip_status rip_set_output_jpeg(rip_pipeline* p, int quality, int restart_rows);
+rip_status rip_get_output_jpeg(const rip_pipeline* p, int* quality, int* restart_rows); /* any pointer may be null */
+rip_status rip_get_output_jpeg_sizes(rip_pipeline* p, uint32_t* sizes, int capacity, int* n);
+rip_status rip_get_output_jpeg_sizes_device(rip_pipeline* p, const uint32_t** d_sizes, int* n);
+/* The tables of a quality as the kernels read them, in natural (row-major) order, luminance then chrominance: the 2 x 64 divisors Q,
+ * the reciprocals ceil(2^32 / (8 Q)) and the rounding terms 4 Q.  No handle is needed. */
+rip_status rip_debug_jpeg_tables(int quality, uint8_t* q, uint32_t* recip, uint32_t* half);
 /* Normalisation of the planar output formats; mean and std hold 3 values in the order of the format's planes.  Defaults:
  * divisor 255, mean (0, 0, 0), std (1, 1, 1); divisor 1 gives the raw values.  For plane c and channel value v in 0..255 the
  * delivered element is the table entry T_c[v]: y = (v / divisor - mean_c) / std_c evaluated in double with every operation

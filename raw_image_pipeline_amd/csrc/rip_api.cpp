@@ -276,10 +276,11 @@ rip_status rip_apply_device(rip_pipeline* p, const void* d_in, size_t in_step, s
     // several kernels put the frame index on gridDim.y (<= 65535): longer batches go through in slices.  The
     // frames of a stream are processed in order either way (the ccc Kalman state lives on the device).
     constexpr int kMaxFramesPerLaunch = 16384;
+    begin_jpeg_call(p, pl, n_frames);
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
       const Taps taps = {d_tap_debayered ? static_cast<uint8_t*>(d_tap_debayered) + (size_t)f0 * tap_frame : nullptr,
                          d_tap_color ? static_cast<uint8_t*>(d_tap_color) + (size_t)f0 * tap_frame : nullptr};
-      run_batch_formatted(p, pl, frames_from(src, f0), frames_from(dst, f0), taps, std::min(kMaxFramesPerLaunch, n_frames - f0));
+      run_batch_formatted(p, pl, frames_from(src, f0), frames_from(dst, f0), taps, std::min(kMaxFramesPerLaunch, n_frames - f0), f0);
     }
     remember_mask_frame(p, pl);
   });
@@ -318,14 +319,51 @@ rip_status rip_apply_device_heads(rip_pipeline* p, const void* d_in, size_t in_s
     const ConstFrameView src = resolve_input_layout(pl, d_in, in_step, in_frame_stride, rows, cols, channels);  // rip_apply_device's rules
     const size_t tap_frame = (size_t)pl.mid_rows * pl.mid_cols * pl.channels;
     constexpr int kMaxFramesPerLaunch = 16384;  // rip_apply_device's slices: per slice the chain runs once, then the heads
+    for (int k = 0; k < n_heads; k++)
+      if (requested[k]) begin_jpeg_call(p, plans[k], n_frames);
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFramesPerLaunch) {
       const Taps taps = {d_tap_debayered ? static_cast<uint8_t*>(d_tap_debayered) + (size_t)f0 * tap_frame : nullptr,
                          d_tap_color ? static_cast<uint8_t*>(d_tap_color) + (size_t)f0 * tap_frame : nullptr};
       FrameView slice[RIP_MAX_OUTPUT_HEADS];
       for (int k = 0; k < n_heads; k++) slice[k] = requested[k] ? frames_from(dsts[k], f0) : dsts[k];
-      run_batch_heads(p, pl, plans, slice, n_heads, frames_from(src, f0), taps, std::min(kMaxFramesPerLaunch, n_frames - f0));
+      run_batch_heads(p, pl, plans, slice, n_heads, frames_from(src, f0), taps, std::min(kMaxFramesPerLaunch, n_frames - f0), f0);
     }
     remember_mask_frame(p, pl);
+  });
+}
+
+// ---- the stream lengths of a "jpeg" head -----------------------------------------------------------
+rip_status rip_get_output_jpeg_sizes(rip_pipeline* p, uint32_t* sizes, int capacity, int* n) {
+  return guarded(p, [&] {
+    need_device(p);
+    const int head = p->m.selected, frames = p->jpeg_frames[head];
+    if (n) *n = frames;
+    if (!sizes) return;  // the count only
+    if (capacity < frames) throw CapacityError("jpeg sizes: room for " + std::to_string(frames) + " frames is needed");
+    DeviceGuard device_guard(p->device);
+    if (frames) HIP_CHECK(hipMemcpyAsync(sizes, p->d_jpeg_sizes[head].ptr, (size_t)frames * 4, hipMemcpyDeviceToHost, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
+  });
+}
+
+rip_status rip_get_output_jpeg_sizes_device(rip_pipeline* p, const uint32_t** d_sizes, int* n) {
+  return guarded(p, [&] {
+    need_device(p);
+    if (!d_sizes) throw InvalidArgument("null sizes pointer");
+    const int head = p->m.selected;
+    *d_sizes = p->jpeg_frames[head] ? p->d_jpeg_sizes[head].as<uint32_t>() : nullptr;
+    if (n) *n = p->jpeg_frames[head];
+  });
+}
+
+rip_status rip_debug_jpeg_tables(int quality, uint8_t* q, uint32_t* recip, uint32_t* half) {
+  return guarded(static_cast<const rip_pipeline*>(nullptr), [&] {
+    rip::check_output_jpeg(quality, 1);
+    if (!q || !recip || !half) throw InvalidArgument("rip_debug_jpeg_tables: null argument");
+    rip::JpegTables t;
+    rip::jpeg_build_tables(quality, t, q);
+    std::memcpy(recip, t.recip, sizeof(t.recip));
+    std::memcpy(half, t.half, sizeof(t.half));
   });
 }
 
@@ -344,10 +382,10 @@ rip_status rip_get_output_mask(rip_pipeline* p, int rows, int cols, int channels
   return guarded(p, [&] {
     int mode = 0;
     const Plan pl = output_mask_plan(p, rows, cols, channels, encoding, &mode);
-    const size_t bytes = (size_t)pl.img_rows * (size_t)pl.dl_cols;  // a mask is the picture's, whatever the format
+    const size_t bytes = (size_t)pl.img_rows * (size_t)pl.dl_pic_cols;  // a mask is the picture's, whatever the format
     if (out && capacity < bytes) throw CapacityError("mask buffer too small: need " + std::to_string(bytes) + " bytes");
     if (height) *height = pl.img_rows;
-    if (width) *width = pl.dl_cols;
+    if (width) *width = pl.dl_pic_cols;
     if (!out) return;  // the geometry only
     need_device(p);
     DeviceGuard device_guard(p->device);

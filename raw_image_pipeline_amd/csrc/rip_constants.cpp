@@ -363,6 +363,22 @@ void ensure_output_table(rip_pipeline* p, int head, int fmt) {
   t.dirty = false;
 }
 
+// The tables and the header blob of a head's JPEG streams (rip_jpeg.hpp), rebuilt and uploaded when the key -- quality, restart rows and
+// the picture's rows, cols and channels -- is not the one they were built for.
+void ensure_jpeg_constants(rip_pipeline* p, const Plan& pl) {
+  const int key[5] = {pl.jpeg_quality, pl.jpeg_restart_rows, pl.img_rows, pl.dl_pic_cols, pl.channels};
+  int* have = p->jpeg_key[pl.head];
+  if (std::memcmp(key, have, sizeof(key)) == 0 && p->d_jpeg_tables[pl.head].ptr) return;
+  rip::JpegTables tables;
+  uint8_t q[128], header[rip::kJpegHeaderColour];
+  rip::jpeg_build_tables(pl.jpeg_quality, tables, q);
+  const int n = rip::jpeg_build_header(pl.img_rows, pl.dl_pic_cols, pl.channels, pl.jpeg_restart_rows, q, header);
+  upload(p, p->d_jpeg_tables[pl.head], &tables, sizeof(tables));
+  upload(p, p->d_jpeg_header[pl.head], header, (size_t)n, rip::kJpegHeaderColour);
+  HIP_CHECK(hipStreamSynchronize(p->stream));
+  std::memcpy(have, key, sizeof(key));
+}
+
 // One table set of the resize stage is kept per output head, whichever filter built it: rebuilt by fill(host copy of `bytes` zeroed bytes)
 // and uploaded when the key -- (R, C, H, W, kind of table) -- is not the one it was built for.  The upload goes through the handle's
 // pageable copy and waits for the stream, like the other ensure_* functions: a handle that alternates between targets pays that

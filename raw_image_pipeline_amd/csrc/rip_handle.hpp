@@ -26,6 +26,7 @@
 #include "rip_area.hpp"
 #include "rip_fit.hpp"
 #include "rip_heads.hpp"
+#include "rip_jpeg.hpp"
 #include "rip_mask.hpp"
 #include "rip_resize.hpp"
 #include "rip_yuv.hpp"
@@ -165,8 +166,12 @@ struct Plan {
   bool clahe = false;
   int clahe_tx = 0, clahe_ty = 0;
   double clahe_clip = 0.0;
+  // the format "jpeg" (rip_set_output_jpeg; read under OUT_JPEG only): the delivered buffer is one row of dl_cols bytes, the default
+  // slot; the picture that is coded is img_rows x dl_pic_cols of `channels` channels
+  int jpeg_quality = 90, jpeg_restart_rows = 1;
+  int dl_pic_cols = 0;  // the width of the delivered picture F': dl_cols, except under "jpeg", whose dl_cols is the slot
   bool win_is_frame() const { return win_x == 0 && win_y == 0 && win_w == out_cols && win_h == out_rows; }
-  bool pic_is_delivered() const { return pic_w == dl_cols && pic_h == img_rows; }
+  bool pic_is_delivered() const { return pic_w == dl_pic_cols && pic_h == img_rows; }
 };
 
 // n frames of rows x cols pixels in device memory: rows `step` bytes apart, frames `frame_stride` bytes apart (both resolved,
@@ -390,6 +395,14 @@ struct rip_pipeline {
   rip::api::DevBuf d_fmt, d_rsz;
   // the tables of a head's CLAHE (rip_clahe.hpp), n frames x tiles x 256 bytes: written and read inside one call, nothing is kept
   rip::api::DevBuf d_clahe;
+  // the format "jpeg" (rip_jpeg.hpp).  Per call: the quantised coefficients of a batch slice, 2 bytes per coded sample, and one word
+  // per restart interval and frame -- no stream is staged, the kernels write into the caller's slots.  Per head: the tables and the
+  // header blob of the key (quality, restart rows, rows, cols, channels) they were built for, and the stream lengths of the head's
+  // last frame call (rip_get_output_jpeg_sizes): jpeg_frames[k] words, 0 after a frame call that delivered another format from head k.
+  rip::api::DevBuf d_jpeg_coef, d_jpeg_intervals;
+  rip::api::DevBuf d_jpeg_tables[rip::kMaxOutputHeads], d_jpeg_header[rip::kMaxOutputHeads], d_jpeg_sizes[rip::kMaxOutputHeads];
+  int jpeg_key[rip::kMaxOutputHeads][5] = {};
+  int jpeg_frames[rip::kMaxOutputHeads] = {};
   int last_chain_walked = 0;  // items per frame the last chain launch of run_batch walked (rip_debug_chain_footprint)
   bool use_tiled_remap = true;
   int last_batch_frames = 0;
@@ -497,6 +510,8 @@ void ensure_tables(rip_pipeline* p);
 void ensure_vignette(rip_pipeline* p, int rows, int cols);
 void ensure_ccc(rip_pipeline* p, int rows, int cols);
 void ensure_output_table(rip_pipeline* p, int head, int fmt);
+// the tables and the header of a head's JPEG streams for the plan's picture and settings (d_jpeg_tables, d_jpeg_header)
+void ensure_jpeg_constants(rip_pipeline* p, const Plan& pl);
 // The resize stage's tables of head `head` for an R x C window and an H x W picture, written into the table fields of the launch's
 // parameter block `r` -- device pointers into ResizeTableConst::dev and the flags that go with them; the other fields are left alone.
 void ensure_resize_tables(rip_pipeline* p, int head, int R, int C, int H, int W, rip::ResizeParams& r);
@@ -518,10 +533,17 @@ void restart_ccc_estimator(rip_pipeline* p);    // first frame, new Kalman filte
 // namespace -- what follows the chain: resize, pad, converter, heads and masks
 size_t fmt_pitch(const Plan& pl);
 void run_batch(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, bool reuse_wb = false);
-void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n);
+// first_frame (here and in run_batch_heads): the index of the slice's first frame inside the frame call
+void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, int first_frame = 0);
+// A frame call of n_frames frames begins, behind its last refusal: a head that delivers "jpeg" gets room for its stream lengths
+// (rip_get_output_jpeg_sizes), which the slices of the call fill from their first_frame on; any other head's count goes to 0.
+void begin_jpeg_call(rip_pipeline* p, const Plan& pl, int n_frames);
+// rip_apply / rip_apply_heads: waits for the stream, then copies the stream of a one-frame jpeg head from the device slot `d_slot`
+// to `out` -- the length first, then the used bytes only
+void download_jpeg_frame(rip_pipeline* p, const Plan& pl, const void* d_slot, uint8_t* out);
 // Several delivered images from one run of the chain (rip_apply_device_heads): plans[k] / dsts[k] for every head k < n_heads, with
 // dsts[k].ptr null for a head that is not requested (its plan is not looked at).  pl: make_plan's, the pipeline's own image.
-void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const FrameView* dsts, int n_heads, ConstFrameView src, Taps taps, int n);
+void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const FrameView* dsts, int n_heads, ConstFrameView src, Taps taps, int n, int first_frame = 0);
 // the heads calls' checks behind make_plan (rip.h rip_apply_device_heads, steps 5 to 7): fills plans[k] and views[k] of every
 // requested head (requested[k]; the others are neither planned nor validated); view_of(k, plan) resolves head k's buffer with its
 // own refusals.  The messages of step 5 are prefixed "output head <k>: " and keep their status.  Nothing is enqueued here.

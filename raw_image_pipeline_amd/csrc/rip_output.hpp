@@ -24,16 +24,19 @@ enum OutputFormat : int {
   // YUV 4:2:0 for encoders: converted by yuv420_kernel of librip_yuv_hip.so (rip_yuv.hpp), not by this library's converter
   OUT_NV12 = 9,
   OUT_I420 = 10,
-  OUT_FORMAT_COUNT = 11
+  // a baseline JPEG stream per frame: encoded by the kernels of librip_jpeg_hip.so (rip_jpeg.hpp), in the converter's place too
+  OUT_JPEG = 11,
+  OUT_FORMAT_COUNT = 12
 };
 inline bool output_format_yuv(int f) { return f == OUT_NV12 || f == OUT_I420; }
+inline bool output_format_jpeg(int f) { return f == OUT_JPEG; }
 inline bool output_format_planar(int f) { return f >= OUT_RGB_CHW_F32 && f <= OUT_BGR_CHW_BF16; }
 inline bool output_format_rgb_planes(int f) { return f >= OUT_RGB_CHW_F32 && f <= OUT_RGB_CHW_BF16; }
 // bytes per delivered element and delivered channels (planes) of a non-native format
 inline int output_format_elem_bytes(int f) {
   return (f == OUT_RGB_CHW_F32 || f == OUT_BGR_CHW_F32) ? 4 : (output_format_planar(f) ? 2 : 1);
 }
-inline int output_format_channels(int f) { return f == OUT_MONO8 || output_format_yuv(f) ? 1 : 3; }
+inline int output_format_channels(int f) { return f == OUT_MONO8 || output_format_yuv(f) || output_format_jpeg(f) ? 1 : 3; }
 
 // Geometry of the converter (rip_output.hip): every lane owns kOutPxPerLane consecutive pixels of one row, a workgroup of
 // kOutBlock lanes covers kOutPxPerBlock pixels of one row; grid = (ceil(cols / kOutPxPerBlock), min(rows, 65535), frames).

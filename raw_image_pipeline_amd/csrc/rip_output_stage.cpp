@@ -49,8 +49,8 @@ FrameView staging_view(const Plan& pl) { return {nullptr, fmt_pitch(pl), fmt_pit
 
 // F' in front of the converter (only under a resize and a format), not yet allocated: the converter's source alignment
 FrameView resized_view(const Plan& pl) {
-  const size_t pitch = pitch16((size_t)pl.dl_cols * pl.channels);
-  return {nullptr, pitch, pitch * (size_t)pl.img_rows, pl.img_rows, pl.dl_cols};
+  const size_t pitch = pitch16((size_t)pl.dl_pic_cols * pl.channels);
+  return {nullptr, pitch, pitch * (size_t)pl.img_rows, pl.img_rows, pl.dl_pic_cols};
 }
 
 // What one head's launches behind F need besides its plan, made ready before the first launch of the batch (the ensure_* functions
@@ -67,6 +67,12 @@ struct HeadPrep {
 size_t rsz_bytes(const Plan& pl, int n) {
   if (!pl.rsz_active || pl.out_fmt == rip::OUT_NATIVE) return 0;
   return resized_view(pl).frame_stride * (size_t)n;
+}
+
+// bytes of d_jpeg_coef / d_jpeg_intervals a head needs for n frames: 0 unless it delivers "jpeg"
+size_t jpeg_coef_scratch(const Plan& pl, int n) { return rip::output_format_jpeg(pl.out_fmt) ? rip::jpeg_coef_bytes(pl.img_rows, pl.dl_pic_cols, pl.channels, n) : 0; }
+size_t jpeg_interval_scratch(const Plan& pl, int n) {
+  return rip::output_format_jpeg(pl.out_fmt) ? rip::jpeg_interval_bytes(pl.img_rows, pl.channels, pl.jpeg_restart_rows, n) : 0;
 }
 
 // bytes of d_clahe a head needs for n frames: the tables of its CLAHE
@@ -88,6 +94,11 @@ HeadPrep prepare_head(rip_pipeline* p, const Plan& pl, const FrameView& staged, 
     }
   }
   p->d_clahe.reserve(clahe_bytes(pl, n));  // several heads: as d_rsz
+  if (rip::output_format_jpeg(pl.out_fmt)) {
+    ensure_jpeg_constants(p, pl);
+    p->d_jpeg_coef.reserve(jpeg_coef_scratch(pl, n));  // several heads: as d_rsz
+    p->d_jpeg_intervals.reserve(jpeg_interval_scratch(pl, n));
+  }
   return hp;
 }
 
@@ -102,7 +113,8 @@ void launched(bool accepted, const Info& info, const char* what, int n) {
 
 // The launches behind F for one head up to its delivered image: the resize, window resize, area or antialiased launch, then the pad,
 // then the converter, reading F in `staged` (16-byte aligned base, pitch and frame stride) and writing the head's delivered frames `dst`.
-void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const FrameView& staged, FrameView dst, int n) {
+// first_frame: the index, inside the frame call, of the slice's first frame -- where a jpeg head's stream lengths go.
+void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const FrameView& staged, FrameView dst, int n, int first_frame) {
   // F': the caller's buffer under "native", else the second staging image; the picture's rectangle of it is what the resize writes
   const FrameView whole_to = pl.out_fmt != rip::OUT_NATIVE ? hp.converted_from : dst;
   FrameView to = whole_to;
@@ -126,7 +138,7 @@ void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, con
     rip::FitPadParams f = {};
     bind_dst(f, whole_to);
     f.rows = pl.img_rows;
-    f.cols = pl.dl_cols;
+    f.cols = pl.dl_pic_cols;
     f.pic_x = pl.pic_x;
     f.pic_y = pl.pic_y;
     f.pic_w = pl.pic_w;
@@ -137,6 +149,32 @@ void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, con
     launched(rip::launch_fit_pad(f, p->stream, &info), info, "the letterbox pad", n);
   }
   if (pl.out_fmt == rip::OUT_NATIVE) return;
+  if (rip::output_format_jpeg(pl.out_fmt)) {  // librip_jpeg_hip.so's four kernels in the converter's place, from the same source
+    rip::JpegParams c = {};
+    bind_src(c, hp.converted_from);
+    bind_dst(c, dst);  // dst.step: the capacity of a slot
+    c.rows = pl.img_rows;
+    c.cols = pl.dl_pic_cols;
+    c.channels = pl.channels;
+    c.n_frames = n;
+    c.restart_rows = pl.jpeg_restart_rows;
+    int coef[9];
+    rip::output_yuv_matrix(rip::output_yuv_matrix_id("bt601_full"), coef, &c.m.yoff);  // JFIF: full-range BT.601, whatever the head's matrix
+    for (int i = 0; i < 3; i++) c.m.y[i] = coef[i], c.m.cb[i] = coef[3 + i], c.m.cr[i] = coef[6 + i];
+    c.tables = p->d_jpeg_tables[pl.head].as<rip::JpegTables>();
+    c.header = p->d_jpeg_header[pl.head].as<uint8_t>();
+    c.coef = p->d_jpeg_coef.as<int16_t>();
+    c.intervals = p->d_jpeg_intervals.as<uint32_t>();
+    if (p->jpeg_frames[pl.head] < first_frame + n || p->d_jpeg_sizes[pl.head].cap < (size_t)(first_frame + n) * 4)
+      throw DeviceError("internal: the jpeg sizes of the frame call were not reserved");
+    c.sizes = p->d_jpeg_sizes[pl.head].as<uint32_t>() + first_frame;
+    rip::JpegLaunchInfo jpeg_info = {};
+    launched(rip::launch_jpeg_transform(c, p->stream, &jpeg_info), jpeg_info, "the JPEG transform", n);
+    launched(rip::launch_jpeg_size(c, p->stream, &jpeg_info), jpeg_info, "the JPEG sizing pass", n);
+    launched(rip::launch_jpeg_scan(c, p->stream, &jpeg_info), jpeg_info, "the JPEG scan", n);
+    launched(rip::launch_jpeg_write(c, p->stream, &jpeg_info), jpeg_info, "the JPEG writing pass", n);
+    return;
+  }
   if (rip::output_format_yuv(pl.out_fmt)) {  // librip_yuv_hip.so's kernel in the converter's place, from the same source
     rip::Yuv420Params c = {};
     bind_src(c, hp.converted_from);
@@ -167,9 +205,9 @@ void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, con
 // Every launch of one head: its delivered image, then CLAHE on the picture's rectangle of it (PARITY.md "Local contrast: CLAHE") -- in
 // place in the delivered buffer, or, where nothing else is launched, from the staging image into the delivered buffer.  The tables
 // in d_clahe are written by the first launch and read by the second.
-void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const FrameView& staged, FrameView dst, int n) {
+void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const FrameView& staged, FrameView dst, int n, int first_frame) {
   LaunchLogScope log_scope(p);
-  enqueue_head_image(p, pl, hp, staged, dst, n);
+  enqueue_head_image(p, pl, hp, staged, dst, n, first_frame);
   if (!pl.clahe) return;
   const bool from_staging = pl.out_fmt == rip::OUT_NATIVE && !pl.rsz_active;
   rip::ClaheParams c = {};
@@ -210,7 +248,7 @@ MaskBaseConst::Key mask_base_key(const rip_pipeline* p, bool remap, int src_rows
 // into the caller's buffer under "native", else into a second staging image; under a letterbox it writes the picture's rectangle of
 // F' and one launch of the pad kernel fills the rest -- and one launch of the converter (librip_out_hip.so) writes the caller's buffer from F' (or from F without a target).  Neither: this is run_batch.
 // dst: the DELIVERED frames.
-void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n) {
+void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, FrameView dst, Taps taps, int n, int first_frame) {
   p->head_record[pl.head] = {identity_head(pl) ? 1 : 0, 0};
   if (identity_head(pl)) {
     run_batch(p, pl, src, dst, taps, n);
@@ -222,7 +260,7 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
   staged.ptr = p->d_fmt.as<uint8_t>();
   const HeadPrep hp = prepare_head(p, pl, staged, n);
   run_batch(p, pl, src, staged, taps, n);
-  enqueue_head(p, pl, hp, staged, dst, n);
+  enqueue_head(p, pl, hp, staged, dst, n, first_frame);
 }
 
 // Several heads from one run of the chain (rip_apply_device_heads; PARITY.md "Output heads").  One requested head: the function above.
@@ -231,12 +269,12 @@ void run_batch_formatted(rip_pipeline* p, const Plan& pl, ConstFrameView src, Fr
 // 16-byte block or a dword that holds a byte of a row's end lies inside that byte's page, whatever follows the caller's buffer), else into d_fmt -- and
 // every other requested head follows in index order on the handle's stream: one head_copy_kernel launch for an identity head,
 // enqueue_head's launches for the others.  d_rsz is shared by the heads, which run one after another: reserved for the largest.
-void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const FrameView* dsts, int n_heads, ConstFrameView src, Taps taps, int n) {
+void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const FrameView* dsts, int n_heads, ConstFrameView src, Taps taps, int n, int first_frame) {
   int n_requested = 0, only = -1;
   for (int k = 0; k < n_heads; k++)
     if (dsts[k].ptr) n_requested++, only = k;
   if (n_requested == 1) {
-    run_batch_formatted(p, plans[only], src, dsts[only], taps, n);
+    run_batch_formatted(p, plans[only], src, dsts[only], taps, n, first_frame);
     return;
   }
   DeviceGuard device_guard(p->device);
@@ -258,6 +296,11 @@ void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const F
   for (int k = 0; k < n_heads; k++)
     if (dsts[k].ptr) clahe = std::max(clahe, clahe_bytes(plans[k], n));
   p->d_clahe.reserve(clahe);
+  size_t jpeg_coef = 0, jpeg_intervals = 0;
+  for (int k = 0; k < n_heads; k++)
+    if (dsts[k].ptr) jpeg_coef = std::max(jpeg_coef, jpeg_coef_scratch(plans[k], n)), jpeg_intervals = std::max(jpeg_intervals, jpeg_interval_scratch(plans[k], n));
+  p->d_jpeg_coef.reserve(jpeg_coef);
+  p->d_jpeg_intervals.reserve(jpeg_intervals);
   HeadPrep hp[rip::kMaxOutputHeads];
   for (int k = 0; k < n_heads; k++)
     if (dsts[k].ptr && !identity_head(plans[k])) hp[k] = prepare_head(p, plans[k], staged, n);
@@ -267,7 +310,7 @@ void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const F
     p->head_record[k] = {k == direct ? 1 : 0, 0};
     if (k == direct) continue;
     if (!identity_head(plans[k])) {
-      enqueue_head(p, plans[k], hp[k], staged, dsts[k], n);
+      enqueue_head(p, plans[k], hp[k], staged, dsts[k], n, first_frame);
       continue;
     }
     LaunchLogScope log_scope(p);
@@ -281,6 +324,23 @@ void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const F
     launched(rip::launch_head_copy(c, p->stream, &info), info, "the head copy", n);
     p->head_record[k].copied = 1;
   }
+}
+
+// ---- the format "jpeg": what surrounds the launches (PARITY.md "Output formats: JPEG") ------------------------------------------
+
+void begin_jpeg_call(rip_pipeline* p, const Plan& pl, int n_frames) {
+  p->jpeg_frames[pl.head] = 0;  // the lengths of an earlier call are not this call's
+  if (!rip::output_format_jpeg(pl.out_fmt)) return;
+  DeviceGuard device_guard(p->device);
+  p->d_jpeg_sizes[pl.head].reserve((size_t)n_frames * 4);
+  p->jpeg_frames[pl.head] = n_frames;
+}
+
+void download_jpeg_frame(rip_pipeline* p, const Plan& pl, const void* d_slot, uint8_t* out) {
+  uint32_t size = 0;
+  HIP_CHECK(hipMemcpyAsync(&size, p->d_jpeg_sizes[pl.head].ptr, 4, hipMemcpyDeviceToHost, p->stream));
+  HIP_CHECK(hipStreamSynchronize(p->stream));
+  if (size) HIP_CHECK(hipMemcpyAsync(out, d_slot, size, hipMemcpyDeviceToHost, p->stream));
 }
 
 // ---- valid-pixel masks (rip_set_rect_mask; PARITY.md "Rect mask") -------------------------------------------------------------
@@ -338,6 +398,7 @@ ConstFrameView ensure_mask_head(rip_pipeline* p, const Plan& frame_pl, int mode)
   pl.clahe = false;  // a mask is coverage, not a picture
   pl.out_fmt = rip::OUT_NATIVE;
   pl.dl_rows = pl.img_rows;  // a mask ignores the format: the picture's rows under a YUV format too
+  pl.dl_cols = pl.dl_pic_cols;  // ... and the picture's width under "jpeg", whose delivered row is a slot
   for (uint8_t& c : pl.pad) c = 0;
   const bool identity = identity_head(pl), binary = mode == 2;
   MaskHeadConst& mh = p->mask_head[pl.head];
@@ -355,7 +416,7 @@ ConstFrameView ensure_mask_head(rip_pipeline* p, const Plan& frame_pl, int mode)
     } else {
       const FrameView staged = {const_cast<uint8_t*>(base.ptr), base.step, base.frame_stride, base.rows, base.cols};  // read only
       const HeadPrep hp = prepare_head(p, pl, staged, 1);
-      enqueue_head(p, pl, hp, staged, dst, 1);
+      enqueue_head(p, pl, hp, staged, dst, 1, 0);
       if (binary) {
         LaunchLogScope log_scope(p);
         rip::MaskThresholdParams t = {dst.ptr, dst.step, dst.rows, dst.cols};

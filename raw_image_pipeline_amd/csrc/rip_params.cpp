@@ -94,7 +94,13 @@ OutputHead output_head_from_node(const YamlNode& o, const std::string& sec) {
     clahe_tiles[1] = (int)v[1];
   }
   check_output_clahe(clahe_clip_limit, clahe_tiles[0], clahe_tiles[1]);
+  // extension keys output: jpeg_quality: 90 / jpeg_restart_rows: 1 (rip_set_output_jpeg); absent keys mean the defaults
+  const double jpeg_quality = o.get("jpeg_quality", 90.0), jpeg_restart_rows = o.get("jpeg_restart_rows", 1.0);
+  if (jpeg_quality != std::floor(jpeg_quality) || jpeg_restart_rows != std::floor(jpeg_restart_rows) || !(std::fabs(jpeg_quality) < 1e6) || !(std::fabs(jpeg_restart_rows) < 1e6))
+    throw std::invalid_argument(sec + ": jpeg_quality: an integer in 1..100 and jpeg_restart_rows: an integer in 1..64 are expected");
+  check_output_jpeg((int)jpeg_quality, (int)jpeg_restart_rows);
   OutputHead h;
+  h.jpeg_quality = (int)jpeg_quality, h.jpeg_restart_rows = (int)jpeg_restart_rows;
   h.clahe_clip_limit = clahe_clip_limit;
   h.clahe_tiles_x = clahe_tiles[0], h.clahe_tiles_y = clahe_tiles[1];
   h.roi_x = roi[0], h.roi_y = roi[1], h.roi_w = roi[2], h.roi_h = roi[3];
@@ -239,15 +245,15 @@ void check_debayer_method(const std::string& method) {
 }
 
 namespace {
-const char* const kOutputFormatNames[11] = {"native", "rgb8", "mono8", "rgb_chw_f32", "rgb_chw_f16", "rgb_chw_bf16",
-                                            "bgr_chw_f32", "bgr_chw_f16", "bgr_chw_bf16", "nv12", "i420"};  // index = rip_output.hpp OutputFormat
+const char* const kOutputFormatNames[12] = {"native", "rgb8", "mono8", "rgb_chw_f32", "rgb_chw_f16", "rgb_chw_bf16",
+                                            "bgr_chw_f32", "bgr_chw_f16", "bgr_chw_bf16", "nv12", "i420", "jpeg"};  // index = rip_output.hpp OutputFormat
 // index = the id output_yuv_matrix_id returns; the rows are rip_yuv.hpp's YuvMatrix (PARITY.md "Output formats: YUV 4:2:0")
 const char* const kYuvMatrixNames[4] = {"bt601", "bt709", "bt601_full", "bt709_full"};
 }  // namespace
 
 int output_format_id(const std::string& name) {
   std::string names;
-  for (int i = 0; i < 11; i++) {
+  for (int i = 0; i < 12; i++) {
     if (name == kOutputFormatNames[i]) return i;
     names += std::string(i ? ", '" : "'") + kOutputFormatNames[i] + "'";
   }
@@ -296,6 +302,12 @@ void check_output_clahe(double clip_limit, int tiles_x, int tiles_y) {
   const bool off = tiles_x == 0 && tiles_y == 0;
   if (!off && (tiles_x < 1 || tiles_x > 16 || tiles_y < 1 || tiles_y > 16))
     throw std::invalid_argument("output clahe: tiles (" + std::to_string(tiles_x) + ", " + std::to_string(tiles_y) + ") not supported: both in 1..16, or (0, 0) for off");
+}
+
+void check_output_jpeg(int quality, int restart_rows) {
+  if (quality < 1 || quality > 100 || restart_rows < 1 || restart_rows > 64)
+    throw std::invalid_argument("output jpeg (quality " + std::to_string(quality) + ", restart rows " + std::to_string(restart_rows) +
+                                ") not supported: the quality is in 1..100 and the MCU rows per restart interval are in 1..64");
 }
 
 int output_interpolation_id(const std::string& name) {

@@ -34,6 +34,9 @@ struct OutputHead {
   // launch of the head; tiles (0, 0) = off
   double clahe_clip_limit = 0.0;
   int clahe_tiles_x = 0, clahe_tiles_y = 0;
+  // extension (rip_set_output_jpeg; PARITY.md "Output formats: JPEG"): the quality (1..100, the IJG scaling of the Annex K tables) and
+  // the MCU rows per restart interval (1..64) of the format "jpeg"; without effect under any other format
+  int jpeg_quality = 90, jpeg_restart_rows = 1;
 };
 
 struct Modules {
@@ -120,6 +123,8 @@ int output_fit_id(const std::string& name);
 void check_output_pad(int b, int g, int r);
 // the settings rip_set_output_clahe accepts: a finite clip limit >= 0 and tiles both in 1 .. 16 or both 0; throws std::invalid_argument
 void check_output_clahe(double clip_limit, int tiles_x, int tiles_y);
+// the settings rip_set_output_jpeg accepts: a quality in 1 .. 100 and 1 .. 64 MCU rows per restart interval; throws std::invalid_argument
+void check_output_jpeg(int quality, int restart_rows);
 bool load_camera_calibration_file(Modules& m, const std::string& path); // undistortion.cpp:157-195
 bool load_color_calibration_file(Modules& m, const std::string& path);  // color_calibration.cpp:52-76
 void apply_example_camera_calibration(Modules& m);  // values of config/alphasense_calib_example.yaml

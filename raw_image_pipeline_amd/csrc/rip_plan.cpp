@@ -154,7 +154,7 @@ void apply_format_and_size(const rip::Modules& mods, int head, Plan& pl) {
   pl.dl_elem_bytes = pl.out_elem_bytes;
   // the resize stage (rip_set_output_size) sits between F and the format: the delivered geometry is the target's
   pl.img_rows = pl.out_rows;
-  pl.dl_cols = pl.out_cols;
+  pl.dl_cols = pl.dl_pic_cols = pl.out_cols;
   pl.win_w = pl.pic_w = pl.out_cols;
   pl.win_h = pl.pic_h = pl.out_rows;
   const int fit = rip::output_fit_id(m.out_fit);
@@ -169,7 +169,7 @@ void apply_format_and_size(const rip::Modules& mods, int head, Plan& pl) {
     rip::output_window_geometry(pl.out_cols, pl.out_rows, roi, m.out_w, m.out_h, fit, src, dst);
     pl.win_x = src[0], pl.win_y = src[1], pl.win_w = src[2], pl.win_h = src[3];
     pl.pic_x = dst[0], pl.pic_y = dst[1], pl.pic_w = dst[2], pl.pic_h = dst[3];
-    pl.dl_cols = m.out_w > 0 ? m.out_w : pl.win_w;
+    pl.dl_cols = pl.dl_pic_cols = m.out_w > 0 ? m.out_w : pl.win_w;
     pl.img_rows = m.out_w > 0 ? m.out_h : pl.win_h;
     if (pl.channels == 1) pl.pad[0] = (uint8_t)rip::output_pad_grey(m.out_pad[0], m.out_pad[1], m.out_pad[2]);
     else for (int i = 0; i < 3; i++) pl.pad[i] = (uint8_t)m.out_pad[i];
@@ -215,11 +215,35 @@ void apply_format_and_size(const rip::Modules& mods, int head, Plan& pl) {
     }
   }
   pl.dl_rows = pl.img_rows;
+  pl.dl_pic_cols = pl.dl_cols;
   const int fmt = rip::output_format_id(m.out_format);
   if (fmt == rip::OUT_NATIVE) return;
   pl.fmt_active = true;
   if (pl.out_elem_bytes != 1)
     throw InvalidArgument("output format [" + m.out_format + "] needs an 8-bit pipeline result; this frame gives bgr16 (set a 16-bit range, or the format 'native')");
+  if (rip::output_format_jpeg(fmt)) {
+    // One slot per frame: a one-channel row of the default slot's bytes; img_rows x dl_pic_cols stays the picture that is coded, one
+    // component from a one-channel result, Y Cb Cr 4:2:0 from B, G, R (PARITY.md "Output formats: JPEG").  The refusals: CLAHE on the
+    // head, then what the stream's 16-bit fields cannot hold.
+    if (m.clahe_tiles_x != 0)
+      throw InvalidArgument("output format [jpeg] does not take CLAHE on the same head (set the clahe tiles (0, 0), or another format)");
+    if (pl.dl_cols > 65535 || pl.img_rows > 65535)
+      throw InvalidArgument("output format [jpeg]: a delivered picture of " + std::to_string(pl.dl_cols) + " x " + std::to_string(pl.img_rows) + " is beyond the 65535 pixels per side a JPEG frame header holds");
+    if ((long long)m.jpeg_restart_rows * rip::jpeg_mcus_x(pl.dl_cols, pl.channels) > 65535)
+      throw InvalidArgument("output format [jpeg]: " + std::to_string(m.jpeg_restart_rows) + " MCU rows of " + std::to_string(rip::jpeg_mcus_x(pl.dl_cols, pl.channels)) +
+                            " MCUs are beyond the 65535 MCUs a restart interval holds (set fewer restart rows)");
+    pl.jpeg_quality = m.jpeg_quality;
+    pl.jpeg_restart_rows = m.jpeg_restart_rows;
+    pl.out_fmt = fmt;
+    pl.dl_channels = 1;
+    pl.dl_elem_bytes = 1;
+    pl.dl_rows = 1;
+    const size_t slot = rip::jpeg_default_slot(pl.img_rows, pl.dl_pic_cols, pl.channels, m.jpeg_restart_rows);
+    if (slot > 0x7FFFFFFFull) throw InvalidArgument("output format [jpeg]: the default slot of " + std::to_string(slot) + " bytes is beyond 2 GiB");
+    pl.dl_cols = (int)slot;
+    pl.encoding_out = m.out_format;
+    return;
+  }
   if (pl.channels == 1) {
     if (fmt != rip::OUT_MONO8)
       throw InvalidArgument("output format [" + m.out_format + "] needs a three-channel pipeline result; this frame gives one channel ('mono8' and 'native' apply)");
@@ -248,7 +272,7 @@ void apply_format_and_size(const rip::Modules& mods, int head, Plan& pl) {
 void apply_output_format(const rip::Modules& mods, int head, Plan& pl) {
   apply_format_and_size(mods, head, pl);
   const rip::OutputHead& m = mods.heads[head];
-  if (m.clahe_tiles_x == 0) return;
+  if (m.clahe_tiles_x == 0 || rip::output_format_jpeg(pl.out_fmt)) return;
   if (pl.dl_channels != 1 || pl.dl_elem_bytes != 1 || rip::output_format_yuv(pl.out_fmt))
     throw InvalidArgument("output clahe needs a delivered one-channel 8-bit picture; this head delivers [" + pl.encoding_out + "] (set the output format 'mono8', or the clahe tiles (0, 0))");
   if (pl.pic_w < 2 * m.clahe_tiles_x || pl.pic_h < 2 * m.clahe_tiles_y)
@@ -272,6 +296,16 @@ FrameView tight_output_view(const Plan& pl, void* d_out) {
 // overlap, are refused instead of writing somewhere else.
 FrameView resolve_output_layout(const Plan& pl, void* d_out, size_t out_step, size_t out_frame_stride) {
   FrameView v = tight_output_view(pl, d_out);
+  if (rip::output_format_jpeg(pl.out_fmt)) {
+    // a row pitch is the capacity of a slot: any the header and EOI fit in; the streams are written at any alignment
+    const size_t least = (size_t)rip::jpeg_header_bytes(pl.channels) + 2;
+    if (out_step) v.step = out_step;
+    if (v.step < least) throw InvalidArgument("output format [jpeg]: a slot of " + std::to_string(v.step) + " bytes is smaller than the header and EOI (" + std::to_string(least) + " bytes)");
+    if (v.step > 0xFFFFFFFFull) throw InvalidArgument("output format [jpeg]: a slot must stay below 4 GiB");
+    v.frame_stride = out_frame_stride ? out_frame_stride : v.step;
+    if (v.frame_stride < v.step) throw InvalidArgument("output frame stride smaller than a frame");
+    return v;
+  }
   const size_t e = (size_t)pl.dl_elem_bytes, row = v.step;
   if (out_step) v.step = out_step;
   if (v.step < row) throw InvalidArgument("output row pitch smaller than a row");

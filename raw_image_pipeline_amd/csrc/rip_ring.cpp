@@ -220,6 +220,8 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     need_device(p);
     if (!image || !encoding || !ticket) throw InvalidArgument("null buffer, encoding or ticket");
     const Plan pl = delivered_plan(p, rows, cols, channels, encoding);  // a null encoding was refused above
+    if (rip::output_format_jpeg(pl.out_fmt))
+      throw InvalidArgument("rip_submit: the output format [jpeg] delivers streams of a length the ring does not carry; use rip_apply, rip_apply_heads or the device calls");
     const HostFrameLayout L(p, pl, rows, cols, channels, step);
     {  // destinations given by the caller (rip_submit_to): checked before anything is enqueued or any slot is touched
       if (ext_out && ext_out_capacity < L.out_bytes) throw CapacityError("rip_submit_to: result buffer too small: need " + std::to_string(L.out_bytes) + " bytes");
@@ -298,6 +300,7 @@ rip_status submit_impl(rip_pipeline* p, const uint8_t* image, int rows, int cols
     }
     HIP_CHECK(hipEventRecord(sl.ev_up, p->ul_stream));
     HIP_CHECK(hipStreamWaitEvent(p->stream, sl.ev_up, 0));
+    begin_jpeg_call(p, pl, 1);  // no jpeg head gets here: the head's stream lengths of an earlier call end
     run_batch_formatted(p, pl, L.staged(sl.d_in.ptr, rows, cols), HostFrameLayout::delivered(pl, sl.d_out.ptr),
                         {sl.has_deb ? sl.d_tap_deb.as<uint8_t>() : nullptr, sl.has_col ? sl.d_tap_col.as<uint8_t>() : nullptr}, 1);
     HIP_CHECK(hipEventRecord(sl.ev_kernels, p->stream));
@@ -346,8 +349,10 @@ rip_status rip_apply(rip_pipeline* p, const uint8_t* image, int rows, int cols, 
     const Taps taps = {L.keep_deb ? p->d_tap_deb.as<uint8_t>() : nullptr, L.keep_col ? p->d_tap_col.as<uint8_t>() : nullptr};
     const ConstFrameView src = L.staged(p->d_in.ptr, rows, cols);
     HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, L.in_pitch, image, L.step, L.in_row, (size_t)rows, hipMemcpyHostToDevice, p->stream));
+    begin_jpeg_call(p, pl, 1);
     run_batch_formatted(p, pl, src, HostFrameLayout::delivered(pl, p->d_out.ptr), taps, 1);
-    HIP_CHECK(hipMemcpyAsync(out, p->d_out.ptr, L.out_bytes, hipMemcpyDeviceToHost, p->stream));
+    if (rip::output_format_jpeg(pl.out_fmt)) download_jpeg_frame(p, pl, p->d_out.ptr, out);  // the length first, then the used bytes
+    else HIP_CHECK(hipMemcpyAsync(out, p->d_out.ptr, L.out_bytes, hipMemcpyDeviceToHost, p->stream));
     HIP_CHECK(hipStreamSynchronize(p->stream));
     const bool eb1 = pl.out_elem_bytes == 1;
     if (p->m.debug && eb1) {
@@ -411,9 +416,14 @@ rip_status rip_apply_heads(rip_pipeline* p, const uint8_t* image, int rows, int 
     const Taps taps = {L.keep_deb ? p->d_tap_deb.as<uint8_t>() : nullptr, L.keep_col ? p->d_tap_col.as<uint8_t>() : nullptr};
     const ConstFrameView src = L.staged(p->d_in.ptr, rows, cols);
     HIP_CHECK(hipMemcpy2DAsync(p->d_in.ptr, L.in_pitch, image, L.step, L.in_row, (size_t)rows, hipMemcpyHostToDevice, p->stream));
-    run_batch_heads(p, pl, plans, dsts, n_heads, src, taps, 1);
     for (int k = 0; k < n_heads; k++)
-      if (requested[k]) HIP_CHECK(hipMemcpyAsync(outs[k], p->d_head_out[k].ptr, delivered_bytes(plans[k]), hipMemcpyDeviceToHost, p->stream));
+      if (requested[k]) begin_jpeg_call(p, plans[k], 1);
+    run_batch_heads(p, pl, plans, dsts, n_heads, src, taps, 1);
+    for (int k = 0; k < n_heads; k++) {
+      if (!requested[k]) continue;
+      if (rip::output_format_jpeg(plans[k].out_fmt)) download_jpeg_frame(p, plans[k], p->d_head_out[k].ptr, outs[k]);
+      else HIP_CHECK(hipMemcpyAsync(outs[k], p->d_head_out[k].ptr, delivered_bytes(plans[k]), hipMemcpyDeviceToHost, p->stream));
+    }
     HIP_CHECK(hipStreamSynchronize(p->stream));
     for (int i = 0; i < 3; i++) p->last_valid[i] = false;
     remember_last(p, RIP_IMAGE_DEBAYERED, &p->d_tap_deb, nullptr, pl.mid_rows, pl.mid_cols, pl.channels, L.keep_deb);

@@ -40,6 +40,7 @@ rip_status rip_set_output_heads(rip_pipeline* p, int n) {
     for (int k = n; k < RIP_MAX_OUTPUT_HEADS; k++) {
       p->m.heads[k] = rip::OutputHead();
       p->head_record[k] = {};
+      p->jpeg_frames[k] = 0;
       invalidate_head(p, k, true);
     }
     p->m.n_heads = n;
@@ -304,6 +305,15 @@ rip_status rip_set_output_clahe(rip_pipeline* p, double clip_limit, int tiles_x,
     p->m.out().clahe_clip_limit = clip_limit;
     p->m.out().clahe_tiles_x = tiles_x;
     p->m.out().clahe_tiles_y = tiles_y;
+  });
+}
+rip_status rip_set_output_jpeg(rip_pipeline* p, int quality, int restart_rows) {
+  return guarded(p, [&] {
+    need(p);
+    invalidate_head(p, p->m.selected, false);
+    rip::check_output_jpeg(quality, restart_rows);
+    p->m.out().jpeg_quality = quality;
+    p->m.out().jpeg_restart_rows = restart_rows;
   });
 }
 rip_status rip_set_flip(rip_pipeline* p, int v) {
@@ -623,6 +633,13 @@ rip_status rip_get_output_pad(const rip_pipeline* p, int* b, int* g, int* r) {
   });
 }
 
+rip_status rip_get_output_jpeg(const rip_pipeline* p, int* quality, int* restart_rows) {
+  return guarded(p, [&] {
+    need(p);
+    if (quality) *quality = p->m.out().jpeg_quality;
+    if (restart_rows) *restart_rows = p->m.out().jpeg_restart_rows;
+  });
+}
 rip_status rip_get_output_clahe(const rip_pipeline* p, double* clip_limit, int* tiles_x, int* tiles_y) {
   return guarded(p, [&] {
     need(p);
@@ -670,7 +687,7 @@ rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int c
       pr[7] *= b;
     } else if (pl.rsz_active) {
       // the inverse of the tables' pixel-centre mapping u = (u' + 0.5) / a - 0.5 (PARITY.md "Resize")
-      const double a = (double)pl.dl_cols / pl.out_cols, b = (double)pl.img_rows / pl.out_rows;
+      const double a = (double)pl.dl_pic_cols / pl.out_cols, b = (double)pl.img_rows / pl.out_rows;
       k[0] *= a;
       k[1] *= a;
       k[2] = a * (k[2] + 0.5) - 0.5;
@@ -685,7 +702,7 @@ rip_status rip_get_output_camera_info(rip_pipeline* p, int rows, int cols, int c
       pr[7] *= b;
     }
     if (height) *height = pl.img_rows;  // the picture, not the buffer a YUV format delivers it in
-    if (width) *width = pl.dl_cols;
+    if (width) *width = pl.dl_pic_cols;
     if (K) std::memcpy(K, k, sizeof(k));
     if (P) std::memcpy(P, pr, sizeof(pr));
   });

@@ -49,6 +49,9 @@ OUTPUT_FORMATS = {
 # and the seeded draws of the suite's fuzzes are taken over OUTPUT_FORMATS as it stands.
 YUV_OUTPUT_FORMATS = {"nv12": (np.uint8, False, 1), "i420": (np.uint8, False, 1)}
 YUV_MATRICES = ("bt601", "bt709", "bt601_full", "bt709_full")
+# The format "jpeg" (set_output_jpeg), a row of the same shape in a table of its own for the same reason: one channel, one row of
+# `slot` bytes per frame, of which the first jpeg_sizes()[f] are frame f's stream (jpeg_streams cuts them out).
+JPEG_OUTPUT_FORMATS = {"jpeg": (np.uint8, False, 1)}
 
 
 def yuv_planes(frame, fmt):
@@ -68,6 +71,16 @@ def yuv_planes(frame, fmt):
     lead = tuple(frame.shape[:-2])
     planes = c.reshape(lead + (2, h // 2, w // 2))  # h / 2 rows of w bytes are h / 2 rows of w / 2 bytes twice
     return y, planes[..., 0, :, :], planes[..., 1, :, :]
+
+
+def jpeg_streams(slots, sizes):
+    """The streams of delivered "jpeg" frames as a list of ``bytes``: ``slots`` is the [n, slot] uint8 array or tensor ``apply_device``
+    returned (any row stride), ``sizes`` the n lengths of ``jpeg_sizes()``.  A frame whose stream did not fit its slot has size 0 and
+    gives ``b""``."""
+    if len(sizes) != slots.shape[0]:
+        raise ValueError("jpeg_streams: %d sizes for %d slots" % (len(sizes), slots.shape[0]))
+    host = slots.cpu().numpy() if hasattr(slots, "cpu") else np.asarray(slots)
+    return [host[f, :int(s)].tobytes() for f, s in enumerate(sizes)]
 
 
 def _delivered(rows, cols, channels, encoding):
@@ -361,6 +374,8 @@ class RawImagePipeline:
                    C.byref(k), enc)
         self.last_encoding = enc.value.decode()
         shape, _ = _delivered(r.value, c.value, k.value, self.last_encoding)
+        if self.last_encoding == "jpeg":  # one slot: the stream is its first jpeg_sizes()[0] bytes, the only ones downloaded
+            return out.reshape(-1)[:int(self.jpeg_sizes()[0])]
         return out if out.shape == shape else out.reshape(shape)
 
     def apply(self, image, encoding, width=None):
@@ -502,6 +517,13 @@ class RawImagePipeline:
                     raise ValueError("out: the elements of a row must be contiguous and the planes of a frame `rows` row pitches apart")
                 out_step = out.stride(2 if planar else 1) * elem
                 out_frame = out.stride(0) * elem if n > 1 else 0
+        elif enc == "jpeg":  # one slot per frame: [n, slot]; a given tensor's width is the slot the caller chose, its row stride the frame stride
+            if out is None:
+                out = torch.empty((n, ocols), dtype=torch.uint8, device=frames.device)
+            elif out.dim() != 2 or out.shape[0] != n or out.dtype != torch.uint8 or out.stride(1) != 1:
+                raise ValueError("out must be a uint8 tensor [%d, slot] with contiguous rows" % n)
+            out_step = out.shape[1]
+            out_frame = out.stride(0) if n > 1 else 0
         else:
             shape = (n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn * (2 if enc.endswith("16") else 1))
             if out is None:
@@ -609,7 +631,14 @@ class RawImagePipeline:
                 planar, tdtype = False, torch.uint8
                 shape = (n, orows, ocols) if ocn == 1 else (n, orows, ocols, ocn * (2 if enc.endswith("16") else 1))
             out_step = out_frame = 0
-            if out is None:
+            if enc == "jpeg":  # apply_device's rule: [n, slot], a given tensor's width is its slot
+                if out is None:
+                    out = torch.empty((n, ocols), dtype=torch.uint8, device=frames.device)
+                elif out.dim() != 2 or out.shape[0] != n or out.dtype != torch.uint8 or out.stride(1) != 1 or out.device != frames.device:
+                    raise ValueError("outs[%d] must be a uint8 tensor [%d, slot] with contiguous rows on the device of frames" % (k, n))
+                out_step = out.shape[1]
+                out_frame = out.stride(0) if n > 1 else 0
+            elif out is None:
                 out = torch.empty(shape, dtype=tdtype, device=frames.device)
             elif tuple(out.shape) != shape or out.dtype != tdtype or out.device != frames.device:
                 raise ValueError("outs[%d] must be a %s tensor of shape %s on the device of frames" % (k, tdtype, shape))
@@ -674,6 +703,8 @@ class RawImagePipeline:
                    ptrs, caps, int(n_heads), r, c, ch)
         for k in wanted:
             assert (r[k], c[k], ch[k]) == info[k][:3]
+            if info[k][3] == "jpeg":  # the stream: the first jpeg_sizes()[0] bytes of the slot, the only ones downloaded
+                result[k] = result[k].reshape(-1)[:int(self.jpeg_sizes(head=k)[0])]
         return result
 
     def set_taps(self, mask):
@@ -944,6 +975,36 @@ class RawImagePipeline:
         of the selected output head (a mono camera, or the format "mono8"); the last launch of the head, letterbox bands stay as they
         are.  clip_limit >= 0 (0: no clipping), tiles both in 1..16 or (0, 0) for off.  include/rip.h rip_set_output_clahe."""
         self._call("rip_set_output_clahe", C.c_double(clip_limit), int(tiles_x), int(tiles_y))
+
+    def set_output_jpeg(self, quality=90, restart_rows=1):
+        """Extension: the quality (1..100, the IJG scaling of the Annex K tables) and the MCU rows per restart interval (1..64) of the
+        output format "jpeg" of the selected output head; without effect under any other format.  include/rip.h rip_set_output_jpeg."""
+        self._call("rip_set_output_jpeg", int(quality), int(restart_rows))
+
+    def get_output_jpeg(self):
+        """(quality, restart_rows) of the selected output head."""
+        q, r = C.c_int(), C.c_int()
+        self._call("rip_get_output_jpeg", C.byref(q), C.byref(r))
+        return q.value, r.value
+
+    def jpeg_sizes(self, head=None):
+        """The stream lengths (numpy uint32 [n]) of the frames of the last frame call of the selected output head (or ``head``): empty
+        when that call delivered another format; an entry 0: the stream did not fit its slot, which was left untouched.  Waits for
+        the handle's stream (rip_get_output_jpeg_sizes)."""
+        was = None
+        if head is not None and int(head) != self.get_selected_output_head():
+            was = self.get_selected_output_head()
+            self._call("rip_select_output_head", int(head))
+        try:
+            n = C.c_int()
+            self._call("rip_get_output_jpeg_sizes", None, 0, C.byref(n))
+            sizes = np.zeros(n.value, np.uint32)
+            if n.value:
+                self._call("rip_get_output_jpeg_sizes", sizes.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+            return sizes
+        finally:
+            if was is not None:
+                self._call("rip_select_output_head", was)
 
     def get_output_clahe(self):
         """(clip_limit, tiles_x, tiles_y) of the selected output head."""
