@@ -1,6 +1,6 @@
-"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its companion libraries -- the table COMPANIONS below: the kernels of
-the output stage, the four libraries of the resize stage, the output heads' copy, the valid-pixel masks and the YUV 4:2:0 formats --
-and the further kernel libraries of the tables STAGE_LIBRARIES (CLAHE) and ENCODER_LIBRARIES (JPEG) for gfx950 with hipcc.
+"""Builds librip_hip.so (the C-ABI library, include/rip.h) and its kernel libraries -- the table KERNEL_LIBRARIES below: the kernels
+of the output stage, the four libraries of the resize stage, the output heads' copy, the valid-pixel masks, the YUV 4:2:0 formats,
+CLAHE and the JPEG encoder -- for gfx950 with hipcc.
 
 In-tree build: the .so lands next to this file so it travels with the repo snapshot.
 -ffp-contract=off is part of the numerical contract (OpenCV's separate float mul/add)."""
@@ -13,12 +13,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librip_hip.so")
 SOURCES = ["rip_chain.hip", "rip_stats.hip", "rip_ccc.hip", "rip_remap.hip", "rip_maps.hip", "rip_fused.hip", "rip_probe.hip", "rip_demosaic.hip", "rip_raw16.hip", "rip_packed.hip", "rip_yaml.cpp", "rip_params.cpp", "rip_output_tables.cpp", "rip_color_tables.cpp", "rip_undistort.cpp", "rip_ccc_model.cpp", "rip_png.cpp", "rip_plan.cpp", "rip_constants.cpp", "rip_batch.cpp", "rip_output_stage.cpp", "rip_ring.cpp", "rip_settings.cpp", "rip_api.cpp"]  # compiled in parallel
-HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile_deal.hpp", "rip_round_map.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_yaml.hpp", "rip_params.hpp", "rip_output_tables.hpp", "rip_color_tables.hpp", "rip_undistort.hpp", "rip_ccc_model.hpp", "rip_png.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", "rip_mask.hpp", "rip_yuv.hpp", "rip_clahe.hpp", "rip_jpeg.hpp", os.path.join("..", "..", "include", "rip.h")]
-# The companion libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
-# what tests/variant_cases.py closes over; each companion's table is closed by a tests/*_variant_cases.py of its own.
+HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_dev.hpp", "rip_tile_deal.hpp", "rip_round_map.hpp", "rip_tile.hpp", "rip_raw16_dev.hpp", "rip_unpack.hpp", "rip_host.hpp", "rip_launch_info.hpp", "rip_yaml.hpp", "rip_params.hpp", "rip_output_tables.hpp", "rip_color_tables.hpp", "rip_undistort.hpp", "rip_ccc_model.hpp", "rip_png.hpp", "rip_handle.hpp", "rip_output.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_fit.hpp", "rip_aa.hpp", "rip_heads.hpp", "rip_mask.hpp", "rip_yuv.hpp", "rip_clahe.hpp", "rip_jpeg.hpp", os.path.join("..", "..", "include", "rip.h")]
+# The kernel libraries: kernels behind one header each, in libraries of their own so that librip_hip.so's kernel table stays
+# what tests/variant_cases.py closes over; each library's table is closed by a tests/*_variant_cases.py of its own.
 # librip_hip.so -- every build of it: the default one, the sanitizer build and the A/B variants under variants/ -- links against
-# these files, in the table's order, and finds them through its $ORIGIN rpath.  A companion's interface is its headers alone, so a
-# rebuild of it does not ask for a relink of the libraries that use it.  One row each, closed by tests/test_companion_libraries.py:
+# these files, in the table's order, and finds them through its $ORIGIN rpath.  A library's interface is its headers alone, so a
+# rebuild of it does not ask for a relink of the libraries that use it.  One row each, closed by tests/test_kernel_libraries.py:
 #   out    the output stage's kernels (rip_set_output_format) and their one launch function; tests/output_variant_cases.py
 #   rsz    the resize stage's kernels (rip_set_output_size); tests/resize_variant_cases.py
 #   area   the resize stage's area interpolation (rip_set_output_interpolation); tests/area_variant_cases.py
@@ -32,10 +32,16 @@ HEADERS = ["rip_kernels.hpp", "rip_device.hpp", "rip_chain_dev.hpp", "rip_remap_
 #          rip_get_output_mask); rip_round_map.hpp is the map quantiser it shares with the remap kernels; tests/mask_variant_cases.py
 #   yuv    yuv420_kernel<true / false>, the delivered BGR picture as nv12 / i420 (rip_set_output_format, rip_set_output_yuv_matrix);
 #          tests/yuv_variant_cases.py
-# rip_resize_dev.hpp is the device code and the launch checks the libraries of the resize stage share.
-Companion = collections.namedtuple("Companion", "key out sources headers build_dir")
+#   clahe  clahe_lut_kernel and clahe_apply_kernel, cv::CLAHE of a delivered one-channel picture (rip_set_output_clahe); its device
+#          code is rip_clahe_dev.hpp; tests/clahe_variant_cases.py
+#   jpeg   jpeg_transform_kernel<true / false>, jpeg_size_kernel, jpeg_scan_kernel and jpeg_write_kernel, the delivered picture as a
+#          baseline JPEG stream (rip_set_output_format "jpeg", rip_set_output_jpeg); its device code is rip_jpeg_dev.hpp, and it takes
+#          the matrix struct of rip_yuv.hpp; tests/jpeg_variant_cases.py
+# rip_resize_dev.hpp is the device code and the launch checks the libraries of the resize stage share; rip_launch_info.hpp is the
+# launch record every launch function fills.
+KernelLibrary = collections.namedtuple("KernelLibrary", "key out sources headers build_dir")
 RESIZE_SHARED = ["rip_resize_dev.hpp", "rip_resize.hpp", "rip_area.hpp"]
-COMPANIONS = tuple(Companion(key, os.path.join(HERE, "librip_%s_hip.so" % key), sources, headers, "build_" + key) for key, sources, headers in (
+KERNEL_LIBRARIES = tuple(KernelLibrary(key, os.path.join(HERE, "librip_%s_hip.so" % key), sources, headers + ["rip_launch_info.hpp"], "build_" + key) for key, sources, headers in (
     ("out", ["rip_output.hip"], ["rip_output.hpp"]),
     ("rsz", ["rip_resize.hip"], RESIZE_SHARED),
     ("area", ["rip_area.hip"], RESIZE_SHARED),
@@ -44,20 +50,7 @@ COMPANIONS = tuple(Companion(key, os.path.join(HERE, "librip_%s_hip.so" % key), 
     ("heads", ["rip_heads.hip"], ["rip_heads.hpp"]),
     ("mask", ["rip_mask.hip"], ["rip_mask.hpp", "rip_round_map.hpp"]),
     ("yuv", ["rip_yuv.hip"], ["rip_yuv.hpp"]),
-))
-# Further kernel libraries of the output stage, in a table of their own: COMPANIONS is closed by tests/test_companion_libraries.py over
-# its eight rows.  Same row type, same build function, same dating; every build of librip_hip.so links them behind the companions.
-#   clahe  clahe_lut_kernel and clahe_apply_kernel, cv::CLAHE of a delivered one-channel picture (rip_set_output_clahe); its device
-#          code is rip_clahe_dev.hpp; tests/clahe_variant_cases.py, closed by tests/test_clahe_library.py
-STAGE_LIBRARIES = tuple(Companion(key, os.path.join(HERE, "librip_%s_hip.so" % key), sources, headers, "build_" + key) for key, sources, headers in (
     ("clahe", ["rip_clahe.hip"], ["rip_clahe.hpp", "rip_clahe_dev.hpp"]),
-))
-# The libraries that turn a delivered picture into a coded stream, in a third table of the same row type: STAGE_LIBRARIES is closed by
-# tests/test_clahe_library.py over its one row.  Same build function, same dating; linked behind the two tables above.
-#   jpeg   jpeg_transform_kernel<true / false>, jpeg_size_kernel, jpeg_scan_kernel and jpeg_write_kernel, the delivered picture as a
-#          baseline JPEG stream (rip_set_output_format "jpeg", rip_set_output_jpeg); its device code is rip_jpeg_dev.hpp, and it takes
-#          the matrix struct of rip_yuv.hpp; tests/jpeg_variant_cases.py, closed by tests/test_jpeg_library.py
-ENCODER_LIBRARIES = tuple(Companion(key, os.path.join(HERE, "librip_%s_hip.so" % key), sources, headers, "build_" + key) for key, sources, headers in (
     ("jpeg", ["rip_jpeg.hip"], ["rip_jpeg.hpp", "rip_jpeg_dev.hpp", "rip_yuv.hpp"]),
 ))
 # per-source additions.  rip_chain.hip: LLVM's max-ILP machine scheduler -- the fused chain is bound by VALU issue and LDS at
@@ -78,17 +71,12 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def companion(key):
-    """The row of COMPANIONS with that key."""
-    return next(c for c in COMPANIONS if c.key == key)
-
-
 def kernel_library(key):
-    """The row of COMPANIONS, STAGE_LIBRARIES or ENCODER_LIBRARIES with that key."""
-    return next(c for c in COMPANIONS + STAGE_LIBRARIES + ENCODER_LIBRARIES if c.key == key)
+    """The row of KERNEL_LIBRARIES with that key."""
+    return next(c for c in KERNEL_LIBRARIES if c.key == key)
 
 
-def companion_up_to_date(key):
+def kernel_library_up_to_date(key):
     c = kernel_library(key)
     if not os.path.exists(c.out):
         return False
@@ -97,30 +85,22 @@ def companion_up_to_date(key):
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def companions_up_to_date():
-    return all(companion_up_to_date(c.key) for c in COMPANIONS)
-
-
-def stage_libraries_up_to_date():
-    return all(companion_up_to_date(c.key) for c in STAGE_LIBRARIES)
-
-
-def encoder_libraries_up_to_date():
-    return all(companion_up_to_date(c.key) for c in ENCODER_LIBRARIES)
+def kernel_libraries_up_to_date():
+    return all(kernel_library_up_to_date(c.key) for c in KERNEL_LIBRARIES)
 
 
 def up_to_date():
-    if not os.path.exists(OUT) or not companions_up_to_date() or not stage_libraries_up_to_date() or not encoder_libraries_up_to_date():
+    if not os.path.exists(OUT) or not kernel_libraries_up_to_date():
         return False
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def build_companion(key, force=False, verbose=False):
-    """One companion, stage or encoder library, next to librip_hip.so."""
+def build_kernel_library(key, force=False, verbose=False):
+    """One kernel library, next to librip_hip.so."""
     _, out, sources, _, bdir_name = kernel_library(key)
-    if not force and companion_up_to_date(key):
+    if not force and kernel_library_up_to_date(key):
         return out
     bdir = os.path.join(HERE, bdir_name)
     os.makedirs(bdir, exist_ok=True)
@@ -170,12 +150,12 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
     out=".../variants/x.so"; the default build takes no extra flags beyond $RIP_EXTRA_FLAGS."""
     if asan:
         out, tag = out or ASAN_OUT, tag or "_asan"
-        if not force and os.path.exists(out) and companions_up_to_date() and stage_libraries_up_to_date() and encoder_libraries_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
+        if not force and os.path.exists(out) and kernel_libraries_up_to_date() and all(os.path.getmtime(os.path.join(CSRC, d)) <= os.path.getmtime(out) for d in SOURCES + HEADERS):
             return out
     if out is None and not force and up_to_date():
         return OUT
-    for c in COMPANIONS + STAGE_LIBRARIES + ENCODER_LIBRARIES:  # every build of librip_hip.so links against all of them; `force` is about the library asked for
-        build_companion(c.key, verbose=verbose)
+    for c in KERNEL_LIBRARIES:  # every build of librip_hip.so links against all of them; `force` is about the library asked for
+        build_kernel_library(c.key, verbose=verbose)
     out = out or OUT
     objs = []
     procs = []
@@ -197,9 +177,9 @@ def build(force=False, verbose=False, out=None, extra_flags=None, tag="", asan=F
             raise RuntimeError("hipcc failed on %s:\n%s" % (s, log))
         if verbose and log.strip():
             print(log)
-    # the companions are found next to the library ($ORIGIN) or one directory up (variants/*.so)
-    companion = ["-L" + HERE] + ["-l:" + os.path.basename(c.out) for c in COMPANIONS + STAGE_LIBRARIES + ENCODER_LIBRARIES] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + companion + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
+    # the kernel libraries are found next to the library ($ORIGIN) or one directory up (variants/*.so)
+    kernel_libs = ["-L" + HERE] + ["-l:" + os.path.basename(c.out) for c in KERNEL_LIBRARIES] + ["-Wl,-rpath,$ORIGIN:$ORIGIN/.."]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + kernel_libs + ([_gcc_lib("libasan.so"), _gcc_lib("libubsan.so"), "-lstdc++", "-lpthread"] if asan else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("link failed:\n" + r.stdout)

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(kAaBlock) void aa_kernel(AaParams p, FitWindow w) {
 }
 }  // namespace
 
-bool launch_aa(const AaParams& p, const FitWindow& w, hipStream_t stream, ResizeLaunchInfo* info) {
+bool launch_aa(const AaParams& p, const FitWindow& w, hipStream_t stream, LaunchInfo* info) {
   if (!layout_ok(p, w) || !aa_ok(p)) return false;
   const bool win = w.x != 0 || w.y != 0 || w.frame_cols != p.src_cols || w.frame_rows != p.src_rows;
   static const NamedKernel<AaParams, FitWindow> kernels[2][2] = {{RIP_NAMED_KERNEL(aa_kernel<1, false>), RIP_NAMED_KERNEL(aa_kernel<1, true>)},
@@ -33,7 +33,7 @@ bool launch_aa(const AaParams& p, const FitWindow& w, hipStream_t stream, Resize
   const dim3 grid = aa_grid(p);
   const size_t lds_bytes = (size_t)p.lds_rows * kAaTileCols * p.channels;
   hipLaunchKernelGGL(k.fn, grid, dim3(kAaBlock), lds_bytes, stream, p, w);
-  if (info) *info = ResizeLaunchInfo{k.name, grid.x, grid.y, (unsigned)kAaBlock};
+  if (info) *info = LaunchInfo{k.name, grid.x, grid.y, (unsigned)kAaBlock};
   return true;
 }
 

@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
 #include "rip_resize.hpp"
 
 namespace rip {
@@ -56,6 +57,6 @@ struct AaParams {
 // F, read in place (rip_resize.hpp FitWindow).  false -- nothing launched -- for sizes or channel counts outside the limits, a factor
 // above kAaMaxFactor on an axis, the identity, pitches that break the alignment rules above, a window that does not lie inside F, a
 // tile height or an LDS size outside the limits, or a missing table.
-__attribute__((visibility("default"))) bool launch_aa(const AaParams& p, const FitWindow& w, hipStream_t stream, ResizeLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_aa(const AaParams& p, const FitWindow& w, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(kAreaBlock) void area_reduce_kernel(AreaParams p) {
 }
 }  // namespace
 
-bool launch_area_reduce(const AreaParams& p, hipStream_t stream, ResizeLaunchInfo* info) {
+bool launch_area_reduce(const AreaParams& p, hipStream_t stream, LaunchInfo* info) {
   bool whole;
   if (!layout_ok(p, whole_frame(p.src_rows, p.src_cols)) || !area_ok(p, &whole)) return false;
   static const NamedKernel<AreaParams> kernels[2][2] = {{RIP_NAMED_KERNEL(area_reduce_kernel<1, false>), RIP_NAMED_KERNEL(area_reduce_kernel<1, true>)},

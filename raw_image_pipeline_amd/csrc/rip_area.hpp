@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
 #include "rip_resize.hpp"
 
 namespace rip {
@@ -49,6 +50,6 @@ struct AreaParams {
 // Enqueues one area resize of n_frames frames on `stream`.  false -- nothing launched -- for sizes or channel counts outside the
 // limits, an upscale on either axis, the identity, pitches that break the alignment rules above, a `whole` flag that does not match
 // the sizes, or a missing table.
-__attribute__((visibility("default"))) bool launch_area_reduce(const AreaParams& p, hipStream_t stream, ResizeLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_area_reduce(const AreaParams& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

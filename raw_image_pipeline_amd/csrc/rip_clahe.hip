@@ -36,20 +36,20 @@ __global__ __launch_bounds__(kClaheBlock) void clahe_apply_kernel(ClaheParams p,
 }
 }  // namespace
 
-bool launch_clahe_lut(const ClaheParams& p, hipStream_t stream, ClaheLaunchInfo* info) {
+bool launch_clahe_lut(const ClaheParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!clahe_ok(p)) return false;
   const dim3 grid((unsigned)p.tiles_x, (unsigned)p.tiles_y, (unsigned)p.n_frames);
   hipLaunchKernelGGL(clahe_lut_kernel, grid, dim3(kClaheBlock), (size_t)kClaheLutLdsBytes, stream, p);
-  if (info) *info = ClaheLaunchInfo{"clahe_lut_kernel", grid.x, grid.y, (unsigned)kClaheBlock};
+  if (info) *info = LaunchInfo{"clahe_lut_kernel", grid.x, grid.y, (unsigned)kClaheBlock};
   return true;
 }
 
-bool launch_clahe_apply(const ClaheParams& p, hipStream_t stream, ClaheLaunchInfo* info) {
+bool launch_clahe_apply(const ClaheParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!clahe_ok(p)) return false;
   const int strip_rows = clahe_strip_rows(p);
   const dim3 grid(1u, (unsigned)((p.tiles_y + 1) * (p.th / strip_rows + 1)), (unsigned)p.n_frames);
   hipLaunchKernelGGL(clahe_apply_kernel, grid, dim3(kClaheBlock), (size_t)2 * p.tiles_x * kClaheBins, stream, p, strip_rows);
-  if (info) *info = ClaheLaunchInfo{"clahe_apply_kernel", grid.x, grid.y, (unsigned)kClaheBlock};
+  if (info) *info = LaunchInfo{"clahe_apply_kernel", grid.x, grid.y, (unsigned)kClaheBlock};
   return true;
 }
 

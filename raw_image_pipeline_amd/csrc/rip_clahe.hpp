@@ -10,6 +10,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
+
 namespace rip {
 
 constexpr int kClaheBlock = 256;          // lanes of a workgroup of either kernel
@@ -63,16 +65,10 @@ inline void clahe_constants(int rows, int cols, int tiles_x, int tiles_y, double
 // bytes of the tables of n frames
 inline size_t clahe_lut_bytes(int tiles_x, int tiles_y, int n_frames) { return (size_t)n_frames * tiles_x * tiles_y * kClaheBins; }
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so)
-struct ClaheLaunchInfo {
-  const char* kernel;
-  unsigned grid_x, grid_y, block;
-};
-
 // Enqueue the table kernel / the blend of n_frames frames on `stream`.  false -- nothing launched -- for a null pointer, a picture
 // with fewer than two pixels per tile and side, tile counts outside 1 .. kClaheMaxTiles, constants that are not clahe_constants' of
 // that picture, a pitch below a row, a misaligned table block or a frame count outside 1 .. 65535.
-__attribute__((visibility("default"))) bool launch_clahe_lut(const ClaheParams& p, hipStream_t stream, ClaheLaunchInfo* info);
-__attribute__((visibility("default"))) bool launch_clahe_apply(const ClaheParams& p, hipStream_t stream, ClaheLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_clahe_lut(const ClaheParams& p, hipStream_t stream, LaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_clahe_apply(const ClaheParams& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kRszBlock) void fit_pad_kernel(FitPadParams p) {
 }
 }  // namespace
 
-bool launch_fit_resize(const ResizeParams& p, const FitWindow& w, hipStream_t stream, ResizeLaunchInfo* info) {
+bool launch_fit_resize(const ResizeParams& p, const FitWindow& w, hipStream_t stream, LaunchInfo* info) {
   bool mean2;
   if (!layout_ok(p, w) || !linear_ok(p, &mean2)) return false;
   static const NamedKernel<ResizeParams, FitWindow> kernels[2][2] = {{RIP_NAMED_KERNEL(fit_linear_kernel<1>), RIP_NAMED_KERNEL(fit_mean2_kernel<1>)},
@@ -71,7 +71,7 @@ bool launch_fit_resize(const ResizeParams& p, const FitWindow& w, hipStream_t st
   return true;
 }
 
-bool launch_fit_area(const AreaParams& p, const FitWindow& w, hipStream_t stream, ResizeLaunchInfo* info) {
+bool launch_fit_area(const AreaParams& p, const FitWindow& w, hipStream_t stream, LaunchInfo* info) {
   bool whole;
   if (!layout_ok(p, w) || !area_ok(p, &whole)) return false;
   static const NamedKernel<AreaParams, FitWindow> kernels[2][2] = {{RIP_NAMED_KERNEL(fit_area_kernel<1, false>), RIP_NAMED_KERNEL(fit_area_kernel<1, true>)},
@@ -80,7 +80,7 @@ bool launch_fit_area(const AreaParams& p, const FitWindow& w, hipStream_t stream
   return true;
 }
 
-bool launch_fit_pad(const FitPadParams& p, hipStream_t stream, ResizeLaunchInfo* info) {
+bool launch_fit_pad(const FitPadParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!p.dst || p.n_frames < 1 || p.n_frames > 65535 || (p.channels != 1 && p.channels != 3)) return false;
   if (p.rows < 1 || p.cols < 1 || p.rows > kRszMaxSide || p.cols > kRszMaxSide) return false;
   if (p.pic_w < 1 || p.pic_h < 1 || p.pic_x < 0 || p.pic_y < 0 || p.pic_x > p.cols - p.pic_w || p.pic_y > p.rows - p.pic_h) return false;
@@ -89,7 +89,7 @@ bool launch_fit_pad(const FitPadParams& p, hipStream_t stream, ResizeLaunchInfo*
   const dim3 grid = rsz_grid(p.rows, p.cols, p.n_frames);
   if (p.channels == 1) hipLaunchKernelGGL((fit_pad_kernel<1>), grid, dim3(kRszBlock), 0, stream, p);
   else hipLaunchKernelGGL((fit_pad_kernel<3>), grid, dim3(kRszBlock), 0, stream, p);
-  if (info) *info = ResizeLaunchInfo{p.channels == 1 ? "fit_pad_kernel<1>" : "fit_pad_kernel<3>", grid.x, grid.y, (unsigned)kRszBlock};
+  if (info) *info = LaunchInfo{p.channels == 1 ? "fit_pad_kernel<1>" : "fit_pad_kernel<3>", grid.x, grid.y, (unsigned)kRszBlock};
   return true;
 }
 

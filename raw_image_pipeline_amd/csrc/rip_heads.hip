@@ -45,14 +45,14 @@ __global__ __launch_bounds__(kHeadBlock) void head_copy_kernel(HeadCopyParams p)
   }
 }
 
-bool launch_head_copy(const HeadCopyParams& p, hipStream_t stream, HeadLaunchInfo* info) {
+bool launch_head_copy(const HeadCopyParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!p.src || !p.dst || p.rows < 1 || p.row_bytes < 1 || p.row_bytes >= ((size_t)1 << 24) || p.n_frames < 1 || p.n_frames > 65535) return false;
   if ((reinterpret_cast<uintptr_t>(p.src) | p.src_step | p.src_frame_stride) & 15) return false;
   if (p.src_step < ((p.row_bytes + 15) & ~(size_t)15) || p.dst_step < p.row_bytes) return false;
   if (p.n_frames > 1 && (p.src_frame_stride < p.src_step * (size_t)p.rows || p.dst_frame_stride < p.dst_step * (size_t)(p.rows - 1) + p.row_bytes)) return false;
   const dim3 grid((unsigned)((p.row_bytes + kHeadBytesPerBlock - 1) / kHeadBytesPerBlock), (unsigned)(p.rows < 65535 ? p.rows : 65535), (unsigned)p.n_frames);
   hipLaunchKernelGGL(head_copy_kernel, grid, dim3(kHeadBlock), 0, stream, p);
-  if (info) *info = HeadLaunchInfo{"head_copy_kernel", grid.x, grid.y, (unsigned)kHeadBlock};
+  if (info) *info = LaunchInfo{"head_copy_kernel", grid.x, grid.y, (unsigned)kHeadBlock};
   return true;
 }
 

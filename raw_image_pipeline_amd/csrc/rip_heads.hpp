@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
+
 namespace rip {
 
 // Geometry of the kernel (the converter's shape, rip_output.hpp): every lane owns kHeadBytesPerLane consecutive source bytes of one
@@ -30,14 +32,8 @@ struct HeadCopyParams {
   size_t row_bytes;  // cols * channels, below 16 MiB
 };
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH), as ResizeLaunchInfo (rip_resize.hpp) says it
-struct HeadLaunchInfo {
-  const char* kernel;
-  unsigned grid_x, grid_y, block;
-};
-
 // Enqueues one copy of n_frames frames on `stream`.  false -- nothing launched -- for an empty image, more than 65535 frames or
 // pitches that break the rules above.
-__attribute__((visibility("default"))) bool launch_head_copy(const HeadCopyParams& p, hipStream_t stream, HeadLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_head_copy(const HeadCopyParams& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

@@ -25,36 +25,36 @@ unsigned groups(size_t items) { return (unsigned)((items + kJpegBlock - 1) / kJp
 
 }  // namespace
 
-bool launch_jpeg_transform(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info) {
+bool launch_jpeg_transform(const JpegParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!jpeg_ok(p)) return false;
   const dim3 grid(groups(jpeg_blocks(p.rows, p.cols, p.channels)), 1, (unsigned)p.n_frames);
   if (p.channels == 3) hipLaunchKernelGGL(jpeg_transform_kernel<true>, grid, dim3(kJpegBlock), 0, stream, p);
   else hipLaunchKernelGGL(jpeg_transform_kernel<false>, grid, dim3(kJpegBlock), 0, stream, p);
-  if (info) *info = JpegLaunchInfo{p.channels == 3 ? "jpeg_transform_kernel<true>" : "jpeg_transform_kernel<false>", grid.x, grid.y, (unsigned)kJpegBlock};
+  if (info) *info = LaunchInfo{p.channels == 3 ? "jpeg_transform_kernel<true>" : "jpeg_transform_kernel<false>", grid.x, grid.y, (unsigned)kJpegBlock};
   return true;
 }
 
-bool launch_jpeg_size(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info) {
+bool launch_jpeg_size(const JpegParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!jpeg_ok(p)) return false;
   const dim3 grid(groups((size_t)jpeg_intervals(p.rows, p.channels, p.restart_rows)), 1, (unsigned)p.n_frames);
   hipLaunchKernelGGL(jpeg_size_kernel, grid, dim3(kJpegBlock), 0, stream, p);
-  if (info) *info = JpegLaunchInfo{"jpeg_size_kernel", grid.x, grid.y, (unsigned)kJpegBlock};
+  if (info) *info = LaunchInfo{"jpeg_size_kernel", grid.x, grid.y, (unsigned)kJpegBlock};
   return true;
 }
 
-bool launch_jpeg_scan(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info) {
+bool launch_jpeg_scan(const JpegParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!jpeg_ok(p)) return false;
   const dim3 grid(groups((size_t)p.n_frames), 1, 1);
   hipLaunchKernelGGL(jpeg_scan_kernel, grid, dim3(kJpegBlock), 0, stream, p);
-  if (info) *info = JpegLaunchInfo{"jpeg_scan_kernel", grid.x, grid.y, (unsigned)kJpegBlock};
+  if (info) *info = LaunchInfo{"jpeg_scan_kernel", grid.x, grid.y, (unsigned)kJpegBlock};
   return true;
 }
 
-bool launch_jpeg_write(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info) {
+bool launch_jpeg_write(const JpegParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!jpeg_ok(p)) return false;
   const dim3 grid(groups((size_t)jpeg_intervals(p.rows, p.channels, p.restart_rows)) + 1, 1, (unsigned)p.n_frames);
   hipLaunchKernelGGL(jpeg_write_kernel, grid, dim3(kJpegBlock), 0, stream, p);
-  if (info) *info = JpegLaunchInfo{"jpeg_write_kernel", grid.x, grid.y, (unsigned)kJpegBlock};
+  if (info) *info = LaunchInfo{"jpeg_write_kernel", grid.x, grid.y, (unsigned)kJpegBlock};
   return true;
 }
 

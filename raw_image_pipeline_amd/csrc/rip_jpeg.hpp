@@ -15,6 +15,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
 #include "rip_yuv.hpp"
 
 namespace rip {
@@ -157,18 +158,12 @@ inline int jpeg_build_header(int rows, int cols, int channels, int restart_rows,
   return (int)(o - out);
 }
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so)
-struct JpegLaunchInfo {
-  const char* kernel;  // the instantiation as the demangler prints it, without namespaces
-  unsigned grid_x, grid_y, block;
-};
-
 // Each enqueues one kernel for n_frames frames on `stream`, in this order.  false -- nothing launched -- for a null pointer, an empty
 // picture, a channel count other than 1 or 3, a side beyond 65535, restart_rows outside 1..64, a restart interval beyond 65535
 // MCUs, a slot below header + 2 or beyond 32 bits, a frame stride below the slot, or more than 65535 frames.
-__attribute__((visibility("default"))) bool launch_jpeg_transform(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info);
-__attribute__((visibility("default"))) bool launch_jpeg_size(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info);
-__attribute__((visibility("default"))) bool launch_jpeg_scan(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info);
-__attribute__((visibility("default"))) bool launch_jpeg_write(const JpegParams& p, hipStream_t stream, JpegLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_jpeg_transform(const JpegParams& p, hipStream_t stream, LaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_jpeg_size(const JpegParams& p, hipStream_t stream, LaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_jpeg_scan(const JpegParams& p, hipStream_t stream, LaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_jpeg_write(const JpegParams& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

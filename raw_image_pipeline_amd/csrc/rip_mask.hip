@@ -90,24 +90,24 @@ __global__ __launch_bounds__(kMaskBlock) void mask_threshold_kernel(MaskThreshol
   }
 }
 
-bool launch_rect_mask(const RectMaskParams& p, hipStream_t stream, MaskLaunchInfo* info) {
+bool launch_rect_mask(const RectMaskParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!p.map_xy || !p.dst || p.drows < 1 || p.dcols < 1 || p.src_rows < 1 || p.src_cols < 1) return false;
   if (reinterpret_cast<uintptr_t>(p.map_xy) & 7) return false;
   if (p.dst_step < (size_t)p.dcols) return false;
   const dim3 grid((unsigned)((p.dcols + kMaskPxPerBlock - 1) / kMaskPxPerBlock), (unsigned)(p.drows < 65535 ? p.drows : 65535));
   if (p.binary) hipLaunchKernelGGL(rect_mask_kernel<true>, grid, dim3(kMaskBlock), 0, stream, p);
   else hipLaunchKernelGGL(rect_mask_kernel<false>, grid, dim3(kMaskBlock), 0, stream, p);
-  if (info) *info = MaskLaunchInfo{p.binary ? "rect_mask_kernel<true>" : "rect_mask_kernel<false>", grid.x, grid.y, (unsigned)kMaskBlock};
+  if (info) *info = LaunchInfo{p.binary ? "rect_mask_kernel<true>" : "rect_mask_kernel<false>", grid.x, grid.y, (unsigned)kMaskBlock};
   return true;
 }
 
-bool launch_mask_threshold(const MaskThresholdParams& p, hipStream_t stream, MaskLaunchInfo* info) {
+bool launch_mask_threshold(const MaskThresholdParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!p.img || p.rows < 1 || p.cols < 1) return false;
   if ((reinterpret_cast<uintptr_t>(p.img) | p.step) & 3) return false;
   if (p.step < (((size_t)p.cols + 3) & ~(size_t)3)) return false;
   const dim3 grid((unsigned)((p.cols + kMaskPxPerBlock - 1) / kMaskPxPerBlock), (unsigned)(p.rows < 65535 ? p.rows : 65535));
   hipLaunchKernelGGL(mask_threshold_kernel, grid, dim3(kMaskBlock), 0, stream, p);
-  if (info) *info = MaskLaunchInfo{"mask_threshold_kernel", grid.x, grid.y, (unsigned)kMaskBlock};
+  if (info) *info = LaunchInfo{"mask_threshold_kernel", grid.x, grid.y, (unsigned)kMaskBlock};
   return true;
 }
 

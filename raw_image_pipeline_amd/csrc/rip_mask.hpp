@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
+
 namespace rip {
 
 // Geometry of both kernels (the converter's shape, rip_output.hpp): every lane owns kMaskPxPerLane consecutive pixels of one row, a
@@ -39,15 +41,9 @@ struct MaskThresholdParams {
   int rows, cols;
 };
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH), as OutputLaunchInfo (rip_output.hpp) says it
-struct MaskLaunchInfo {
-  const char* kernel;
-  unsigned grid_x, grid_y, block;
-};
-
 // Enqueue one launch on `stream`.  false -- nothing launched -- for a null pointer, an empty image or source, or pointers and
 // pitches that break the rules above.
-__attribute__((visibility("default"))) bool launch_rect_mask(const RectMaskParams& p, hipStream_t stream, MaskLaunchInfo* info);
-__attribute__((visibility("default"))) bool launch_mask_threshold(const MaskThresholdParams& p, hipStream_t stream, MaskLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_rect_mask(const RectMaskParams& p, hipStream_t stream, LaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_mask_threshold(const MaskThresholdParams& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

@@ -118,14 +118,14 @@ __global__ __launch_bounds__(kOutBlock) void output_convert_kernel(OutputConvert
 }
 
 template <typename Fmt>
-void launch(const OutputConvertParams& p, hipStream_t stream, const char* name, OutputLaunchInfo* info) {
+void launch(const OutputConvertParams& p, hipStream_t stream, const char* name, LaunchInfo* info) {
   const dim3 grid((unsigned)((p.cols + kOutPxPerBlock - 1) / kOutPxPerBlock), (unsigned)(p.rows < 65535 ? p.rows : 65535), (unsigned)p.n_frames);
   hipLaunchKernelGGL(output_convert_kernel<Fmt>, grid, dim3(kOutBlock), 0, stream, p);
-  if (info) *info = OutputLaunchInfo{name, grid.x, grid.y, (unsigned)kOutBlock};
+  if (info) *info = LaunchInfo{name, grid.x, grid.y, (unsigned)kOutBlock};
 }
 }  // namespace
 
-bool launch_output_convert(const OutputConvertParams& p, hipStream_t stream, OutputLaunchInfo* info) {
+bool launch_output_convert(const OutputConvertParams& p, hipStream_t stream, LaunchInfo* info) {
   if (!p.src || !p.dst || p.rows < 1 || p.cols < 1 || p.n_frames < 1 || p.n_frames > 65535) return false;
   if ((reinterpret_cast<uintptr_t>(p.src) | p.src_step | p.src_frame_stride) & 3) return false;
   if (p.src_step < (((size_t)p.cols * 3 + 3) & ~(size_t)3)) return false;

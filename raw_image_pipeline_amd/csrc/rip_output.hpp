@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
+
 namespace rip {
 
 // ids of the format names of rip.h, in the order rip_host.cpp kOutputFormatNames lists them
@@ -59,14 +61,8 @@ struct OutputConvertParams {
   const void* table;  // planar formats: 3 x 256 elements on the device, plane-major (rip::build_output_table)
 };
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so)
-struct OutputLaunchInfo {
-  const char* kernel;  // the instantiation as the demangler prints it, without namespaces
-  unsigned grid_x, grid_y, block;
-};
-
 // Enqueues one conversion of n_frames frames on `stream`.  false -- nothing launched -- for an unknown format, an empty image
 // or pitches that break the alignment rules above.
-__attribute__((visibility("default"))) bool launch_output_convert(const OutputConvertParams& p, hipStream_t stream, OutputLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_output_convert(const OutputConvertParams& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

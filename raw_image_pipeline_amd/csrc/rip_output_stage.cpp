@@ -1,8 +1,8 @@
 // rip_output_stage.cpp -- everything behind the pipeline's image F: the staging image the chain's last kernel writes, the resize,
 // pad, converter and YUV launches of one output head (prepare_head, enqueue_head), several heads from one run of the chain
 // (run_batch_heads) and the valid-pixel masks, which run a head's launches on the coverage image.  The kernels live in the
-// companion libraries (rip_output/resize/area/fit/aa/heads/mask/yuv.hpp) and in librip_clahe_hip.so (rip_clahe.hpp), whose two launches
-// end a head that equalises its picture; the chain in front is rip_batch.cpp's run_batch.
+// kernel libraries (rip_output/resize/area/fit/aa/heads/mask/yuv/clahe/jpeg.hpp; CLAHE's two launches end a head that equalises its
+// picture); the chain in front is rip_batch.cpp's run_batch.
 #include <algorithm>
 
 #include "rip_handle.hpp"
@@ -78,8 +78,26 @@ size_t jpeg_interval_scratch(const Plan& pl, int n) {
 // bytes of d_clahe a head needs for n frames: the tables of its CLAHE
 size_t clahe_bytes(const Plan& pl, int n) { return pl.clahe ? rip::clahe_lut_bytes(pl.clahe_tx, pl.clahe_ty, n) : 0; }
 
+// the scratch of the handle a head's launches use for n frames: bytes of d_rsz, d_clahe, d_jpeg_coef and d_jpeg_intervals
+struct HeadScratch {
+  size_t rsz, clahe, jpeg_coef, jpeg_intervals;
+};
+HeadScratch head_scratch(const Plan& pl, int n) { return {rsz_bytes(pl, n), clahe_bytes(pl, n), jpeg_coef_scratch(pl, n), jpeg_interval_scratch(pl, n)}; }
+HeadScratch max(const HeadScratch& a, const HeadScratch& b) {
+  return {std::max(a.rsz, b.rsz), std::max(a.clahe, b.clahe), std::max(a.jpeg_coef, b.jpeg_coef), std::max(a.jpeg_intervals, b.jpeg_intervals)};
+}
+// The heads of a batch run one after another and share the scratch: reserved for the largest before the first of them is prepared,
+// so that a head's own reserve finds room and no buffer moves once a HeadPrep points into it.
+void reserve_head_scratch(rip_pipeline* p, const HeadScratch& s) {
+  p->d_rsz.reserve(s.rsz);
+  p->d_clahe.reserve(s.clahe);
+  p->d_jpeg_coef.reserve(s.jpeg_coef);
+  p->d_jpeg_intervals.reserve(s.jpeg_intervals);
+}
+
 HeadPrep prepare_head(rip_pipeline* p, const Plan& pl, const FrameView& staged, int n) {
   HeadPrep hp;
+  reserve_head_scratch(p, head_scratch(pl, n));
   if (pl.dl_planar) ensure_output_table(p, pl.head, pl.out_fmt);
   hp.converted_from = staged;  // what the converter reads: F, or F' behind a resize
   if (pl.rsz_active) {
@@ -89,22 +107,15 @@ HeadPrep prepare_head(rip_pipeline* p, const Plan& pl, const FrameView& staged, 
     else ensure_resize_tables(p, pl.head, pl.win_h, pl.win_w, pl.pic_h, pl.pic_w, hp.linear);
     if (pl.out_fmt != rip::OUT_NATIVE) {
       hp.converted_from = resized_view(pl);
-      p->d_rsz.reserve(rsz_bytes(pl, n));  // several heads: reserved for the largest before the first of them is prepared
       hp.converted_from.ptr = p->d_rsz.as<uint8_t>();
     }
   }
-  p->d_clahe.reserve(clahe_bytes(pl, n));  // several heads: as d_rsz
-  if (rip::output_format_jpeg(pl.out_fmt)) {
-    ensure_jpeg_constants(p, pl);
-    p->d_jpeg_coef.reserve(jpeg_coef_scratch(pl, n));  // several heads: as d_rsz
-    p->d_jpeg_intervals.reserve(jpeg_interval_scratch(pl, n));
-  }
+  if (rip::output_format_jpeg(pl.out_fmt)) ensure_jpeg_constants(p, pl);
   return hp;
 }
 
 // every launch behind F: a refusal is a bug of the frame call's checks; then the launch error, then the launch record
-template <typename Info>
-void launched(bool accepted, const Info& info, const char* what, int n) {
+void launched(bool accepted, const rip::LaunchInfo& info, const char* what, int n) {
   if (!accepted) throw DeviceError(std::string("internal: ") + what + " refused a layout the frame call had accepted");
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) throw DeviceError(std::string("kernel launch failed: ") + hipGetErrorString(le));
@@ -121,7 +132,7 @@ void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, con
   to.ptr += (size_t)pl.pic_y * to.step + (size_t)pl.pic_x * pl.channels;
   // a window other than F is read in place by the kernels of librip_fit_hip.so, which take the window's origin; no copy of it is made
   const rip::FitWindow win = {pl.win_x, pl.win_y, pl.out_cols, pl.out_rows};
-  rip::ResizeLaunchInfo info = {};
+  rip::LaunchInfo info = {};
   if (pl.rsz_active && pl.rsz_kind >= 2) {  // an antialiased filter: one launch function for all of F and for a window
     const rip::AaParams r = resize_params(hp.aa, staged, to, pl, n);
     launched(rip::launch_aa(r, win, p->stream, &info), info, "the antialiased resize", n);
@@ -168,11 +179,10 @@ void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, con
     if (p->jpeg_frames[pl.head] < first_frame + n || p->d_jpeg_sizes[pl.head].cap < (size_t)(first_frame + n) * 4)
       throw DeviceError("internal: the jpeg sizes of the frame call were not reserved");
     c.sizes = p->d_jpeg_sizes[pl.head].as<uint32_t>() + first_frame;
-    rip::JpegLaunchInfo jpeg_info = {};
-    launched(rip::launch_jpeg_transform(c, p->stream, &jpeg_info), jpeg_info, "the JPEG transform", n);
-    launched(rip::launch_jpeg_size(c, p->stream, &jpeg_info), jpeg_info, "the JPEG sizing pass", n);
-    launched(rip::launch_jpeg_scan(c, p->stream, &jpeg_info), jpeg_info, "the JPEG scan", n);
-    launched(rip::launch_jpeg_write(c, p->stream, &jpeg_info), jpeg_info, "the JPEG writing pass", n);
+    launched(rip::launch_jpeg_transform(c, p->stream, &info), info, "the JPEG transform", n);
+    launched(rip::launch_jpeg_size(c, p->stream, &info), info, "the JPEG sizing pass", n);
+    launched(rip::launch_jpeg_scan(c, p->stream, &info), info, "the JPEG scan", n);
+    launched(rip::launch_jpeg_write(c, p->stream, &info), info, "the JPEG writing pass", n);
     return;
   }
   if (rip::output_format_yuv(pl.out_fmt)) {  // librip_yuv_hip.so's kernel in the converter's place, from the same source
@@ -186,8 +196,7 @@ void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, con
     int coef[9];
     rip::output_yuv_matrix(pl.yuv_matrix, coef, &c.m.yoff);
     for (int i = 0; i < 3; i++) c.m.y[i] = coef[i], c.m.cb[i] = coef[3 + i], c.m.cr[i] = coef[6 + i];
-    rip::YuvLaunchInfo yuv_info = {};
-    launched(rip::launch_yuv420(c, p->stream, &yuv_info), yuv_info, "the YUV 4:2:0 converter", n);
+    launched(rip::launch_yuv420(c, p->stream, &info), info, "the YUV 4:2:0 converter", n);
     return;
   }
   rip::OutputConvertParams c = {};
@@ -198,8 +207,7 @@ void enqueue_head_image(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, con
   c.n_frames = n;
   c.format = pl.out_fmt;
   c.table = pl.dl_planar ? p->out_table[pl.head].dev.ptr : nullptr;
-  rip::OutputLaunchInfo out_info = {};
-  launched(rip::launch_output_convert(c, p->stream, &out_info), out_info, "the output converter", n);
+  launched(rip::launch_output_convert(c, p->stream, &info), info, "the output converter", n);
 }
 
 // Every launch of one head: its delivered image, then CLAHE on the picture's rectangle of it (PARITY.md "Local contrast: CLAHE") -- in
@@ -220,7 +228,7 @@ void enqueue_head(rip_pipeline* p, const Plan& pl, const HeadPrep& hp, const Fra
   c.cols = pl.pic_w;
   c.n_frames = n;
   rip::clahe_constants(pl.pic_h, pl.pic_w, pl.clahe_tx, pl.clahe_ty, pl.clahe_clip, c);
-  rip::ClaheLaunchInfo info = {};
+  rip::LaunchInfo info = {};
   launched(rip::launch_clahe_lut(c, p->stream, &info), info, "the CLAHE tables", n);
   launched(rip::launch_clahe_apply(c, p->stream, &info), info, "the CLAHE blend", n);
 }
@@ -288,19 +296,10 @@ void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const F
     p->d_fmt.reserve(staged.frame_stride * (size_t)n);
     staged.ptr = p->d_fmt.as<uint8_t>();
   }
-  size_t rsz = 0;
+  HeadScratch scratch = {};
   for (int k = 0; k < n_heads; k++)
-    if (dsts[k].ptr) rsz = std::max(rsz, rsz_bytes(plans[k], n));
-  p->d_rsz.reserve(rsz);
-  size_t clahe = 0;
-  for (int k = 0; k < n_heads; k++)
-    if (dsts[k].ptr) clahe = std::max(clahe, clahe_bytes(plans[k], n));
-  p->d_clahe.reserve(clahe);
-  size_t jpeg_coef = 0, jpeg_intervals = 0;
-  for (int k = 0; k < n_heads; k++)
-    if (dsts[k].ptr) jpeg_coef = std::max(jpeg_coef, jpeg_coef_scratch(plans[k], n)), jpeg_intervals = std::max(jpeg_intervals, jpeg_interval_scratch(plans[k], n));
-  p->d_jpeg_coef.reserve(jpeg_coef);
-  p->d_jpeg_intervals.reserve(jpeg_intervals);
+    if (dsts[k].ptr) scratch = max(scratch, head_scratch(plans[k], n));
+  reserve_head_scratch(p, scratch);
   HeadPrep hp[rip::kMaxOutputHeads];
   for (int k = 0; k < n_heads; k++)
     if (dsts[k].ptr && !identity_head(plans[k])) hp[k] = prepare_head(p, plans[k], staged, n);
@@ -320,7 +319,7 @@ void run_batch_heads(rip_pipeline* p, const Plan& pl, const Plan* plans, const F
     c.rows = pl.out_rows;
     c.n_frames = n;
     c.row_bytes = (size_t)pl.out_cols * pl.channels;
-    rip::HeadLaunchInfo info = {};
+    rip::LaunchInfo info = {};
     launched(rip::launch_head_copy(c, p->stream, &info), info, "the head copy", n);
     p->head_record[k].copied = 1;
   }
@@ -374,7 +373,7 @@ ConstFrameView ensure_mask_base(rip_pipeline* p, bool remap, int src_rows, int s
       r.dst = buf.as<uint8_t>();
       r.dst_step = pitch;
       r.binary = binary ? 1 : 0;
-      rip::MaskLaunchInfo info = {};
+      rip::LaunchInfo info = {};
       launched(rip::launch_rect_mask(r, p->stream, &info), info, "the rect mask", 0);
     } else {
       HIP_CHECK(hipMemsetAsync(buf.ptr, 255, pitch * (size_t)rows, p->stream));
@@ -420,7 +419,7 @@ ConstFrameView ensure_mask_head(rip_pipeline* p, const Plan& frame_pl, int mode)
       if (binary) {
         LaunchLogScope log_scope(p);
         rip::MaskThresholdParams t = {dst.ptr, dst.step, dst.rows, dst.cols};
-        rip::MaskLaunchInfo info = {};
+        rip::LaunchInfo info = {};
         launched(rip::launch_mask_threshold(t, p->stream, &info), info, "the mask threshold", 0);
       }
     }

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(kRszBlock) void resize_kernel(ResizeParams p) {
 }
 }  // namespace
 
-bool launch_resize(const ResizeParams& p, hipStream_t stream, ResizeLaunchInfo* info) {
+bool launch_resize(const ResizeParams& p, hipStream_t stream, LaunchInfo* info) {
   bool mean2;
   if (!layout_ok(p, whole_frame(p.src_rows, p.src_cols)) || !linear_ok(p, &mean2)) return false;
   static const NamedKernel<ResizeParams> kernels[2][2] = {{RIP_NAMED_KERNEL(resize_kernel<1, false>), RIP_NAMED_KERNEL(resize_kernel<1, true>)},

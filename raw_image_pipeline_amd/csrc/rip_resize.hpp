@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
+
 namespace rip {
 
 // Geometry of the kernel (the converter's, rip_output.hpp): every lane owns kRszPxPerLane consecutive output pixels of one row, a
@@ -50,15 +52,8 @@ struct FitWindow {
   int frame_rows;  // y + src_rows <= frame_rows
 };
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so): the one
-// record of every launch function of the resize stage (this header, rip_area.hpp, rip_fit.hpp)
-struct ResizeLaunchInfo {
-  const char* kernel;  // the instantiation as the demangler prints it, without namespaces
-  unsigned grid_x, grid_y, block;
-};
-
 // Enqueues one resize of n_frames frames on `stream`.  false -- nothing launched -- for sizes or channel counts outside the limits,
 // pitches that break the alignment rules above, or an area2 flag that does not match the sizes.
-__attribute__((visibility("default"))) bool launch_resize(const ResizeParams& p, hipStream_t stream, ResizeLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_resize(const ResizeParams& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

@@ -344,10 +344,10 @@ struct NamedKernel {
 // launches variants[channels == 3][flag] and writes the launch record
 template <typename... A>
 inline void launch_variant(const NamedKernel<A...> (&variants)[2][2], int channels, bool flag, dim3 grid, int block, hipStream_t stream,
-                           ResizeLaunchInfo* info, const A&... args) {
+                           LaunchInfo* info, const A&... args) {
   const NamedKernel<A...>& k = variants[channels == 3][flag];
   hipLaunchKernelGGL(k.fn, grid, dim3(block), 0, stream, args...);
-  if (info) *info = ResizeLaunchInfo{k.name, grid.x, grid.y, (unsigned)block};
+  if (info) *info = LaunchInfo{k.name, grid.x, grid.y, (unsigned)block};
 }
 
 }  // namespace rip

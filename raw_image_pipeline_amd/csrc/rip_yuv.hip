@@ -117,15 +117,15 @@ __global__ __launch_bounds__(kYuvBlock) void yuv420_kernel(Yuv420Params p) {
 }
 
 template <bool SemiPlanar>
-void launch(const Yuv420Params& p, hipStream_t stream, const char* name, YuvLaunchInfo* info) {
+void launch(const Yuv420Params& p, hipStream_t stream, const char* name, LaunchInfo* info) {
   const int groups = (p.rows / 2 + kYuvPairsPerBlock - 1) / kYuvPairsPerBlock;
   const dim3 grid((unsigned)((p.cols + kYuvPxPerBlockX - 1) / kYuvPxPerBlockX), (unsigned)(groups < 65535 ? groups : 65535), (unsigned)p.n_frames);
   hipLaunchKernelGGL(yuv420_kernel<SemiPlanar>, grid, dim3(kYuvBlock), 0, stream, p);
-  if (info) *info = YuvLaunchInfo{name, grid.x, grid.y, (unsigned)kYuvBlock};
+  if (info) *info = LaunchInfo{name, grid.x, grid.y, (unsigned)kYuvBlock};
 }
 }  // namespace
 
-bool launch_yuv420(const Yuv420Params& p, hipStream_t stream, YuvLaunchInfo* info) {
+bool launch_yuv420(const Yuv420Params& p, hipStream_t stream, LaunchInfo* info) {
   if (!p.src || !p.dst || p.rows < 2 || p.cols < 2 || ((p.rows | p.cols) & 1) || p.n_frames < 1 || p.n_frames > 65535) return false;
   if ((reinterpret_cast<uintptr_t>(p.src) | p.src_step | p.src_frame_stride) & 3) return false;
   if (p.src_step < (((size_t)p.cols * 3 + 3) & ~(size_t)3)) return false;

@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rip_launch_info.hpp"
+
 namespace rip {
 
 // Geometry of the kernel: every lane owns 2 rows x kYuvPxPerLane columns (four 2 x 2 blocks); a workgroup of kYuvBlock lanes is
@@ -42,14 +44,8 @@ struct Yuv420Params {
   YuvMatrix m;
 };
 
-// what was launched, for the launch record (rip_kernels.hpp RIP_LOG_LAUNCH; the record's sink is private to librip_hip.so)
-struct YuvLaunchInfo {
-  const char* kernel;  // the instantiation as the demangler prints it, without namespaces
-  unsigned grid_x, grid_y, block;
-};
-
 // Enqueues one conversion of n_frames frames on `stream`.  false -- nothing launched -- for an empty or odd-sized picture, source
 // pitches that break the alignment rule above, a destination pitch below a row or an odd one under i420.
-__attribute__((visibility("default"))) bool launch_yuv420(const Yuv420Params& p, hipStream_t stream, YuvLaunchInfo* info);
+__attribute__((visibility("default"))) bool launch_yuv420(const Yuv420Params& p, hipStream_t stream, LaunchInfo* info);
 
 }  // namespace rip

@@ -2,7 +2,7 @@
 and the GPU tests (tests/test_resize_area_gpu.py).  Importable without a GPU; nothing here looks at the library.
 
 Sizes are (width, height).  The workgroup's output rectangle is TILE_W x TILE_H = 64 x 8 pixels (rip_area.hpp kAreaTileCols /
-kAreaTileRows; tests/test_companion_libraries.py checks the header still says so), one lane per output column, four waves that take the
+kAreaTileRows; tests/test_kernel_libraries.py checks the header still says so), one lane per output column, four waves that take the
 rows w, w + 4 of the rectangle.  kind: "general" (tap lists), "whole" (block sums), "mean2" (the linear path's 2 x 2 kernel)."""
 import collections
 

@@ -84,7 +84,7 @@ static int run(FILE* in, FILE* out) {
   p.yweight = exact_copy(yw.data(), (size_t)yo[H - 1] + yc[H - 1]);
   const rip::FitWindow w = {wx, wy, C, R};
   const bool win = wx != 0 || wy != 0 || ww != C || wh != R;
-  rip::ResizeLaunchInfo info = {};
+  rip::LaunchInfo info = {};
   host_stub::last_launch.count = 0;
   if (!rip::launch_aa(p, w, nullptr, &info) || host_stub::last_launch.count != 1) { printf("refused %d x %d -> %d x %d\n", ww, wh, W, H); return 1; }
   char expect[64];

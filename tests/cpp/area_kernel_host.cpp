@@ -52,7 +52,7 @@ static int run(FILE* in, FILE* out) {
   p.whole = whole; p.scale = scale;
   p.xfirst = xfirst.data(); p.xcount = xcount.data(); p.xwofs = xwofs; p.xweight = xweight;
   p.yfirst = yfirst.data(); p.ycount = ycount.data(); p.ywofs = ywofs; p.yweight = yweight;
-  rip::ResizeLaunchInfo info = {};
+  rip::LaunchInfo info = {};
   if (!rip::launch_area_reduce(p, nullptr, &info)) { printf("refused %d x %d -> %d x %d\n", C, R, W, H); return 1; }
   const char* expect = cn == 1 ? (whole ? "area_reduce_kernel<1, true>" : "area_reduce_kernel<1, false>")
                                : (whole ? "area_reduce_kernel<3, true>" : "area_reduce_kernel<3, false>");

@@ -79,7 +79,7 @@ static int run(FILE* in, FILE* out) {
   p.lut = lut;
   p.rows = H; p.cols = W; p.n_frames = n;
   rip::clahe_constants(H, W, tx, ty, clip, p);
-  rip::ClaheLaunchInfo info = {};
+  rip::LaunchInfo info = {};
   host_stub::last_launch.count = 0;
   if (!rip::launch_clahe_lut(p, nullptr, &info) || host_stub::last_launch.count != 1) { printf("the table launch was refused\n"); return 1; }
   const host_stub::Launch& l = host_stub::last_launch;

@@ -35,7 +35,7 @@ static int run(FILE* in, FILE* out) {
   memset(base, 0xA5, total);
   uint8_t* pic = base + dst_off + (size_t)top * dstep + (size_t)left * cn;
   const rip::FitWindow win = {xs, ys, C, R};
-  rip::ResizeLaunchInfo info = {};
+  rip::LaunchInfo info = {};
   const bool same = ws == Wi && hs == Hi, mean2 = ws == 2 * Wi && hs == 2 * Hi;
   char expect[64];
   if (area && !same && !mean2) {

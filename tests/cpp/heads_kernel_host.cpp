@@ -28,7 +28,7 @@ static int run(size_t row_bytes, int rows, int n, size_t offset, int pitch_kind)
   p.src = src; p.src_step = sstep; p.src_frame_stride = sframe;
   p.dst = base + offset; p.dst_step = dstep; p.dst_frame_stride = dframe;
   p.rows = rows; p.n_frames = n; p.row_bytes = row_bytes;
-  rip::HeadLaunchInfo info = {};
+  rip::LaunchInfo info = {};
   if (!rip::launch_head_copy(p, nullptr, &info)) { printf("refused %zu x %d\n", row_bytes, rows); return 1; }
   if (strcmp(info.kernel, "head_copy_kernel") != 0 || info.grid_x != (unsigned)((row_bytes + 4095) / 4096) || info.grid_y != (unsigned)rows || info.block != 256) {
     printf("launch record %s %u %u %u\n", info.kernel, info.grid_x, info.grid_y, info.block);

@@ -104,7 +104,7 @@ int main(int argc, char** argv) {
     Case c;
     if (!make_case(c, h, in)) { printf("case %d: cannot be set up\n", i); return 2; }
     if (i == 0) bad += refusals(c.p);
-    rip::JpegLaunchInfo info[4] = {};
+    rip::LaunchInfo info[4] = {};
     const bool ok = rip::launch_jpeg_transform(c.p, nullptr, &info[0]) && rip::launch_jpeg_size(c.p, nullptr, &info[1]) &&
                     rip::launch_jpeg_scan(c.p, nullptr, &info[2]) && rip::launch_jpeg_write(c.p, nullptr, &info[3]);
     const unsigned intervals = (unsigned)rip::jpeg_intervals(c.p.rows, c.p.channels, c.p.restart_rows);

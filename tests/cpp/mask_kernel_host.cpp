@@ -33,7 +33,7 @@ static int threshold_cases() {
       std::vector<uint8_t> was(step * rows);
       for (size_t i = 0; i < step * rows; i++) was[i] = img[i] = (uint8_t)((i * 37u + (i >> 3)) % 5 == 0 ? 255 : (i * 131u + 7u) % 256);
       rip::MaskThresholdParams t = {img, step, rows, w};
-      rip::MaskLaunchInfo info = {};
+      rip::LaunchInfo info = {};
       if (!rip::launch_mask_threshold(t, nullptr, &info) || strcmp(info.kernel, "mask_threshold_kernel") != 0) { printf("threshold refused width %d\n", w); bad++; }
       for (size_t i = 0; i < step * rows && !bad; i++) {
         const bool touched = i % step < (((size_t)w + 3) & ~(size_t)3);  // the dwords that hold a pixel; the rest of the pitch stays
@@ -95,7 +95,7 @@ int main(int argc, char** argv) {
     rip::RectMaskParams p = {};
     p.map_xy = maps; p.drows = drows; p.dcols = dcols; p.src_rows = h[2]; p.src_cols = h[3];
     p.dst = (uint8_t*)dblock + dst_off; p.dst_step = pitch; p.binary = binary;
-    rip::MaskLaunchInfo info = {};
+    rip::LaunchInfo info = {};
     if (!rip::launch_rect_mask(p, nullptr, &info)) { printf("case %d refused\n", i); bad++; }
     else if (strcmp(info.kernel, binary ? "rect_mask_kernel<true>" : "rect_mask_kernel<false>") != 0 || info.grid_x != (unsigned)((dcols + 1023) / 1024) ||
              info.grid_y != (unsigned)drows || info.block != 256) {

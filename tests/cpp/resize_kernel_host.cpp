@@ -38,7 +38,7 @@ static int run(int R, int C, int H, int W, int cn, int n, size_t dst_pad, size_t
   p.dst = dst; p.dst_step = dstep; p.dst_frame_stride = dframe;
   p.src_rows = R; p.src_cols = C; p.rows = H; p.cols = W; p.channels = cn; p.n_frames = n; p.area2 = area;
   p.xofs = xofs; p.alpha = alpha; p.yofs = yofs; p.beta = beta;
-  rip::ResizeLaunchInfo info;
+  rip::LaunchInfo info;
   if (!rip::launch_resize(p, nullptr, &info)) { printf("refused %d %d %d %d\n", R, C, H, W); return 1; }
   // expectation: every byte of the buffer
   std::vector<uint8_t> want(total, 0xA5), tight((size_t)R * C * cn), out((size_t)H * W * cn);

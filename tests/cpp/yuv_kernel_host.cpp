@@ -66,7 +66,7 @@ int main(int argc, char** argv) {
     p.rows = rows; p.cols = cols; p.n_frames = frames; p.semi_planar = semi;
     for (int k = 0; k < 3; k++) p.m.y[k] = m[k], p.m.cb[k] = m[3 + k], p.m.cr[k] = m[6 + k];
     p.m.yoff = m[9];
-    rip::YuvLaunchInfo info = {};
+    rip::LaunchInfo info = {};
     const unsigned groups = (unsigned)((rows / 2 + rip::kYuvPairsPerBlock - 1) / rip::kYuvPairsPerBlock);
     if (!rip::launch_yuv420(p, nullptr, &info)) { printf("case %d refused\n", i); bad++; }
     else if (strcmp(info.kernel, semi ? "yuv420_kernel<true>" : "yuv420_kernel<false>") != 0 ||

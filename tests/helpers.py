@@ -1,5 +1,8 @@
 """Shared test helpers: one stage configuration applied both to the HIP pipeline (through the public
 setters, as a reference caller would) and to the CPU oracle."""
+import os
+import subprocess
+
 import numpy as np
 
 from raw_image_pipeline_amd import synth
@@ -99,6 +102,35 @@ def expected_mht(O, c, frame, pattern, ccc=None, taps=False):
     (tests/mht_reference.py).  Returns what oracle_run returns: (out, encoding[, debayered tap, colour tap])."""
     from mht_reference import mht_reference
     return oracle_run(O, c, mht_reference(frame, pattern), "bgr8", ccc=ccc, taps=taps)
+
+
+# ---- kernels run on the host (tests/cpp/*_kernel_host.cpp) --------------------------------------------
+TESTS = os.path.dirname(os.path.abspath(__file__))
+CPP = os.path.join(TESTS, "cpp")
+CSRC = os.path.join(os.path.dirname(TESTS), "raw_image_pipeline_amd", "csrc")
+HOST_SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
+
+
+def host_clangxx():
+    """The clang++ that stands next to hipcc."""
+    from raw_image_pipeline_amd import build as B
+    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
+    if not os.path.exists(clang):
+        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
+    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
+    return clang
+
+
+def build_host_program(tmp_path, name, sources, stub="hip_host_stub", sanitize=False, extra=()):
+    """Compiles a stand-alone program (its own main; device code as host code through tests/cpp/<stub>) with host_clangxx() and
+    returns the executable's path.  sources: paths, or names under tests/cpp; extra: further flags, objects and libraries.
+    sanitize: HOST_SANITIZE in the program itself, which then needs nothing around it to run."""
+    exe = str(tmp_path / (name + ("_san" if sanitize else "")))
+    cmd = [host_clangxx(), "-std=c++17", "-O1", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + (HOST_SANITIZE if sanitize else [])
+    cmd += ["-I", os.path.join(CPP, stub), "-I", CSRC] + [os.path.join(CPP, s) for s in sources] + list(extra) + ["-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
 
 
 # ---- device batches in other layouts than tightly packed ----------------------------------------------

@@ -1,8 +1,8 @@
 """CLAHE on the delivered one-channel picture (include/rip.h rip_set_output_clahe; PARITY.md "Local contrast: CLAHE") without a GPU:
 the definition's known answers and properties on tests/clahe_reference.py, the setter / getter / YAML keys per head, the queries,
 refusals and masks on RIP_DEVICE_NONE handles, the C++ facade, and both kernels of csrc/rip_clahe.hip executed on the host phase by
-phase against the reference -- plainly, and under AddressSanitizer + UndefinedBehaviorSanitizer as a stand-alone program when
-RIP_CLAHE_HOST_SANITIZE is set.  Tolerance 0 wherever the library is compared."""
+phase against the reference -- plainly, and under AddressSanitizer + UndefinedBehaviorSanitizer as a stand-alone program.
+Tolerance 0 wherever the library is compared."""
 import math
 import os
 import struct
@@ -13,6 +13,7 @@ import pytest
 
 import clahe_cases as CC
 import clahe_reference as CL
+from helpers import build_host_program
 from raw_image_pipeline_amd import RawImagePipeline
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
@@ -315,24 +316,15 @@ def test_the_masks_do_not_see_it(rip_lib):
 
 
 # ---- the kernels on the host ----------------------------------------------------------------------------------------------------------
-def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path):
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, sanitize):
     """tests/cpp/clahe_kernel_host.cpp: csrc/rip_clahe.hip compiled as host code with the toolchain's clang++; per workgroup of a
     launcher's grid a heap block of exactly the launch's LDS size and the kernel's phases one after another, each for all 256 threads;
-    frames, tables and destinations in exactly sized heap blocks, destinations with sentinels.  RIP_CLAHE_HOST_SANITIZE=1 adds
+    frames, tables and destinations in exactly sized heap blocks, destinations with sentinels.  The second build adds
     -fsanitize=address,undefined to this stand-alone program (no access outside a frame, a table block or the LDS block, no misaligned
     wide access, no signed overflow)."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if os.environ.get("RIP_CLAHE_HOST_SANITIZE") else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "clahe_kernel_host")
-    cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub_lds"), "-I", csrc, os.path.join(cpp, "clahe_kernel_host.cpp"), "-o", exe, "-lm"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "clahe_kernel_host", ["clahe_kernel_host.cpp"], stub="hip_host_stub_lds", sanitize=sanitize,
+                             extra=["-ffp-contract=off", "-Wno-unused-function", "-lm"])
     cases = CC.host_cases()
     assert len(cases) >= 50 and {c.in_place for c in cases} == {0, 1} and {c.offset for c in cases} >= {0, 1, 2, 3}
     assert {(c.width, c.height) for c in cases} >= {s for s, _ in CC.SHAPES} | {CC.LARGE_SHAPE[0]} and {c.clip for c in cases} == set(CC.CLIPS)

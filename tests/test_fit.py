@@ -14,6 +14,7 @@ import pytest
 import fit_cases as FC
 import fit_reference as FR
 import resize_reference as Z
+from helpers import CSRC, build_host_program
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
 from test_resize import neutral, write_params
@@ -364,25 +365,15 @@ def test_the_whole_frame_cases_take_the_four_paths():
         assert FC.geometry(c)[:2] == ((0, 0) + c.size, (0, 0) + c.target) and c.target[0] % 4
 
 
-def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, rip_lib):
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, rip_lib, sanitize):
     """tests/cpp/fit_kernel_host.cpp: csrc/rip_fit.hip compiled as host code with the toolchain's clang++ (-ffp-contract=off), every
     thread of the launchers' grids run in turn from an exactly sized staging image into exactly sized buffers with sentinels,
     tables in exactly sized heap blocks; the geometry is the reference's.  Every byte of the destination is compared: picture,
-    bands, row padding, gaps.  RIP_RESIZE_HOST_SANITIZE=1 adds -fsanitize=address,undefined to this stand-alone program (no
+    bands, row padding, gaps.  The second build adds -fsanitize=address,undefined to this stand-alone program (no
     access outside F or the destination, no misaligned wide access)."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if os.environ.get("RIP_RESIZE_HOST_SANITIZE") else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "fit_kernel_host")
-    cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "fit_kernel_host.cpp"), os.path.join(csrc, "rip_output_tables.cpp"),
-        "-o", exe, "-lm", "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "fit_kernel_host", ["fit_kernel_host.cpp", os.path.join(CSRC, "rip_output_tables.cpp")], sanitize=sanitize,
+                             extra=["-ffp-contract=off", "-lm", "-lpthread"])
     cases = host_cases()
     assert len(cases) >= 200
     cases_path, out_path = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import heads_cases as HC
+from helpers import build_host_program
 from raw_image_pipeline_amd import RawImagePipeline
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
@@ -233,16 +234,6 @@ def test_the_kernel_run_on_the_host_copies_every_byte_and_no_other(tmp_path, san
     launcher's grid run in turn from an exactly sized staging image into an exactly sized destination: row lengths 1 .. 70 and 4095 ..
     4098 bytes, destination phases 0 .. 17, three pitches, 1 and 3 frames; every byte compared, sentinels everywhere else.  The second
     build adds -fsanitize=address,undefined to this stand-alone program: no access outside either block, no misaligned wide access."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = "/opt/rocm/llvm/bin/clang++"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "heads_kernel_host")
-    cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "heads_kernel_host.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "heads_kernel_host", ["heads_kernel_host.cpp"], sanitize=sanitize, extra=["-ffp-contract=off", "-Wall"])
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "7992 cases, 0 bad" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -12,6 +12,7 @@ import warnings
 import numpy as np
 import pytest
 
+from helpers import build_host_program
 import jpeg_reference as JR
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
@@ -377,18 +378,7 @@ def host_cases():
 
 
 def run_host_kernels(tmp_path, sanitize):
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / ("jpeg_kernel_host" + ("_san" if sanitize else "")))
-    cmd = [clang, "-std=c++17", "-O1", "-Wall", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "jpeg_kernel_host.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "jpeg_kernel_host", ["jpeg_kernel_host.cpp"], sanitize=sanitize, extra=["-Wall"])
     cases = host_cases()
     with open(tmp_path / "cases.bin", "wb") as f:
         f.write(struct.pack("<i", len(cases)))

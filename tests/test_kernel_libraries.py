@@ -1,6 +1,6 @@
-"""The companion libraries of raw_image_pipeline_amd/build.py's one table COMPANIONS: the table itself is closed, every library's
+"""The kernel libraries of raw_image_pipeline_amd/build.py's one table KERNEL_LIBRARIES: the table itself is closed, every library's
 tests/*_variant_cases.py table is closed over that library's kernels, no library holds a kernel of another, every library is dated by
-up_to_date() and linked by librip_hip.so.  Reads the symbol tables (the host-side launch stubs) with the parser of
+up_to_date() and linked by librip_hip.so in the table's order.  Reads the symbol tables (the host-side launch stubs) with the parser of
 tests/test_variant_cases.py; no instruction stream."""
 import collections
 import importlib
@@ -18,10 +18,10 @@ from test_variant_cases import instantiations
 # rebuilt when it changes), the stems of the library's kernel names ("^..." is a prefix, anything else a substring) and the row of
 # build.py as literals.
 Lib = collections.namedtuple("Lib", "cases abi header stems so sources headers")
-RESIZE_SHARED = ["rip_resize_dev.hpp", "rip_resize.hpp", "rip_area.hpp"]
+RESIZE_SHARED = ["rip_resize_dev.hpp", "rip_resize.hpp", "rip_area.hpp", "rip_launch_info.hpp"]
 LIBS = collections.OrderedDict([
     ("out", Lib("output_variant_cases", ["rip_set_output_format"], "rip_output.hpp", ["output_convert"],
-                "librip_out_hip.so", ["rip_output.hip"], ["rip_output.hpp"])),
+                "librip_out_hip.so", ["rip_output.hip"], ["rip_output.hpp", "rip_launch_info.hpp"])),
     ("rsz", Lib("resize_variant_cases", ["rip_set_output_size"], "rip_resize.hpp", ["resize_kernel"],
                 "librip_rsz_hip.so", ["rip_resize.hip"], RESIZE_SHARED)),
     ("area", Lib("area_variant_cases", ["rip_set_output_interpolation", "rip_debug_resize_area_tables"], "rip_area.hpp", ["area_reduce_kernel"],
@@ -31,11 +31,15 @@ LIBS = collections.OrderedDict([
     ("aa", Lib("aa_variant_cases", ["rip_set_output_interpolation", "rip_debug_resize_aa_tables"], "rip_aa.hpp", ["aa_kernel"],
                "librip_aa_hip.so", ["rip_aa.hip"], ["rip_aa.hpp", "rip_aa_dev.hpp"] + RESIZE_SHARED)),
     ("heads", Lib("heads_variant_cases", ["rip_apply_device_heads", "rip_debug_output_head_info"], "rip_heads.hpp", ["head_copy_kernel"],
-                  "librip_heads_hip.so", ["rip_heads.hip"], ["rip_heads.hpp"])),
+                  "librip_heads_hip.so", ["rip_heads.hip"], ["rip_heads.hpp", "rip_launch_info.hpp"])),
     ("mask", Lib("mask_variant_cases", ["rip_set_rect_mask", "rip_get_rect_mask_mode", "rip_get_output_mask", "rip_get_output_mask_device", "rip_debug_rect_mask_info"],
-                 "rip_mask.hpp", ["rect_mask", "mask_threshold"], "librip_mask_hip.so", ["rip_mask.hip"], ["rip_mask.hpp", "rip_round_map.hpp"])),
+                 "rip_mask.hpp", ["rect_mask", "mask_threshold"], "librip_mask_hip.so", ["rip_mask.hip"], ["rip_mask.hpp", "rip_round_map.hpp", "rip_launch_info.hpp"])),
     ("yuv", Lib("yuv_variant_cases", ["rip_set_output_yuv_matrix", "rip_get_output_yuv_matrix"], "rip_yuv.hpp", ["yuv420"],
-                "librip_yuv_hip.so", ["rip_yuv.hip"], ["rip_yuv.hpp"])),
+                "librip_yuv_hip.so", ["rip_yuv.hip"], ["rip_yuv.hpp", "rip_launch_info.hpp"])),
+    ("clahe", Lib("clahe_variant_cases", ["rip_set_output_clahe", "rip_get_output_clahe"], "rip_clahe.hpp", ["clahe_"],
+                  "librip_clahe_hip.so", ["rip_clahe.hip"], ["rip_clahe.hpp", "rip_clahe_dev.hpp", "rip_launch_info.hpp"])),
+    ("jpeg", Lib("jpeg_variant_cases", ["rip_set_output_jpeg", "rip_get_output_jpeg", "rip_get_output_jpeg_sizes", "rip_get_output_jpeg_sizes_device", "rip_debug_jpeg_tables"],
+                 "rip_jpeg.hpp", ["jpeg_"], "librip_jpeg_hip.so", ["rip_jpeg.hip"], ["rip_jpeg.hpp", "rip_jpeg_dev.hpp", "rip_yuv.hpp", "rip_launch_info.hpp"])),
 ])
 KEYS = list(LIBS)
 CORE = "librip_hip.so"
@@ -47,10 +51,10 @@ def matches(name, stems):
 
 @pytest.fixture(scope="module")
 def kernels(rip_lib):
-    """Counter of the kernel instantiations of each of the nine libraries, read once."""
+    """Counter of the kernel instantiations of each of the eleven libraries, read once."""
     from raw_image_pipeline_amd import LIB_PATH
     from raw_image_pipeline_amd import build as B
-    found = {c.key: instantiations(c.out) for c in B.COMPANIONS}
+    found = {c.key: instantiations(c.out) for c in B.KERNEL_LIBRARIES}
     found[CORE] = instantiations(LIB_PATH)
     return found
 
@@ -58,23 +62,25 @@ def kernels(rip_lib):
 # ---- the table -----------------------------------------------------------------------------------------------------------------
 def test_the_table_holds_exactly_these_libraries_in_link_order():
     from raw_image_pipeline_amd import build as B
-    assert [c.key for c in B.COMPANIONS] == KEYS == ["out", "rsz", "area", "fit", "aa", "heads", "mask", "yuv"]
-    assert [B.companion(k) for k in KEYS] == list(B.COMPANIONS)
+    assert [c.key for c in B.KERNEL_LIBRARIES] == KEYS == ["out", "rsz", "area", "fit", "aa", "heads", "mask", "yuv", "clahe", "jpeg"]
+    assert [B.kernel_library(k) for k in KEYS] == list(B.KERNEL_LIBRARIES) and all(type(c) is B.KernelLibrary for c in B.KERNEL_LIBRARIES)
     assert "rip_round_map.hpp" in B.HEADERS         # rip_remap_dev.hpp includes it: the remap kernels share the quantiser
-    assert "rip_round_map.hpp" in B.companion("mask").headers
+    assert "rip_round_map.hpp" in B.kernel_library("mask").headers
 
 
 @pytest.mark.parametrize("key", KEYS)
 def test_the_row_is_what_it_was_and_its_files_exist(rip_lib, key):
     from raw_image_pipeline_amd import LIB_PATH
     from raw_image_pipeline_amd import build as B
-    row, lib = B.companion(key), LIBS[key]
+    row, lib = B.kernel_library(key), LIBS[key]
     assert os.path.basename(row.out) == lib.so and row.sources == lib.sources and set(row.headers) == set(lib.headers)
     assert row.build_dir == "build_" + key
     assert os.path.exists(row.out) and os.path.dirname(row.out) == os.path.dirname(LIB_PATH)
     for f in row.sources + row.headers:
         assert os.path.exists(os.path.join(B.CSRC, f)), f
     assert lib.header in row.headers and lib.header in B.HEADERS
+    assert not [h for h in row.headers if h.endswith("_dev.hpp") and h in B.HEADERS]      # librip_hip.so sees the interface alone
+    assert "rip_launch_info.hpp" in row.headers and "rip_launch_info.hpp" in B.HEADERS
     for name in lib.abi:
         assert hasattr(rip_lib, name), name
 
@@ -104,7 +110,7 @@ def test_the_librarys_kernels_carry_its_stems_and_no_other_librarys_do(kernels, 
 
 
 def test_no_two_libraries_hold_the_same_instantiation(kernels):
-    assert len(kernels) == 9
+    assert len(kernels) == 11
     for a, b in itertools.combinations(kernels, 2):
         assert not (set(kernels[a]) & set(kernels[b])), (a, b)
 
@@ -123,25 +129,32 @@ def test_the_core_library_has_gained_no_kernel(kernels):
 # ---- dating and link ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key", KEYS)
 def test_up_to_date_looks_at_the_librarys_file(rip_lib, key):
-    """Older than its source, the library is out of date -- for its own check, for the check of all and for up_to_date()."""
+    """Older than its sources and headers, the library is out of date -- for its own check, for the check of all and for
+    up_to_date(); every other library's own check keeps its meaning."""
     from raw_image_pipeline_amd import build as B
-    row = B.companion(key)
-    fresh = lambda: (B.up_to_date(), B.companion_up_to_date(key), B.companions_up_to_date())
-    assert fresh() == (True, True, True)
+    row = B.kernel_library(key)
+    others = [k for k in KEYS if k != key]
+    fresh = lambda: (B.up_to_date(), B.kernel_library_up_to_date(key), B.kernel_libraries_up_to_date(), [B.kernel_library_up_to_date(k) for k in others])
+    assert fresh() == (True, True, True, [True] * 9)
     before = os.stat(row.out)
     try:
-        os.utime(row.out, (before.st_atime, os.path.getmtime(os.path.join(B.CSRC, row.sources[0])) - 10))
-        assert fresh() == (False, False, False)
+        os.utime(row.out, (before.st_atime, min(os.path.getmtime(os.path.join(B.CSRC, f)) for f in row.sources + row.headers) - 10))
+        assert fresh() == (False, False, False, [True] * 9)
     finally:
         os.utime(row.out, (before.st_atime, before.st_mtime))
-    assert fresh() == (True, True, True)
+    assert fresh() == (True, True, True, [True] * 9)
 
 
 @pytest.mark.parametrize("key", KEYS)
 def test_the_core_library_links_the_library_through_origin(rip_lib, key):
+    """... in the table's order, and the library carries its own file name as its soname."""
     from raw_image_pipeline_amd import LIB_PATH
+    from raw_image_pipeline_amd import build as B
     needed = subprocess.run(["readelf", "-d", LIB_PATH], capture_output=True, text=True).stdout
     assert LIBS[key].so in needed and "$ORIGIN" in needed
+    assert re.findall(r"\(NEEDED\).*\[(librip_\w+_hip\.so)\]", needed) == [lib.so for lib in LIBS.values()]
+    own = subprocess.run(["readelf", "-d", B.kernel_library(key).out], capture_output=True, text=True).stdout
+    assert re.findall(r"\(SONAME\).*\[(.*)\]", own) == [LIBS[key].so]
 
 
 # ---- what each library's cases promise beyond their names --------------------------------------------------------------------------

@@ -1,8 +1,7 @@
 """Valid-pixel masks (include/rip.h rip_set_rect_mask, rip_get_output_mask; PARITY.md "Rect mask") without a GPU: defaults, the setter
 and getter, the YAML key, the C++ facade, the geometry and the refusals of rip_get_output_mask against rip_query_output for every head
 set of tests/heads_cases.py, and the kernels of csrc/rip_mask.hip executed on the host thread by thread against the oracle's remap of
-a white image -- plainly, and under AddressSanitizer + UndefinedBehaviorSanitizer as a stand-alone program when
-RIP_RESIZE_HOST_SANITIZE is set (the switch of the resize stage's host tests).  Everything at tolerance 0."""
+a white image -- plainly, and under AddressSanitizer + UndefinedBehaviorSanitizer as a stand-alone program.  Everything at tolerance 0."""
 import ctypes as C
 import os
 import struct
@@ -13,6 +12,7 @@ import pytest
 
 import heads_cases as HC
 import mask_cases as MC
+from helpers import build_host_program
 from raw_image_pipeline_amd import RawImagePipeline
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
@@ -231,23 +231,13 @@ def test_the_expectations_hold_every_class(oracle):
         assert {0, 255} <= seen and seen - {0, 255}, (src, sorted(seen))          # outside, inside and partly covered entries
 
 
-def test_the_kernels_run_on_the_host_equal_the_oracles_remap_of_white(tmp_path, oracle):
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_kernels_run_on_the_host_equal_the_oracles_remap_of_white(tmp_path, oracle, sanitize):
     """tests/cpp/mask_kernel_host.cpp: csrc/rip_mask.hip compiled as host code with the toolchain's clang++, every thread of the
     launcher's grid run in turn from exactly sized maps into exactly sized masks with sentinels behind every row, at tight, 16-byte and
-    odd pitches, BINARY both ways.  RIP_RESIZE_HOST_SANITIZE=1 adds -fsanitize=address,undefined to this stand-alone program (no
+    odd pitches, BINARY both ways.  The second build adds -fsanitize=address,undefined to this stand-alone program (no
     out-of-bounds access, no misaligned wide access)."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if os.environ.get("RIP_RESIZE_HOST_SANITIZE") else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "mask_kernel_host")
-    cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "mask_kernel_host.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "mask_kernel_host", ["mask_kernel_host.cpp"], sanitize=sanitize, extra=["-ffp-contract=off", "-Wall"])
     cases = host_cases(oracle)
     assert len(cases) == 6 * (16 + 3 + 2 * 13)
     cases_path, out_path = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")

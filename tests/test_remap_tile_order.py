@@ -1,11 +1,10 @@
 """The order in which the ring remap kernels visit their tiles (csrc/rip_tile_deal.hpp), walked on the host: every run length and
 order enumerates every tile exactly once.  No GPU."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import build_host_program
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
@@ -16,16 +15,6 @@ def test_every_order_and_run_length_visits_every_tile_exactly_once(tmp_path, san
     XCDs without work), the sizes of the GPU suite, the three benchmark sizes 2448 x 2048, 1920 x 1200, 3840 x 2160, and the widest
     and the highest plan the launchers accept.  Run lengths 0 (contiguous) to 2^20 tile rows, orders row-major, column strips, column strips
     where they deal out evenly, and an unknown one.  The second build adds -fsanitize=address,undefined to this stand-alone program."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = "/opt/rocm/llvm/bin/clang++"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "tile_deal_test")
-    cmd = [clang, "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "tile_deal_test.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "tile_deal_test", ["tile_deal_test.cpp"], sanitize=sanitize, extra=["-Wall", "-Werror"])
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "3696 cases, 0 bad" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

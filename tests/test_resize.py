@@ -11,6 +11,7 @@ import pytest
 import output_reference as R
 import resize_reference as Z
 from raw_image_pipeline_amd import pipeline as P
+from helpers import CSRC, HOST_SANITIZE, build_host_program, host_clangxx
 from raw_image_pipeline_amd import synth
 from test_cpp_facade import BRANCHES, run_env
 
@@ -326,27 +327,18 @@ def test_facade_sets_gets_and_throws(tmp_path, rip_lib, branch):
 
 
 # ---- the kernel, executed on the host ----------------------------------------------------------------------------------------
-def test_the_kernel_run_on_the_host_equals_the_oracle_byte_for_byte(tmp_path, rip_lib, oracle):
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_kernel_run_on_the_host_equals_the_oracle_byte_for_byte(tmp_path, rip_lib, oracle, sanitize):
     """tests/cpp/resize_kernel_host.cpp: csrc/rip_resize.hip compiled as host code, every thread of the launcher's grid run in turn,
     both channel counts x the widths around the lane and the workgroup x down- / upscale / the 2 x 2 path x pitches, offsets and
-    frame gaps, plus 3000 seeded cases; exactly sized buffers with sentinels.  RIP_RESIZE_HOST_SANITIZE=1 adds
-    -fsanitize=address,undefined to this stand-alone program (no out-of-bounds access, no misaligned wide access)."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if os.environ.get("RIP_RESIZE_HOST_SANITIZE") else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    obj, exe = str(tmp_path / "rip_oracle.o"), str(tmp_path / "resize_kernel_host")
-    cc = os.path.join(os.path.dirname(clang), "clang")
-    r = subprocess.run([cc, "-O1", "-c", "-x", "c"] + san + [os.path.join(ROOT, "oracle", "rip_oracle.c"), "-I", os.path.join(ROOT, "oracle"), "-o", obj],
+    frame gaps, plus 3000 seeded cases; exactly sized buffers with sentinels.  The second build adds -fsanitize=address,undefined
+    to this stand-alone program (no out-of-bounds access, no misaligned wide access)."""
+    obj = str(tmp_path / "rip_oracle.o")
+    cc = os.path.join(os.path.dirname(host_clangxx()), "clang")
+    r = subprocess.run([cc, "-O1", "-c", "-x", "c"] + (HOST_SANITIZE if sanitize else []) + [os.path.join(ROOT, "oracle", "rip_oracle.c"), "-I", os.path.join(ROOT, "oracle"), "-o", obj],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "resize_kernel_host.cpp"), os.path.join(csrc, "rip_output_tables.cpp"), obj,
-        "-o", exe, "-lm", "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "resize_kernel_host", ["resize_kernel_host.cpp", os.path.join(CSRC, "rip_output_tables.cpp")], sanitize=sanitize,
+                             extra=["-ffp-contract=off", obj, "-lm", "-lpthread"])
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "3376 cases, 0 bad" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

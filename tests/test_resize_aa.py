@@ -13,6 +13,7 @@ import pytest
 
 import aa_cases as AC
 import aa_reference as A
+from helpers import CSRC, build_host_program
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
 from test_resize import neutral, write_params
@@ -369,24 +370,14 @@ def host_cases():
     return out
 
 
-def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, rip_lib):
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, rip_lib, sanitize):
     """tests/cpp/aa_kernel_host.cpp: csrc/rip_aa.hip compiled as host code with the toolchain's clang++; per workgroup of the
     launcher's grid a heap block of exactly the launch's LDS size, phase 1 for all 256 threads, then phase 2; frames and tables in
-    exactly sized heap blocks, destinations with sentinels.  RIP_RESIZE_HOST_SANITIZE=1 adds -fsanitize=address,undefined to this
+    exactly sized heap blocks, destinations with sentinels.  The second build adds -fsanitize=address,undefined to this
     stand-alone program (no out-of-bounds access to a frame, a table or the LDS block, no misaligned wide access, no signed overflow)."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if os.environ.get("RIP_RESIZE_HOST_SANITIZE") else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "aa_kernel_host")
-    cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub_lds"), "-I", csrc, os.path.join(cpp, "aa_kernel_host.cpp"), os.path.join(csrc, "rip_output_tables.cpp"),
-        "-o", exe, "-lm", "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "aa_kernel_host", ["aa_kernel_host.cpp", os.path.join(CSRC, "rip_output_tables.cpp")], stub="hip_host_stub_lds", sanitize=sanitize,
+                             extra=["-ffp-contract=off", "-lm", "-lpthread"])
     cases = host_cases()
     assert len(cases) >= 150
     assert {c[14] for c in cases} >= {0, 1, 2, 4, 8} and {(c[3] * c[9]) % 4 for c in cases if c[9] == 3} == {0, 1, 2, 3}

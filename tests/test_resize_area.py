@@ -12,6 +12,7 @@ import pytest
 
 import area_cases as AC
 import area_reference as A
+from helpers import CSRC, build_host_program
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
 from test_resize import neutral, write_params
@@ -308,24 +309,14 @@ def host_cases():
     return out
 
 
-def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, rip_lib):
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_kernels_run_on_the_host_equal_the_reference_byte_for_byte(tmp_path, rip_lib, sanitize):
     """tests/cpp/area_kernel_host.cpp: csrc/rip_area.hip compiled as host code with the toolchain's clang++ (-ffp-contract=off), every
     thread of the launcher's grid run in turn into exactly sized buffers with sentinels, tables in exactly sized heap blocks.
-    RIP_RESIZE_HOST_SANITIZE=1 adds -fsanitize=address,undefined to this stand-alone program (no out-of-bounds access, no
+    The second build adds -fsanitize=address,undefined to this stand-alone program (no out-of-bounds access, no
     misaligned wide access)."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if os.environ.get("RIP_RESIZE_HOST_SANITIZE") else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "area_kernel_host")
-    cmd = [clang, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "area_kernel_host.cpp"), os.path.join(csrc, "rip_output_tables.cpp"),
-        "-o", exe, "-lm", "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_program(tmp_path, "area_kernel_host", ["area_kernel_host.cpp", os.path.join(CSRC, "rip_output_tables.cpp")], sanitize=sanitize,
+                             extra=["-ffp-contract=off", "-lm", "-lpthread"])
     cases = host_cases()
     assert len(cases) >= 100
     cases_path, out_path = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")

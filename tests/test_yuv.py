@@ -2,7 +2,7 @@
 a GPU: the definition's known answers and properties on tests/yuv_reference.py, an independent check against Pillow where it imports,
 the setter / getter / YAML key per head, the queries on RIP_DEVICE_NONE handles against hand-computed values, the refusals and their
 order, the C++ facade, and the kernel of csrc/rip_yuv.hip executed on the host thread by thread against the reference -- plainly, and
-under AddressSanitizer + UndefinedBehaviorSanitizer as a stand-alone program when RIP_RESIZE_HOST_SANITIZE is set.  Tolerance 0."""
+under AddressSanitizer + UndefinedBehaviorSanitizer as a stand-alone program.  Tolerance 0."""
 import os
 import struct
 import subprocess
@@ -12,6 +12,7 @@ import pytest
 
 import output_reference
 import yuv_reference as Y
+from helpers import build_host_program
 from raw_image_pipeline_amd import RawImagePipeline
 from raw_image_pipeline_amd import pipeline as P
 from test_cpp_facade import BRANCHES, run_env
@@ -322,22 +323,12 @@ def frame_total(h, w, semi, pitch):
     return h * pitch + (h // 2) * (pitch // 2) + (h // 2 - 1) * (pitch // 2) + w // 2
 
 
-def test_the_kernel_run_on_the_host_equals_the_reference(tmp_path):
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_the_kernel_run_on_the_host_equals_the_reference(tmp_path, sanitize):
     """tests/cpp/yuv_kernel_host.cpp: csrc/rip_yuv.hip compiled as host code with the toolchain's clang++, every thread of the
     launcher's grid run in turn from exactly sized sources into exactly sized destinations with sentinels around every row.
-    RIP_RESIZE_HOST_SANITIZE=1 adds -fsanitize=address,undefined to this stand-alone program."""
-    from raw_image_pipeline_amd import build as B
-    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(B.hipcc()))), "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = os.path.join(os.path.dirname(os.path.realpath(B.hipcc())), "clang++")
-    assert os.path.exists(clang), "clang++ of the ROCm toolchain not found next to hipcc"
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"] if os.environ.get("RIP_RESIZE_HOST_SANITIZE") else []
-    cpp, csrc = os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "raw_image_pipeline_amd", "csrc")
-    exe = str(tmp_path / "yuv_kernel_host")
-    cmd = [clang, "-std=c++17", "-O1", "-Wall", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__"] + san + [
-        "-I", os.path.join(cpp, "hip_host_stub"), "-I", csrc, os.path.join(cpp, "yuv_kernel_host.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    The second build adds -fsanitize=address,undefined to this stand-alone program."""
+    exe = build_host_program(tmp_path, "yuv_kernel_host", ["yuv_kernel_host.cpp"], sanitize=sanitize, extra=["-Wall"])
     cases = host_cases()
     assert len(cases) == 10 * 4 * 2 + 4 * 2 * 3 * 4
     cases_path, out_path = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")

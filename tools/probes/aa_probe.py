@@ -52,7 +52,7 @@ ptr = lambda a: a.ctypes.data_as(C.c_void_p)
 
 
 def area_launch(lib, frames, dst):
-    launch = getattr(C.CDLL(B.companion("area").out), "_ZN3rip18launch_area_reduceERKNS_10AreaParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
+    launch = getattr(C.CDLL(B.kernel_library("area").out), "_ZN3rip18launch_area_reduceERKNS_10AreaParamsEP12ihipStream_tPNS_10LaunchInfoE")
     launch.restype = C.c_bool
     xf, xc, xw = np.zeros(W, np.int32), np.zeros(W, np.int32), np.zeros(C_ + 2 * W, np.float32)
     yf, yc, yw = np.zeros(H, np.int32), np.zeros(H, np.int32), np.zeros(R_ + 2 * H, np.float32)
@@ -70,7 +70,7 @@ def area_launch(lib, frames, dst):
 
 
 def aa_launch(lib, name, frames, dst):
-    launch = getattr(C.CDLL(B.companion("aa").out), "_ZN3rip9launch_aaERKNS_8AaParamsERKNS_9FitWindowEP12ihipStream_tPNS_16ResizeLaunchInfoE")
+    launch = getattr(C.CDLL(B.kernel_library("aa").out), "_ZN3rip9launch_aaERKNS_8AaParamsERKNS_9FitWindowEP12ihipStream_tPNS_10LaunchInfoE")
     launch.restype = C.c_bool
     S = 2 if name == "cubic_aa" else 1
     xf, xc, xo, xw = np.zeros(W, np.int32), np.zeros(W, np.int32), np.zeros(W, np.int32), np.zeros(2 * S * C_ + W, np.int16)

@@ -150,8 +150,8 @@ def main():
         res["bar_c_at_most_1_05_a"] = res["ratio_c_over_a"] <= 1.05
 
     # e: the copy kernel alone, from a staging image of F's padded pitch into the shifted buffer
-    lib = C.CDLL(B.companion("heads").out)
-    launch = getattr(lib, "_ZN3rip16launch_head_copyERKNS_14HeadCopyParamsEP12ihipStream_tPNS_14HeadLaunchInfoE")
+    lib = C.CDLL(B.kernel_library("heads").out)
+    launch = getattr(lib, "_ZN3rip16launch_head_copyERKNS_14HeadCopyParamsEP12ihipStream_tPNS_10LaunchInfoE")
     launch.restype = C.c_bool
     staging = torch.empty(n * H * row, dtype=torch.uint8, device="cuda")
     prm = HeadCopyParams(staging.data_ptr(), row, row * H, shifted.data_ptr(), row, row * H, H, n, row)

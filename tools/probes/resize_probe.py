@@ -75,7 +75,7 @@ class AreaParams(C.Structure):
 
 def linear_launch(lib, rsz, frames, dst, H, W):
     """(callable that enqueues resize_kernel on the current stream, kernel name, objects to keep alive)"""
-    launch = getattr(rsz, "_ZN3rip13launch_resizeERKNS_12ResizeParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
+    launch = getattr(rsz, "_ZN3rip13launch_resizeERKNS_12ResizeParamsEP12ihipStream_tPNS_10LaunchInfoE")
     launch.restype = C.c_bool
     wp = (W + 3) // 4 * 4
     xofs, alpha = np.zeros(wp, np.int32), np.zeros((wp, 2), np.int16)
@@ -94,7 +94,7 @@ def linear_launch(lib, rsz, frames, dst, H, W):
 
 
 def area_launch(lib, frames, dst, H, W):
-    launch = getattr(C.CDLL(B.companion("area").out), "_ZN3rip18launch_area_reduceERKNS_10AreaParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
+    launch = getattr(C.CDLL(B.kernel_library("area").out), "_ZN3rip18launch_area_reduceERKNS_10AreaParamsEP12ihipStream_tPNS_10LaunchInfoE")
     launch.restype = C.c_bool
     xf, xc, xw = np.zeros(W, np.int32), np.zeros(W, np.int32), np.zeros(C_ + 2 * W, np.float32)
     yf, yc, yw = np.zeros(H, np.int32), np.zeros(H, np.int32), np.zeros(R_ + 2 * H, np.float32)
@@ -118,7 +118,7 @@ def interpolation_main():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import area_reference as A
     lib = load_library()
-    rsz = C.CDLL(B.companion("rsz").out)
+    rsz = C.CDLL(B.kernel_library("rsz").out)
     g = torch.Generator(device="cuda").manual_seed(1)
     frames = torch.randint(0, 256, (N, R_, C_, 3), dtype=torch.uint8, device="cuda", generator=g)
     say("frames %d x %d x %d x 3 uint8 = %.1f MB resident; HIP events around 4 launches, 5 rounds per kernel alternating area / linear, after 2 "
@@ -212,8 +212,8 @@ def main():
     if INTERPOLATION:
         return interpolation_main()
     lib = load_library()
-    rsz = C.CDLL(B.companion("rsz").out)
-    launch = getattr(rsz, "_ZN3rip13launch_resizeERKNS_12ResizeParamsEP12ihipStream_tPNS_16ResizeLaunchInfoE")
+    rsz = C.CDLL(B.kernel_library("rsz").out)
+    launch = getattr(rsz, "_ZN3rip13launch_resizeERKNS_12ResizeParamsEP12ihipStream_tPNS_10LaunchInfoE")
     launch.restype = C.c_bool
     g = torch.Generator(device="cuda").manual_seed(1)
     frames = torch.randint(0, 256, (N, R_, C_, 3), dtype=torch.uint8, device="cuda", generator=g)
